@@ -2,6 +2,20 @@
 """Benchmark of the MI355X Smith-Waterman score path (BASELINE.json metric: GCUPS).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload auto|pair|batch|slab]
+                    [--full] [--dump-outputs DIR]
+
+A plain run does what the headline figure needs and no more: it puts the step's input in
+HBM, warms up, times K steps of the hot path and prints one JSON line (`value`,
+`ms_per_step`, the kernel that ran, parity of the timed score against the committed golden).
+--full adds every other measurement to that line: the roofline (with the traced launch of
+`step_ns`), `host_api`, the batched config and the int32 kernels after it, the affine step,
+the C5 and byte-alphabet launches and the CPU baseline (--no-extra, --no-c5,
+--no-cpu-baseline and --cpu-seconds trim that set).  The committed lines under profiles/
+and the numbers the documents quote are --full lines.
+--dump-outputs DIR writes what the timed path returned in its last timed step, the int32
+scores a caller receives (one per pair of the job, in global order; the slab workload's one
+score), to DIR/scores.npy as float64.  The inputs are seeded, so two builds run with the
+same arguments can be compared score for score.
 
 Ranks: one process per GPU.  Under torchrun (RANK/WORLD_SIZE set) this process
 is one rank; standalone with --gpus N > 1 it checks that N GPUs are visible
@@ -23,13 +37,13 @@ cudaSmithM.cu:200-212, sequences resident in HBM before the timed region):
          the pipeline fill are reported beside `value`.
   auto   `value` is the pair workload at every N (C2 at N=1: configs[1], the
          metric's single-GPU config), so the 1/2/4/8 series compares the same
-         per-GPU work.  The batched config is measured after it on the same
-         ranks and reported as "batch_c3" (N=1) or "batch_c4" (N>1: 1024 pairs
-         per GPU, C4 at N=8; north_star's >= 7.5x is stated on batched pairs).
+         per-GPU work.  With --full the batched config is measured after it on
+         the same ranks and reported as "batch_c3" (N=1) or "batch_c4" (N>1: 1024
+         pairs per GPU, C4 at N=8; north_star's >= 7.5x is stated on batched pairs).
 A step is one full pass of the hot path over the step's input; `value` is the
 whole-job GCUPS (sum of n*m over all ranks' pairs / max-over-ranks time).
 
-Roofline: the kernels keep H/E/F in registers, so the bound
+Roofline (--full): the kernels keep H/E/F in registers, so the bound
 that applies is VALU issue, not HBM.  `roofline.achieved` = VALU lane-ops of one
 launch (rocprofv3 SQ_INSTS_VALU x 64, profiles/pmc_<workload>.json, valid only
 for the same libswmi355.so, checked by sha256) / the launch time measured here;
@@ -72,16 +86,28 @@ def parse():
                     help="slab workload, one GPU: time slab 0 of a K-way column split alone (per-rank cost)")
     ap.add_argument("--n", type=int, default=0, help="override sequence length")
     ap.add_argument("--pairs-per-gpu", type=int, default=1024)
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the CPU baseline leg")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="N=1 auto: skip the extra C3 / affine / C5 measurements")
-    ap.add_argument("--no-c5", action="store_true", help="N=1 auto: skip the extra C5 (N=2^20) launches")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: roofline, host_api, the batched / affine / C5 / byte-alphabet extras "
+                         "and the CPU baseline (off: the timed steps and the result line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the scores of the last timed step to DIR/scores.npy (float64)")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="--full: budget of the CPU baseline leg")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline leg")
+    ap.add_argument("--no-extra", action="store_true",
+                    help="--full, N=1 auto: skip the extra C3 / affine / C5 measurements")
+    ap.add_argument("--no-c5", action="store_true", help="--full, N=1 auto: skip the extra C5 (N=2^20) launches")
     ap.add_argument("--W", type=int, default=0)
     ap.add_argument("--C", type=int, default=0)
     ap.add_argument("--mode", type=int, default=-1, help="engine option 'mode' (-1 = automatic plan)")
     ap.add_argument("--params", default="1,-1,1,1", help="MATCH,MISMATCH,G_INIT,G_EXT")
     ap.add_argument("--opt", action="append", default=[], help="engine option key=value (sw_set_option)")
     return ap.parse_args()
+
+
+def dump_outputs(dirname, scores):
+    """--dump-outputs: the scores the timed path returned in its last step, as DIR/scores.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "scores.npy"), np.asarray(scores, dtype=np.float64).reshape(-1))
 
 
 def load_golden():
@@ -791,6 +817,8 @@ def main():
                                                               args.warmup)
         cells_job = cells_rank * world
         per_launch_cells = cells_rank
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, allsc)
         cfg = {"workload": ("C4 batch, %d pairs/GPU (%d pairs)" % (P, P * world)) if world > 1
                else "C3 batch of %d pairs" % P, "N": N, "pairs_per_gpu": P, "global_pairs": P * world,
                "parallelism": "pair-sharded x%d + RCCL gather of scores" % world if world > 1 else "single GPU"}
@@ -874,11 +902,14 @@ def main():
             slabs.close()
         if slab_buf is not None:
             slab_buf.free()
-        if rank == 0 and world == 1 and slab_buf is None:
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, [first] if slabs is not None else
+                         (gathered[0] if gathered[0] is not None else scores).cpu().numpy())
+        if args.full and rank == 0 and world == 1 and slab_buf is None:
             step_ns = measure_step_ns(sw, torch, arena, offs_a, lens, offs_b, scores, sptr, N)
         # PCIe-inclusive rate of the synchronous host entry point (H2D of the two
         # sequences + launch + score D2H): reported beside `value`, never as it
-        if rank == 0 and workload == "pair":
+        if args.full and rank == 0 and workload == "pair":
             a_h, b_h = host[:N], host[N:]
             sw.SmithWatermanScoreCUDA(a_h, b_h)
             calls = 10
@@ -902,20 +933,20 @@ def main():
         # N=1: the general affine step on the same pair (the automatic plan takes the
         # exact linear-gap step at G_INIT == G_EXT), for reference
         affine = None
-        if workload == "pair" and world == 1 and args.workload == "auto" and not args.no_extra and \
+        if args.full and workload == "pair" and world == 1 and args.workload == "auto" and not args.no_extra and \
                 params[2] == params[3]:
             affine = affine_runs(sw, torch, launch, scores, stream, gold, N, args.steps, params, defaults)
         c5 = None
-        if workload == "pair" and world == 1 and args.workload == "auto" and not args.no_extra and \
+        if args.full and workload == "pair" and world == 1 and args.workload == "auto" and not args.no_extra and \
                 not args.no_c5 and defaults and N == 65536:
             c5 = c5_runs(sw, torch, gold, 2)
         alpha = None
-        if workload == "pair" and world == 1 and args.workload == "auto" and not args.no_extra and \
+        if args.full and workload == "pair" and world == 1 and args.workload == "auto" and not args.no_extra and \
                 not args.no_c5 and defaults and N == 65536:
             alpha = alphabet_runs(sw, torch, gold, args.steps)
         # the batched config measured right after on the same ranks, as an extra key:
         # C3 at N=1, 1024 pairs per GPU sharded + RCCL-gathered at N>1 (C4 at N=8)
-        if workload == "pair" and args.workload == "auto" and not args.no_extra:
+        if args.full and workload == "pair" and args.workload == "auto" and not args.no_extra:
             bsteps = max(3, args.steps // 2)
             bt, bk, bsc, bcells, bst = run_batch(sw, torch, dist, world, rank, 8192, 1024, bsteps, 1)
             ref = gold.get("C4", gold.get("C3", {})).get("scores", [])
@@ -977,10 +1008,12 @@ def main():
             "kernel_gcups": round(per_launch_cells / (avg_kern_ms * 1e-3) / 1e9, 3),
             "parity": parity,
             "host_api": host_api,
-            "roofline": roofline((workload if args.slab_of <= 1 else "slab_part") + affine_key(st), per_launch_cells, avg_kern_ms,
-                                 step_ns, cfg["N"], cfg["N"], bool(st["variant"] & 16),
-                                 waves_per_simd=None if workload == "pair" else resident_waves_per_simd(st, torch)),
         }
+        if args.full:
+            out["roofline"] = roofline((workload if args.slab_of <= 1 else "slab_part") + affine_key(st),
+                                       per_launch_cells, avg_kern_ms, step_ns, cfg["N"], cfg["N"],
+                                       bool(st["variant"] & 16),
+                                       waves_per_simd=None if workload == "pair" else resident_waves_per_simd(st, torch))
         if rccl is not None:
             out["rccl_world"] = rccl
         if extra is not None:
@@ -990,7 +1023,7 @@ def main():
         # the scaling series: `value` is the same per-GPU work at every N (one C2-size pair per
         # GPU), so value(N) / (N * value(1)) is the efficiency; the batched series is
         # batch_c4.value(N) against the N = 1 line's batch_c3.value (1024 pairs per GPU in both)
-        if workload == "pair" and args.workload == "auto":
+        if args.full and workload == "pair" and args.workload == "auto":
             out["scaling_note"] = ("value: one C2-size pair (N=%d) per GPU at every N; batched pairs: %s.value "
                                    "vs the N=1 line's batch_c3.value (1024 pairs N=8192 per GPU)"
                                    % (N, "batch_c3" if world == 1 else "batch_c4"))
@@ -1000,7 +1033,7 @@ def main():
             out["c5"] = c5
         if workload != "batch" and alpha is not None:
             out["byte_alphabets"] = alpha
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(workload, cfg["N"], args.cpu_seconds, params)
             except Exception as e:   # the baseline leg must not kill the GPU number

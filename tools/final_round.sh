@@ -10,7 +10,8 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 rm -rf gpurun_out/prof gpurun_out/lines
 bash tools/gpu_run.sh tests smoke
 round=${1:-r06}
+lines=${2:?usage: bash tools/final_round.sh rNN LINES_DIR (where tools/bench_lines.sh writes)}
 bash tools/prof_round.sh c2 c3 c3a c5 c5p8 c2a c5a
 timeout -k 10 120 python tools/pmc_summary.py gpurun_out/prof "$round" > gpurun_out/pmc_summary.log 2>&1
-bash tools/bench_lines.sh
+bash tools/bench_lines.sh "$lines"
 echo "final_round done"

@@ -48,7 +48,7 @@ def block():
     if own:
         line = [json.loads(l) for l in open(own[1]) if l.startswith("{")][-1]
         s = line["summary"]
-        out.append("This round's default bench line (`%s`, `bench.py --steps 10 --warmup 2` on one MI355X, every "
+        out.append("This round's default bench line (`%s`, `bench.py --full --steps 10 --warmup 2` on one MI355X, every "
                    "score checked against its reference-pinned golden):" % os.path.relpath(own[1], ROOT))
         out.append("")
         out.append("| workload | ms per step | GCUPS | parity |")
