@@ -23,7 +23,8 @@ __all__ = [
     "SmithWatermanScoreCUDA", "SmithDiagonalGPU", "score", "score_batch", "score_batch_device",
     "set_params", "get_params", "set_option", "get_option", "last_stats", "gen_pair", "gen_batch",
     "SwError", "LIB_PATH", "SW_FLAG_DNA", "SW_FLAG_BYTES", "slab_bounds", "SlabBuffer", "slab_alloc",
-    "ipc_open", "ipc_close", "score_slab_device", "Database",
+    "ipc_open", "ipc_close", "score_slab_device", "Database", "Matrix", "score_matrix", "score_matrix_batch",
+    "SW_MATRIX_FOLD_CASE",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -162,6 +163,31 @@ def lib() -> ctypes.CDLL:
     L.sw_db_search_db.restype = i
     L.sw_db_close.argtypes = [vp]
     L.sw_db_close.restype = None
+    # substitution matrices (include/algoGPU.h)
+    i8p = ctypes.POINTER(ctypes.c_byte)
+    L.sw_matrix_create.argtypes = [u8p, i, i8p, i, i]
+    L.sw_matrix_create.restype = vp
+    L.sw_matrix_parse.argtypes = [ctypes.c_char_p, ctypes.c_longlong]
+    L.sw_matrix_parse.restype = vp
+    L.sw_matrix_open.argtypes = [ctypes.c_char_p]
+    L.sw_matrix_open.restype = vp
+    L.sw_matrix_size.argtypes = [vp]
+    L.sw_matrix_size.restype = i
+    L.sw_matrix_symbols.argtypes = [vp, u8p]
+    L.sw_matrix_symbols.restype = i
+    L.sw_matrix_score.argtypes = [vp, ctypes.c_ubyte, ctypes.c_ubyte, ctypes.POINTER(i)]
+    L.sw_matrix_score.restype = i
+    L.sw_matrix_free.argtypes = [vp]
+    L.sw_matrix_free.restype = None
+    L.sw_score_matrix.argtypes = [vp, u8p, u8p, i, i, i, i]
+    L.sw_score_matrix.restype = i
+    L.sw_score_matrix_batch.argtypes = [vp, ctypes.POINTER(u8p), ctypes.POINTER(i), ctypes.POINTER(u8p),
+                                        ctypes.POINTER(i), i, i, i, ctypes.POINTER(i)]
+    L.sw_score_matrix_batch.restype = i
+    L.sw_db_search_matrix.argtypes = [vp, vp, u8p, i, i, i, ctypes.POINTER(i)]
+    L.sw_db_search_matrix.restype = i
+    L.sw_db_search_db_matrix.argtypes = [vp, vp, vp, i, i, ctypes.POINTER(i)]
+    L.sw_db_search_db_matrix.restype = i
     _lib = L
     return L
 
@@ -378,6 +404,104 @@ def gen_batch(seed_base: int, npairs: int, length: int) -> np.ndarray:
     arena = np.empty(2 * length * npairs, dtype=np.uint8)
     lib().sw_gen_batch(seed_base, npairs, length, _ptr(arena))
     return arena
+
+
+# ---- substitution-matrix scoring (include/algoGPU.h sw_matrix_*) ---------------------------
+
+SW_MATRIX_FOLD_CASE = 1
+
+
+class Matrix:
+    """A substitution matrix: K distinct byte symbols and a K x K table, ``scores[i][j]`` scoring
+    symbol i of seq1 / the query against symbol j of seq2 / the record (it need not be symmetric).
+    ``other``: the index every byte outside the alphabet maps to, or -1 (such a byte is then an
+    error); ``fold_case``: a-z score as A-Z wherever the lower-case byte is not itself a symbol.
+    No named matrix is built in: ``Matrix.open("BLOSUM62")`` reads a file in the NCBI text format.
+    Immutable; usable from any thread."""
+
+    def __init__(self, symbols=None, scores=None, other: int = -1, fold_case: bool = False, _handle=None):
+        if _handle is None:
+            sym = _u8(symbols)
+            tab = np.ascontiguousarray(scores, dtype=np.int64).reshape(-1)
+            if tab.size != len(sym) * len(sym):
+                raise SwError("matrix: the table is not %d x %d" % (len(sym), len(sym)))
+            if tab.size and (tab.min() < -127 or tab.max() > 127):
+                raise SwError("matrix: an entry is outside [-127, 127]")
+            t8 = tab.astype(np.int8)
+            _handle = lib().sw_matrix_create(_ptr(sym), len(sym), t8.ctypes.data_as(ctypes.POINTER(ctypes.c_byte)),
+                                             int(other), SW_MATRIX_FOLD_CASE if fold_case else 0)
+        if not _handle:
+            raise SwError(lib().sw_last_error().decode(errors="replace"))
+        self._h = ctypes.c_void_p(_handle)
+
+    @classmethod
+    def parse(cls, text) -> "Matrix":
+        """From the NCBI text format ('#' comments, a header line of symbols, K labelled rows)."""
+        if isinstance(text, str):
+            text = text.encode("latin-1")
+        return cls(_handle=lib().sw_matrix_parse(text, len(text)) or 0)
+
+    @classmethod
+    def open(cls, path) -> "Matrix":
+        return cls(_handle=lib().sw_matrix_open(os.fsencode(path)) or 0)
+
+    def _handle(self):
+        if self._h is None:
+            raise SwError("matrix is closed")
+        return self._h
+
+    @property
+    def symbols(self) -> bytes:
+        k = lib().sw_matrix_size(self._handle())
+        out = np.zeros(max(k, 1), dtype=np.uint8)
+        _check(lib().sw_matrix_symbols(self._handle(), _ptr(out)))
+        return out[:k].tobytes()
+
+    def score(self, a, b) -> int:
+        """The entry for bytes (a, b), through the byte-to-code map the kernel uses."""
+        out = ctypes.c_int()
+        _check(lib().sw_matrix_score(self._handle(), int(_u8(a)[0]), int(_u8(b)[0]), ctypes.byref(out)))
+        return out.value
+
+    def close(self) -> None:
+        if self._h is not None and self._h.value:
+            lib().sw_matrix_free(self._h)
+        self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def score_matrix(seq1, seq2, matrix: Matrix, gap_init: int, gap_ext: int) -> int:
+    """Best local-alignment score under ``matrix``; a gap of L residues costs gap_init + (L-1)*gap_ext
+    (BLAST's "open 11, extend 1" is gap_init=12, gap_ext=1)."""
+    a, b = _u8(seq1), _u8(seq2)
+    return _check(lib().sw_score_matrix(matrix._handle(), _ptr(a), _ptr(b), len(a), len(b), int(gap_init), int(gap_ext)))
+
+
+def score_matrix_batch(pairs: Iterable[Sequence], matrix: Matrix, gap_init: int, gap_ext: int) -> list:
+    """Scores of many independent pairs under ``matrix`` in one launch (sw_score_matrix_batch)."""
+    arrs = [(_u8(a), _u8(b)) for a, b in pairs]
+    n = len(arrs)
+    if n == 0:
+        return []
+    u8p = ctypes.POINTER(ctypes.c_ubyte)
+    A = (u8p * n)(*[_ptr(x) for x, _ in arrs])
+    B = (u8p * n)(*[_ptr(y) for _, y in arrs])
+    AL = (ctypes.c_int * n)(*[len(x) for x, _ in arrs])
+    BL = (ctypes.c_int * n)(*[len(y) for _, y in arrs])
+    out = (ctypes.c_int * n)()
+    _check(lib().sw_score_matrix_batch(matrix._handle(), A, AL, B, BL, n, int(gap_init), int(gap_ext), out))
+    return list(out)
 
 
 from .db import Database  # noqa: E402  (FASTA databases, query x database search)

@@ -15,6 +15,7 @@
 // the long tail starts early); scores come back in record order.
 #include "sw_internal.h"
 #include "sw_db_host.h"
+#include "sw_matrix_host.h"
 #include "../../include/algoGPU.h"
 
 #include <algorithm>
@@ -198,12 +199,105 @@ int search_many(sw_db* db, const sw_db* queries, int* scores_out) {
     return sw_stream_status(st);   // a kernel's hand-off timeout surfaces here
 }
 
+// ---- substitution-matrix searches (sw_matrix.hip's kernel over the same arena and query slot) ----
+
+// every residue of the database has a code in mx: checked once per (database, matrix)
+int check_records(sw_db* db, const sw_matrix* mx) {
+    if (db->matrix_ok.count(mx->id)) return 0;
+    const long long bad = matrix_first_bad(mx, db->res.data(), (long long)db->res.size());
+    if (bad >= 0) {
+        // the record that holds residue `bad`: the last one whose offset is <= bad and that is not empty
+        int rec = 0;
+        for (size_t r = 0; r < db->len.size(); ++r)
+            if (db->len[r] > 0 && db->off[r] <= bad && bad < db->off[r] + db->len[r]) rec = (int)r;
+        char m[160];
+        std::snprintf(m, sizeof m, "record %d: position %lld: byte 0x%02x is outside the matrix alphabet", rec,
+                      bad - (long long)db->off[rec], db->res[(size_t)bad]);
+        report_error(m);
+        return -1;
+    }
+    db->matrix_ok.insert(mx->id);
+    return 0;
+}
+
+int check_query(const sw_db* db, const sw_matrix* mx, const unsigned char* query, int qlen, int qidx) {
+    const long long bad = matrix_first_bad(mx, query, qlen);
+    if (bad >= 0) {
+        char m[160];
+        std::snprintf(m, sizeof m, "query %d: position %lld: byte 0x%02x is outside the matrix alphabet", qidx, bad,
+                      query[bad]);
+        report_error(m);
+        return -1;
+    }
+    for (size_t r = 0; r < db->len.size(); ++r) {
+        if ((long long)std::min(qlen, db->len[r]) * mx->max_entry >= (1LL << 28)) {
+            char m[160];
+            std::snprintf(m, sizeof m, "record %d: score range exceeds the int32 engine (min length * largest entry >= 2^28)", (int)r);
+            report_error(m);
+            return -1;
+        }
+    }
+    return 0;
+}
+
+// the query spread across the lanes against every record, longest first; scores in record order
+int search_matrix(sw_db* db, const sw_matrix* mx, const unsigned char* query, int qlen, int gap_init, int gap_ext,
+                  int* scores_out, int qslot, int qidx) {
+    const int nrec = (int)db->len.size();
+    if (nrec == 0) return 0;
+    if (check_records(db, mx) || check_query(db, mx, query, qlen, qidx)) return -1;
+    sw_db::Dev* v = nullptr;
+    if (device_arena(db, std::max(qlen, qslot), &v)) return -1;
+    std::vector<int64_t> b_off;
+    std::vector<int> blen;
+    record_order(db, b_off, blen);
+    const int64_t qoff = (int64_t)db->res.size();
+    if (qlen > 0) DBCHK(hipMemcpy(v->arena + qoff, query, (size_t)qlen, hipMemcpyHostToDevice));
+    std::vector<int64_t> a_off((size_t)nrec, qoff);
+    std::vector<int> alen((size_t)nrec, qlen);
+    if (matrix_score_device(mx, v->arena, a_off.data(), alen.data(), b_off.data(), blen.data(), nrec, gap_init, gap_ext,
+                            v->scores, true))
+        return -1;
+    std::vector<int> got((size_t)nrec);
+    DBCHK(hipMemcpy(got.data(), v->scores, (size_t)nrec * sizeof(int), hipMemcpyDeviceToHost));
+    for (int k = 0; k < nrec; ++k) scores_out[db->order[k]] = got[k];
+    return 0;
+}
+
 }  // namespace
 }  // namespace swmi
 
 using namespace swmi;
 
 extern "C" {
+
+int sw_db_search_matrix(sw_db* db, const sw_matrix* mx, const unsigned char* query, int qlen, int gap_init,
+                        int gap_ext, int* scores_out) {
+    if (!db || !mx || qlen < 0 || (qlen > 0 && !query) || (!db->len.empty() && !scores_out)) {
+        report_error("sw_db_search_matrix: invalid arguments");
+        return -1;
+    }
+    std::lock_guard<std::mutex> g(db->mu);
+    return search_matrix(db, mx, query, qlen, gap_init, gap_ext, scores_out, qlen, 0);
+}
+
+// (one query after another: the pipelining of sw_db_search_db is not done for matrix searches)
+int sw_db_search_db_matrix(sw_db* db, const sw_db* queries, const sw_matrix* mx, int gap_init, int gap_ext,
+                           int* scores_out) {
+    if (!db || !queries || !mx || (!db->len.empty() && !queries->len.empty() && !scores_out)) {
+        report_error("sw_db_search_db_matrix: invalid arguments");
+        return -1;
+    }
+    std::lock_guard<std::mutex> g(db->mu);
+    const size_t nrec = db->len.size();
+    int longest = 0;
+    for (int l : queries->len) longest = std::max(longest, l);
+    for (size_t q = 0; q < queries->len.size(); ++q)
+        if (search_matrix(db, mx, queries->res.data() + queries->off[q], queries->len[q], gap_init, gap_ext,
+                          scores_out + q * nrec, longest, (int)q))
+            return -1;
+    return 0;
+}
 
 int sw_db_search(sw_db* db, const unsigned char* query, int qlen, int* scores_out) {
     if (!db || qlen < 0 || (qlen > 0 && !query) || (!db->len.empty() && !scores_out)) {

@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <map>
 #include <mutex>
+#include <set>
 #include <string>
 #include <vector>
 
@@ -17,6 +18,8 @@ struct sw_db {
     std::vector<std::string> header;    // the '>' line without '>' and line end
     std::vector<int> order;             // record indices, longest first
     int dna = -1;                       // every residue in {A,C,G,T}: 1 / 0, -1 not scanned yet (sw_db.hip)
+    std::set<unsigned long long> matrix_ok;   // ids of the matrices whose alphabet holds every residue (checked once
+                                        // per (database, matrix); sw_db_search_matrix)
     struct Dev {
         unsigned char* arena = nullptr; // residues, then two query slots of qcap bytes
         size_t qcap = 0;

@@ -1367,6 +1367,8 @@ __global__ void alphabet_kernel(const unsigned char* arena, const PairDesc* pair
 
 // the thread's sw_last_error() text, for the other host modules (sw_db.hip)
 void report_error(const char* msg) { set_err("%s", msg); }
+// the thread's sw_last_stats(), for a launch made by another module (sw_matrix.hip)
+void report_stats(const sw_stats& s) { t_stats = s; }
 
 // ---- multi-GPU batch (sw_score_batch_multi) ---------------------------------
 // Contiguous shard of pair rank r of ngpus (sizes differ by <= 1): the partition of

@@ -1,0 +1,197 @@
+// sw_matrix_host.cpp -- substitution matrices, host only (no HIP): creation from a table, the
+// NCBI text format, the byte-to-code map the kernel uses (sw_matrix.hip stages this very array)
+// and the accessors of include/algoGPU.h.  No named matrix is compiled in: users pass a file.
+#include "sw_matrix_host.h"
+#include "../../include/algoGPU.h"
+
+#include <atomic>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+namespace swmi {
+namespace {
+
+std::atomic<unsigned long long> g_next_id{1};
+
+sw_matrix* fail(const char* fmt, long long a = 0, long long b = 0) {
+    char m[200];
+    std::snprintf(m, sizeof m, fmt, a, b);
+    report_error(m);
+    return nullptr;
+}
+
+sw_matrix* make(const unsigned char* symbols, int k, const signed char* scores, int other, int flags) {
+    if (k < 1 || k > SW_MATRIX_MAX_K) return fail("matrix: %lld symbols (need 1 to 32)", k);
+    if (!symbols || !scores) return fail("matrix: null table");
+    if (other < -1 || other >= k) return fail("matrix: 'other' index %lld is not a symbol index or -1", other);
+    if (flags & ~SW_MATRIX_FOLD_CASE) return fail("matrix: unknown flags %lld", flags);
+    bool seen[256] = {};
+    for (int i = 0; i < k; ++i) {
+        if (seen[symbols[i]]) return fail("matrix: duplicate symbol 0x%02llx", symbols[i]);
+        seen[symbols[i]] = true;
+    }
+    for (int i = 0; i < k * k; ++i)
+        if (scores[i] < -127) return fail("matrix: entry %lld is outside [-127, 127]", scores[i]);
+    sw_matrix* m = new sw_matrix();
+    m->k = k;
+    m->other = other;
+    m->flags = flags;
+    std::memcpy(m->sym, symbols, (size_t)k);
+    std::memcpy(m->sc, scores, (size_t)k * (size_t)k);
+    for (int i = 0; i < k * k; ++i) m->max_entry = scores[i] > m->max_entry ? scores[i] : m->max_entry;
+    for (int b = 0; b < 256; ++b) m->code[b] = (unsigned char)(other >= 0 ? other : SW_MATRIX_NOCODE);
+    if (flags & SW_MATRIX_FOLD_CASE)   // a-z as A-Z, wherever the lower-case byte is not itself a symbol
+        for (int i = 0; i < k; ++i)
+            if (symbols[i] >= 'A' && symbols[i] <= 'Z' && !seen[symbols[i] + 32]) m->code[symbols[i] + 32] = (unsigned char)i;
+    for (int i = 0; i < k; ++i) m->code[symbols[i]] = (unsigned char)i;
+    m->id = g_next_id.fetch_add(1);
+    return m;
+}
+
+bool blank(char c) { return c == ' ' || c == '\t' || c == '\r' || c == '\v' || c == '\f'; }
+
+// the blank-separated tokens of one line
+void split(const char* p, const char* end, std::vector<std::string>& out) {
+    out.clear();
+    while (p < end) {
+        while (p < end && blank(*p)) ++p;
+        const char* q = p;
+        while (q < end && !blank(*q)) ++q;
+        if (q > p) out.emplace_back(p, q);
+        p = q;
+    }
+}
+
+// a decimal integer with an optional sign; false if the token is anything else
+bool to_int(const std::string& t, long long* v) {
+    size_t i = (t[0] == '-' || t[0] == '+') ? 1 : 0;
+    if (i >= t.size() || t.size() - i > 9) return false;
+    long long x = 0;
+    for (; i < t.size(); ++i) {
+        if (t[i] < '0' || t[i] > '9') return false;
+        x = x * 10 + (t[i] - '0');
+    }
+    *v = t[0] == '-' ? -x : x;
+    return true;
+}
+
+sw_matrix* parse(const char* text, size_t nbytes) {
+    std::vector<std::string> tok;
+    unsigned char sym[SW_MATRIX_MAX_K];
+    signed char sc[SW_MATRIX_MAX_K * SW_MATRIX_MAX_K];
+    int k = 0, rows = 0, other = -1, line_no = 0;
+    const char* p = text;
+    const char* const end = text + nbytes;
+    while (p < end) {
+        const char* e = (const char*)std::memchr(p, '\n', (size_t)(end - p));
+        if (!e) e = end;
+        ++line_no;
+        split(p, e, tok);
+        p = e < end ? e + 1 : end;
+        if (tok.empty() || tok[0][0] == '#') continue;
+        if (k == 0) {   // the header: one symbol per token
+            if (tok.size() > (size_t)SW_MATRIX_MAX_K) return fail("matrix file: %lld symbols (at most 32)", (long long)tok.size());
+            for (const std::string& t : tok) {
+                if (t.size() != 1) return fail("matrix file line %lld: a symbol must be one byte", line_no);
+                for (int i = 0; i < k; ++i)
+                    if (sym[i] == (unsigned char)t[0]) return fail("matrix file: duplicate symbol 0x%02llx", (unsigned char)t[0]);
+                if (t[0] == '*') other = k;
+                sym[k++] = (unsigned char)t[0];
+            }
+            continue;
+        }
+        if (rows >= k) return fail("matrix file line %lld: more rows than the %lld symbols of the header (not square)", line_no, k);
+        if (tok[0].size() != 1 || (unsigned char)tok[0][0] != sym[rows])
+            return fail("matrix file line %lld: the row label disagrees with symbol %lld of the header", line_no, rows);
+        if (tok.size() != (size_t)k + 1)
+            return fail("matrix file line %lld: %lld entries in the row (not square)", line_no, (long long)tok.size() - 1);
+        for (int j = 0; j < k; ++j) {
+            long long v = 0;
+            if (!to_int(tok[(size_t)j + 1], &v)) return fail("matrix file line %lld: entry %lld is not an integer", line_no, j);
+            if (v < -127 || v > 127) return fail("matrix file line %lld: entry %lld is outside [-127, 127]", line_no, v);
+            sc[rows * k + j] = (signed char)v;
+        }
+        ++rows;
+    }
+    if (k == 0) return fail("matrix file: no header line and no rows");
+    if (rows == 0) return fail("matrix file: no rows at all");
+    if (rows != k) return fail("matrix file: %lld rows for %lld symbols (not square)", rows, k);
+    return make(sym, k, sc, other, 0);
+}
+
+}  // namespace
+
+long long matrix_first_bad(const sw_matrix* m, const unsigned char* p, long long len) {
+    if (m->other >= 0) return -1;
+    for (long long i = 0; i < len; ++i)
+        if (m->code[p[i]] == SW_MATRIX_NOCODE) return i;
+    return -1;
+}
+
+}  // namespace swmi
+
+using namespace swmi;
+
+extern "C" {
+
+sw_matrix* sw_matrix_create(const unsigned char* symbols, int k, const signed char* scores, int other, int flags) {
+    return make(symbols, k, scores, other, flags);
+}
+
+sw_matrix* sw_matrix_parse(const char* text, long long nbytes) {
+    if (nbytes < 0 || (nbytes > 0 && !text)) return fail("sw_matrix_parse: invalid arguments");
+    return parse(text, (size_t)nbytes);
+}
+
+sw_matrix* sw_matrix_open(const char* path) {
+    if (!path) return fail("sw_matrix_open: null path");
+    std::FILE* f = std::fopen(path, "rb");
+    if (!f) {
+        const std::string msg = std::string("cannot open matrix file ") + path;
+        report_error(msg.c_str());
+        return nullptr;
+    }
+    std::vector<char> buf;
+    char chunk[4096];
+    size_t got = 0;
+    while ((got = std::fread(chunk, 1, sizeof chunk, f)) > 0) {
+        buf.insert(buf.end(), chunk, chunk + got);
+        if (buf.size() > (1u << 20)) break;   // 32 rows of 32 entries: anything larger is not a matrix
+    }
+    std::fclose(f);
+    if (buf.size() > (1u << 20)) return fail("matrix file: larger than 1 MiB");
+    return parse(buf.data(), buf.size());
+}
+
+int sw_matrix_size(const sw_matrix* m) { return m ? m->k : -1; }
+
+int sw_matrix_symbols(const sw_matrix* m, unsigned char* out) {
+    if (!m || !out) {
+        report_error("sw_matrix_symbols: invalid arguments");
+        return -1;
+    }
+    std::memcpy(out, m->sym, (size_t)m->k);
+    return m->k;
+}
+
+int sw_matrix_score(const sw_matrix* m, unsigned char a, unsigned char b, int* out) {
+    if (!m || !out) {
+        report_error("sw_matrix_score: invalid arguments");
+        return -1;
+    }
+    const int ca = m->code[a], cb = m->code[b];
+    if (ca == SW_MATRIX_NOCODE || cb == SW_MATRIX_NOCODE) {
+        char msg[96];
+        std::snprintf(msg, sizeof msg, "byte 0x%02x is outside the matrix alphabet", ca == SW_MATRIX_NOCODE ? a : b);
+        report_error(msg);
+        return -1;
+    }
+    *out = m->sc[ca * m->k + cb];
+    return 0;
+}
+
+void sw_matrix_free(sw_matrix* m) { delete m; }
+
+}  // extern "C"

@@ -7,7 +7,8 @@ engine's C-ABI (include/algoGPU.h ``sw_db_*``): the parse, the database file
 and the search all run in libswmi355.so; a search is one batch launch over
 residues resident in HBM.  Scores are the reference's byte-equality affine
 scores (main.cpp:28-66), so ``Database.search(q)[i]`` equals
-``SmithWatermanScore(q, record i)``.
+``SmithWatermanScore(q, record i)``; with ``matrix=`` (a ``Matrix`` read from a
+file such as BLOSUM62) they are substitution-matrix scores.
 
     db = Database.open("sp.fasta")          # or a file written by db.save()
     scores = db.search(b"MKTAYIAKQR...")    # one int per record, record order
@@ -105,21 +106,44 @@ class Database:
         return np.array([self.length(i) for i in range(len(self))], dtype=np.int64)
 
     # ---- search ---------------------------------------------------------------
-    def search(self, query) -> np.ndarray:
-        """int32 score of ``query`` against every record, in record order."""
+    @staticmethod
+    def _gaps(matrix, gap_init, gap_ext):
+        if matrix is None:
+            if gap_init is not None or gap_ext is not None:
+                raise SwError("gap_init / gap_ext go with matrix= (equality searches use set_params)")
+            return None
+        if gap_init is None or gap_ext is None:
+            raise SwError("a matrix search needs gap_init and gap_ext")
+        return int(gap_init), int(gap_ext)
+
+    def search(self, query, matrix=None, gap_init=None, gap_ext=None) -> np.ndarray:
+        """int32 score of ``query`` against every record, in record order.  With ``matrix`` (a
+        :class:`Matrix`; the query is its first index) the scores are substitution-matrix scores
+        with the gap penalties given here; without, byte-equality scores as set_params has them."""
         q = _u8(query)
         out = np.zeros(len(self), dtype=np.int32)
+        gaps = self._gaps(matrix, gap_init, gap_ext)
+        if gaps is not None:
+            _check(lib().sw_db_search_matrix(self._h, matrix._handle(), _ptr(q), len(q), gaps[0], gaps[1],
+                                             out.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+            return out
         _check(lib().sw_db_search(self._h, _ptr(q), len(q), out.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
         return out
 
-    def search_db(self, queries: "Database") -> np.ndarray:
-        """[len(queries), len(self)] int32 scores of every query record against every record."""
+    def search_db(self, queries: "Database", matrix=None, gap_init=None, gap_ext=None) -> np.ndarray:
+        """[len(queries), len(self)] int32 scores of every query record against every record
+        (``matrix``, ``gap_init``, ``gap_ext`` as in :meth:`search`; matrix queries run one by one)."""
         out = np.zeros((len(queries), len(self)), dtype=np.int32)
+        gaps = self._gaps(matrix, gap_init, gap_ext)
+        if gaps is not None:
+            _check(lib().sw_db_search_db_matrix(self._h, queries._h, matrix._handle(), gaps[0], gaps[1],
+                                                out.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+            return out
         _check(lib().sw_db_search_db(self._h, queries._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
         return out
 
-    def top(self, query, k: int = 10) -> list:
+    def top(self, query, k: int = 10, matrix=None, gap_init=None, gap_ext=None) -> list:
         """The k best records: [(score, index, header)], score descending, index ascending on ties."""
-        sc = self.search(query)
+        sc = self.search(query, matrix=matrix, gap_init=gap_init, gap_ext=gap_ext)
         idx = np.lexsort((np.arange(len(sc)), -sc.astype(np.int64)))[:k]
         return [(int(sc[i]), int(i), self.header(int(i))) for i in idx]

@@ -144,8 +144,9 @@ int sw_ipc_close(void* d_ptr);
 /* ---- FASTA databases: query x database scoring (no reference counterpart;
  * SURVEY.md 8(f) f-4, the makedb / align workflow of the reference's timing.sh:3-8
  * around the external CUDASW++4 tool, Makefile_CUDASW4.mak:44-56) ------------
- * Scores are this engine's (byte equality MATCH/MISMATCH, affine gaps,
- * main.cpp:28-66), not CUDASW++'s BLOSUM62.  A database holds its residues
+ * These entry points score by byte equality (MATCH/MISMATCH, affine gaps,
+ * main.cpp:28-66); sw_db_search_matrix below scores under a substitution matrix
+ * read from a file (BLOSUM62 is not compiled in).  A database holds its residues
  * host-side and, after the first search, once in device memory (one arena,
  * per device); searches launch one batch over all of its records, longest
  * first, and return the scores in record order.
@@ -173,6 +174,70 @@ int sw_db_search(sw_db* db, const unsigned char* query, int qlen, int* scores_ou
 int sw_db_search_db(sw_db* db, const sw_db* queries, int* scores_out);
 void sw_db_close(sw_db* db);
 
+/* ---- substitution-matrix scoring (no reference counterpart; the scoring of the
+ * CUDASW++4 search that timing.sh:3-8 runs) ------------------------------------
+ * The same recurrence (main.cpp:54-66: E from the left, F from above, borders 0,
+ * H = max(0, diag + s, E, F), score = max H, int32, bit-exact) with s(a, b) read
+ * from a table instead of a byte compare.
+ *
+ * A matrix is K distinct byte symbols (1 <= K <= 32), a K x K table of entries in
+ * [-127, 127] -- scores[i*K + j] scores symbol i of seq1 / the query against symbol
+ * j of seq2 / the record; it need not be symmetric, and score(b, a, transpose) ==
+ * score(a, b, M) -- `other`, the index of the symbol that every byte outside the
+ * alphabet maps to, or -1, and flags: SW_MATRIX_FOLD_CASE maps a-z to A-Z wherever
+ * the lower-case byte is not itself a symbol.  With other = -1 a byte outside the
+ * alphabet is an error: the call returns -1 and sw_last_error() names the pair,
+ * record or query index, the position and the byte (checked on the host: a
+ * database's records once per (database, matrix), the query on every search).
+ * A matrix is immutable and may be used from any thread at once.
+ *
+ * Gaps: a gap of L residues costs gap_init + (L-1) * gap_ext, the engine's model;
+ * BLAST-style "open 11, extend 1" is gap_init = 12, gap_ext = 1.  Matrix calls take
+ * the two as arguments (0 <= gap_init, gap_ext <= 1<<20, either may be the larger)
+ * and neither read nor write sw_set_params' process-wide constants.
+ *
+ * sw_matrix_create: from a table.  NULL on error (sw_last_error).
+ * sw_matrix_parse / sw_matrix_open: the NCBI text format: '#' comment lines, one
+ *   header line of symbols, then K rows of a symbol and K integers; any run of
+ *   blanks separates tokens, CRLF and a missing final newline are accepted, a '*'
+ *   symbol becomes `other`.  NULL (with a message) for a table that is not square, a
+ *   row label that disagrees with the header, a duplicate symbol, more than 32
+ *   symbols, an entry outside +-127, a token that is not an integer, or no rows.
+ *   No named matrix (BLOSUM, PAM) is compiled in: pass a file.
+ * sw_matrix_size / sw_matrix_symbols: K (symbols copies the K bytes and returns K).
+ * sw_matrix_score: *out = the entry for bytes (a, b) through the byte-to-code map
+ *   the kernel uses (other, fold case); -1 if either byte has no code.
+ * sw_score_matrix: one pair; the score, or -1.
+ * sw_score_matrix_batch: scores_out[k] = score(a[k], b[k]); one launch; 0 or -1.
+ *   n == 0 or m == 0 scores 0; npairs == 0 returns 0; a pair with
+ *   max(0, largest entry) * min(n, m) >= 2^28 is refused before anything is launched.
+ * sw_db_search_matrix / sw_db_search_db_matrix: as sw_db_search / sw_db_search_db
+ *   (scores in record order; the database's device arena and query slot, no second
+ *   copy of the residues); the query is seq1.  The queries of search_db run one
+ *   after another (not pipelined).  Equality and matrix searches of one open database
+ *   may alternate.
+ * Limits: ONE WAVE scores one pair (sw_matrix.hip), so a launch needs thousands of
+ * pairs to fill the GPU and one long pair runs at a few GCUPS; 16-bit packed
+ * kernels and a multi-wave pair are not built. */
+typedef struct sw_matrix sw_matrix;
+#define SW_MATRIX_FOLD_CASE 1
+sw_matrix* sw_matrix_create(const unsigned char* symbols, int k, const signed char* scores, int other, int flags);
+sw_matrix* sw_matrix_parse(const char* text, long long nbytes);
+sw_matrix* sw_matrix_open(const char* path);
+int  sw_matrix_size(const sw_matrix*);
+int  sw_matrix_symbols(const sw_matrix*, unsigned char* out /* k bytes */);
+int  sw_matrix_score(const sw_matrix*, unsigned char a, unsigned char b, int* out);
+void sw_matrix_free(sw_matrix*);
+int  sw_score_matrix(const sw_matrix*, const unsigned char* seq1, const unsigned char* seq2, int n, int m,
+                     int gap_init, int gap_ext);                       /* score, or -1 */
+int  sw_score_matrix_batch(const sw_matrix*, const unsigned char* const* a, const int* alen,
+                           const unsigned char* const* b, const int* blen, int npairs,
+                           int gap_init, int gap_ext, int* scores_out); /* 0 or -1 */
+int  sw_db_search_matrix(sw_db*, const sw_matrix*, const unsigned char* query, int qlen,
+                         int gap_init, int gap_ext, int* scores_out);
+int  sw_db_search_db_matrix(sw_db*, const sw_db* queries, const sw_matrix*,
+                            int gap_init, int gap_ext, int* scores_out);
+
 /* Tuning knobs (process-wide).  Keys:
  *   "W"        columns per lane: 0 = auto, 1, 2, 4, 8
  *   "C"        rows per strip hand-off chunk: 0 = auto, 16, 32, 64
@@ -188,6 +253,8 @@ void sw_db_close(sw_db* db);
  *              5 = the flow2 / flow3 wavefront step (DNA, one column per lane or more, chunked
  *                  LDS / granule hand-offs; the automatic plan for single long pairs, column
  *                  slabs and batches whose scores need int32)
+ *              (sw_last_stats also reports mode 6 = wave per pair, substitution matrix: the
+ *              sw_*_matrix entry points, which honour "blocks" and "W" only)
  *   "duo16"    1 = (default) packed duos take max3 through v_pk_maximum3_f16 when every
  *              value stays below 0x7C00 (MATCH*(min(n,m)+1) <= 31743), 0 = u16 max only
  *   "linear"   -1 = (default) the exact linear-gap step when G_INIT == G_EXT

@@ -5,8 +5,12 @@ so the figure is host-API GCUPS, not kernel-only.  Records are uniform ACGT with
 [lo, hi]; the arena is uploaded to HBM by the first (untimed) search.  --alphabet protein: uniform over
 the 20 amino-acid letters (SwissProt-style; the engine's byte path, duo kernels with option duo_raw = 1).
 
+--matrix random|FILE --gaps G_INIT,G_EXT: the same search under a substitution matrix (sw_db_search_matrix, the
+wave-per-pair kernel of sw_matrix.hip): FILE in the NCBI text format, or "random": a seeded random table over the
+alphabet's letters with diagonal entries in [4, 11] and off-diagonal entries in [-4, 3].
+
     python tools/bench_db.py [--records R] [--qlen Q] [--lo L] [--hi H] [--steps K] [--alphabet dna|protein]
-                             [--opt k=v ...]
+                             [--opt k=v ...] [--matrix random|FILE --gaps G_INIT,G_EXT]
 """
 import argparse
 import json
@@ -31,7 +35,11 @@ def main():
     ap.add_argument("--queries", type=int, default=0,
                     help="also time search_db over this many queries of qlen (pipelined on the database's stream)")
     ap.add_argument("--opt", action="append", default=[], help="engine option k=v (sw_set_option), repeatable")
+    ap.add_argument("--matrix", default=None, help="'random' or a matrix file: search under a substitution matrix")
+    ap.add_argument("--gaps", default=None, help="G_INIT,G_EXT of a --matrix search")
     a = ap.parse_args()
+    if (a.matrix is None) != (a.gaps is None):
+        ap.error("--matrix and --gaps go together")
     import concurrentproject_amd as sw
     for kv in a.opt:
         k, v = kv.split("=")
@@ -44,14 +52,27 @@ def main():
         parts.append(b">r%d\n" % i + acgt[rng.integers(0, len(acgt), size=n)].tobytes() + b"\n")
     db = Database.from_fasta(b"".join(parts))
     q = acgt[rng.integers(0, len(acgt), size=a.qlen)]
-    db.search(q)  # upload + warm
+    kw, extra = {}, {}
+    if a.matrix is not None:
+        if a.matrix == "random":
+            trng = np.random.default_rng(62)
+            k = len(acgt)
+            tab = trng.integers(-4, 4, (k, k))
+            tab[np.arange(k), np.arange(k)] = trng.integers(4, 12, k)
+            mx = sw.Matrix(acgt.tobytes(), tab)
+        else:
+            mx = sw.Matrix.open(a.matrix)
+        gi, ge = (int(x) for x in a.gaps.split(","))
+        kw = {"matrix": mx, "gap_init": gi, "gap_ext": ge}
+        extra = {"matrix": a.matrix, "gaps": [gi, ge]}
+    db.search(q, **kw)  # upload + warm
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        sc = db.search(q)
+        sc = db.search(q, **kw)
     dt = (time.perf_counter() - t0) / a.steps
     cells = int(lens.sum()) * a.qlen
     st = sw.last_stats()
-    print(json.dumps({"metric": "db search GCUPS (host API, synchronous)", "alphabet": a.alphabet,
+    print(json.dumps({**extra, "metric": "db search GCUPS (host API, synchronous)", "alphabet": a.alphabet,
                       "kernel_ms": round(st.get("kernel_ms", -1), 3), "mode": st["mode"], "W": st["W"], "value": round(cells / dt / 1e9, 2),
                       "unit": "GCUPS", "ms_per_search": round(dt * 1e3, 3), "records": a.records,
                       "residues": int(lens.sum()), "qlen": a.qlen, "len_range": [a.lo, a.hi],
