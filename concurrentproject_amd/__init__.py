@@ -24,7 +24,7 @@ __all__ = [
     "set_params", "get_params", "set_option", "get_option", "last_stats", "gen_pair", "gen_batch",
     "SwError", "LIB_PATH", "SW_FLAG_DNA", "SW_FLAG_BYTES", "slab_bounds", "SlabBuffer", "slab_alloc",
     "ipc_open", "ipc_close", "score_slab_device", "Database", "Matrix", "score_matrix", "score_matrix_batch",
-    "SW_MATRIX_FOLD_CASE",
+    "SW_MATRIX_FOLD_CASE", "Alignment", "align_matrix", "align_matrix_batch", "last_align_ms",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -51,6 +51,11 @@ class _Stats(ctypes.Structure):
                 ("W", ctypes.c_int), ("C", ctypes.c_int), ("dna", ctypes.c_int), ("blocks", ctypes.c_int),
                 ("waves_per_cu", ctypes.c_int), ("items", ctypes.c_int), ("boundary_bytes", ctypes.c_longlong),
                 ("mode", ctypes.c_int), ("variant", ctypes.c_int)]
+
+
+class _Alignment(ctypes.Structure):
+    _fields_ = [("score", ctypes.c_int), ("beg1", ctypes.c_int), ("end1", ctypes.c_int), ("beg2", ctypes.c_int),
+                ("end2", ctypes.c_int), ("ncigar", ctypes.c_int), ("cigar_off", ctypes.c_longlong)]
 
 
 _lib = None
@@ -188,6 +193,19 @@ def lib() -> ctypes.CDLL:
     L.sw_db_search_matrix.restype = i
     L.sw_db_search_db_matrix.argtypes = [vp, vp, vp, i, i, ctypes.POINTER(i)]
     L.sw_db_search_db_matrix.restype = i
+    # alignments (include/algoGPU.h sw_align_*; absent from older builds that SWMI355_LIB may name for an A/B)
+    ll = ctypes.c_longlong
+    if hasattr(L, "sw_align_matrix_batch"):
+        for name in ("sw_align_matrix_batch", "sw_align_matrix_cpu"):
+            f = getattr(L, name)
+            f.argtypes = [vp, ctypes.POINTER(u8p), ctypes.POINTER(i), ctypes.POINTER(u8p), ctypes.POINTER(i), i, i, i,
+                          ctypes.POINTER(_Alignment), ctypes.POINTER(ctypes.c_uint), ll, ctypes.POINTER(ll)]
+            f.restype = i
+        L.sw_db_align_matrix.argtypes = [vp, vp, u8p, i, ctypes.POINTER(i), i, i, i, ctypes.POINTER(_Alignment),
+                                         ctypes.POINTER(ctypes.c_uint), ll, ctypes.POINTER(ll)]
+        L.sw_db_align_matrix.restype = i
+        L.sw_last_align_ms.argtypes = [ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
+        L.sw_last_align_ms.restype = None
     _lib = L
     return L
 
@@ -445,6 +463,17 @@ class Matrix:
     def open(cls, path) -> "Matrix":
         return cls(_handle=lib().sw_matrix_open(os.fsencode(path)) or 0)
 
+    @classmethod
+    def equality(cls, symbols, match: int, mismatch: int) -> "Matrix":
+        """The table of a byte-equality scoring over the distinct bytes ``symbols`` (at most 32):
+        ``match`` on the diagonal, ``mismatch`` elsewhere.  With it, alignments under the
+        reference's own scoring (``Params``) need no matrix file."""
+        sym = bytes(sorted(set(_u8(symbols).tolist())))
+        if not 1 <= len(sym) <= 32:
+            raise SwError("equality matrix: %d distinct bytes (need 1 to 32)" % len(sym))
+        k = len(sym)
+        return cls(sym, np.where(np.eye(k, dtype=bool), int(match), int(mismatch)))
+
     def _handle(self):
         if self._h is None:
             raise SwError("matrix is closed")
@@ -502,6 +531,115 @@ def score_matrix_batch(pairs: Iterable[Sequence], matrix: Matrix, gap_init: int,
     out = (ctypes.c_int * n)()
     _check(lib().sw_score_matrix_batch(matrix._handle(), A, AL, B, BL, n, int(gap_init), int(gap_ext), out))
     return list(out)
+
+
+# ---- alignments (include/algoGPU.h sw_align_*) ------------------------------------------------------
+
+@dataclass(frozen=True)
+class Alignment:
+    """One local alignment: its score, the half-open ranges [beg1, end1) of seq1 and [beg2, end2)
+    of seq2 it covers, and its operations: ``ops`` is a tuple of (length, op) with op one of "M" (a
+    residue of seq1 aligned with one of seq2), "I" (a residue of seq1 against a gap), "D" (a
+    residue of seq2 against a gap); ``cigar`` the same as a string such as ``12M2D40M``.  A pair
+    with score 0 has empty ranges at 0 and no operations."""
+    score: int
+    beg1: int
+    end1: int
+    beg2: int
+    end2: int
+    ops: tuple = ()
+
+    @property
+    def cigar(self) -> str:
+        return "".join("%d%s" % (n, op) for n, op in self.ops)
+
+    def columns(self, seq1, seq2):
+        """The aligned columns as (row1, row2) byte strings with '-' for a gap."""
+        a, b = _u8(seq1), _u8(seq2)
+        i, j = self.beg1, self.beg2
+        r1, r2 = [], []
+        for n, op in self.ops:
+            if op == "M":
+                r1.append(a[i:i + n].tobytes())
+                r2.append(b[j:j + n].tobytes())
+                i, j = i + n, j + n
+            elif op == "I":
+                r1.append(a[i:i + n].tobytes())
+                r2.append(b"-" * n)
+                i += n
+            else:
+                r1.append(b"-" * n)
+                r2.append(b[j:j + n].tobytes())
+                j += n
+        return b"".join(r1), b"".join(r2)
+
+    def identities(self, seq1, seq2) -> int:
+        """Aligned pairs (M columns) whose two bytes are equal."""
+        r1, r2 = self.columns(seq1, seq2)
+        return sum(1 for x, y in zip(r1, r2) if x == y and x != 0x2D)
+
+    def pretty(self, seq1, seq2) -> str:
+        """The usual three lines: seq1's row, '|' under equal bytes, seq2's row."""
+        r1, r2 = self.columns(seq1, seq2)
+        mid = "".join("|" if x == y and x != 0x2D else " " for x, y in zip(r1, r2))
+        return "%s\n%s\n%s" % (r1.decode("latin-1"), mid, r2.decode("latin-1"))
+
+
+_OPS = "MID"
+
+
+def _alignments(out, cigar) -> list:
+    res = []
+    for o in out:
+        ent = cigar[o.cigar_off:o.cigar_off + o.ncigar]
+        res.append(Alignment(o.score, o.beg1, o.end1, o.beg2, o.end2, tuple((int(e) >> 4, _OPS[int(e) & 15]) for e in ent)))
+    return res
+
+
+def _align_call(call, n: int, cap: int) -> list:
+    """call(out, cigar, cap, used) -> rc, with a cigar buffer of `cap` entries; once more with what was
+    needed if that was too small."""
+    out = (_Alignment * max(n, 1))()
+    used = ctypes.c_longlong(0)
+    for _ in range(2):
+        cigar = np.zeros(max(cap, 1), dtype=np.uint32)
+        rc = call(out, cigar.ctypes.data_as(ctypes.POINTER(ctypes.c_uint)), len(cigar), ctypes.byref(used))
+        if rc == 0 or used.value <= len(cigar):
+            break
+        cap = used.value
+    _check(rc)
+    return _alignments(out[:n], cigar)
+
+
+def align_matrix_batch(pairs: Iterable[Sequence], matrix: Matrix, gap_init: int, gap_ext: int, cpu: bool = False) -> list:
+    """An :class:`Alignment` per pair under ``matrix`` (seq1 is its first index) with affine gaps, on
+    the GPU (sw_align_matrix_batch: the traced matrix kernel and a walk) or, with ``cpu=True``, from
+    the library's plain full-matrix aligner on the host (sw_align_matrix_cpu), which gives the same
+    result.  Which alignment is reported when several reach the score is fixed (include/algoGPU.h)."""
+    arrs = [(_u8(a), _u8(b)) for a, b in pairs]
+    n = len(arrs)
+    if n == 0:
+        return []
+    u8p = ctypes.POINTER(ctypes.c_ubyte)
+    A = (u8p * n)(*[_ptr(x) for x, _ in arrs])
+    B = (u8p * n)(*[_ptr(y) for _, y in arrs])
+    AL = (ctypes.c_int * n)(*[len(x) for x, _ in arrs])
+    BL = (ctypes.c_int * n)(*[len(y) for _, y in arrs])
+    f = lib().sw_align_matrix_cpu if cpu else lib().sw_align_matrix_batch
+    return _align_call(lambda out, cig, cap, used: f(matrix._handle(), A, AL, B, BL, n, int(gap_init), int(gap_ext),
+                                                     out, cig, cap, used), n, 16 * n)
+
+
+def align_matrix(seq1, seq2, matrix: Matrix, gap_init: int, gap_ext: int, cpu: bool = False) -> Alignment:
+    """One pair (see :func:`align_matrix_batch`)."""
+    return align_matrix_batch([(seq1, seq2)], matrix, gap_init, gap_ext, cpu=cpu)[0]
+
+
+def last_align_ms() -> tuple:
+    """(fill_ms, walk_ms): device time of this thread's last GPU alignment call, over its launches."""
+    f, w = ctypes.c_float(), ctypes.c_float()
+    lib().sw_last_align_ms(ctypes.byref(f), ctypes.byref(w))
+    return f.value, w.value
 
 
 from .db import Database  # noqa: E402  (FASTA databases, query x database search)

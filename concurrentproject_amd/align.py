@@ -8,7 +8,13 @@ cells, time and GCUPS go to stderr.  Scores are the reference's byte-equality
 affine scores (main.cpp:28-66) with --params MATCH,MISMATCH,G_INIT,G_EXT, or, with
 --matrix FILE --gaps G_INIT,G_EXT, scores under the substitution matrix of FILE (NCBI
 text format, e.g. BLOSUM62; none is built in).  A gap of L residues costs
-G_INIT + (L-1)*G_EXT: BLAST's "open 11, extend 1" is --gaps 12,1."""
+G_INIT + (L-1)*G_EXT: BLAST's "open 11, extend 1" is --gaps 12,1.
+
+With --alignments every hit line gains ``q_beg  q_end  d_beg  d_end  cigar``: the half-open
+ranges of the query and of the record that the alignment covers and its operations (M an aligned
+pair, I a query residue against a gap, D a record residue against a gap; ``*`` for a score of 0).
+Only the top K of each query are aligned.  Without --matrix the alignments are made under the
+equality table of --params over the bytes present (at most 32 distinct ones)."""
 import argparse
 import sys
 import time
@@ -27,6 +33,7 @@ def main(argv=None) -> int:
     ap.add_argument("--params", default="1,-1,1,1", help="MATCH,MISMATCH,G_INIT,G_EXT")
     ap.add_argument("--matrix", default=None, help="substitution matrix file (NCBI text format); needs --gaps")
     ap.add_argument("--gaps", default=None, help="G_INIT,G_EXT of a --matrix search")
+    ap.add_argument("--alignments", action="store_true", help="align the top K hits: ranges and cigar per line")
     a = ap.parse_args(argv)
     if (a.matrix is None) != (a.gaps is None):
         ap.error("--matrix and --gaps go together")
@@ -37,7 +44,8 @@ def main(argv=None) -> int:
             ap.error("--gaps takes G_INIT,G_EXT")
         matrix = Matrix.open(a.matrix)
     else:
-        set_params(Params(*(int(x) for x in a.params.split(","))))
+        prm = Params(*(int(x) for x in a.params.split(",")))
+        set_params(prm)
     with Database.open(a.db) as db, Database.open(a.query) as qs:
         lens = db.lengths()
         t0 = time.perf_counter()
@@ -45,10 +53,29 @@ def main(argv=None) -> int:
         dt = time.perf_counter() - t0
         cells = int(qs.lengths().sum()) * int(lens.sum())
         out = sys.stdout
+        amatrix, agaps = matrix, gaps
+        if a.alignments and matrix is None:   # the equality table of --params over the bytes present
+            present = set()
+            for d in (db, qs):
+                for r in range(len(d)):
+                    present.update(d.record(r)[1])
+            if len(present) > 32:
+                print("align --alignments: %d distinct bytes in the query and the database; an equality matrix "
+                      "holds at most 32 (pass --matrix)" % len(present), file=sys.stderr)
+                return 2
+            amatrix = Matrix.equality(bytes(sorted(present)) or b"A", prm.match, prm.mismatch)
+            agaps = (prm.gap_init, prm.gap_ext)
         for q in range(len(qs)):
             qh = qs.header(q)
             sc = scores[q]
             order = np.lexsort((np.arange(len(sc)), -sc.astype(np.int64)))[:a.top]
+            if a.alignments:
+                al = db.align(qs.record(q)[1], [int(i) for i in order], amatrix, agaps[0], agaps[1])
+                for r, (i, x) in enumerate(zip(order, al)):
+                    out.write("%d\t%s\t%d\t%d\t%d\t%s\t%d\t%d\t%d\t%d\t%s\n"
+                              % (q, qh, r + 1, int(sc[i]), int(i), db.header(int(i)), x.beg1, x.end1, x.beg2, x.end2,
+                                 x.cigar or "*"))
+                continue
             for r, i in enumerate(order):
                 out.write("%d\t%s\t%d\t%d\t%d\t%s\n" % (q, qh, r + 1, int(sc[i]), int(i), db.header(int(i))))
         print("%d queries x %d records: %.3e cells in %.3f s = %.2f GCUPS"

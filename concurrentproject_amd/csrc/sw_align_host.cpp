@@ -1,0 +1,220 @@
+// sw_align_host.cpp -- alignments under a substitution matrix, host only (no HIP): the argument
+// checks shared by the GPU and the CPU entry points, the reverse-and-encode routine that turns a
+// walk's operations into run-length encoded cigar entries, and sw_align_matrix_cpu, a plain
+// full-matrix aligner with exactly the end-cell rule and the walk priorities of the traced kernel
+// (sw_matrix.hip; include/algoGPU.h states both).  It checks the GPU path and is a usable
+// fallback for a machine without a device; it needs n * m bytes a pair.
+#include "sw_matrix_host.h"
+#include "../../include/algoGPU.h"
+
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+namespace swmi {
+
+namespace {
+constexpr long long ALIGN_MAX_SEQ = (1LL << 27) - 1;   // the engine's longest sequence (sw_matrix.hip)
+constexpr long long CPU_MAX_CELLS = 1LL << 32;         // the CPU aligner's matrix: a byte a cell
+}  // namespace
+
+int align_check(const char* fn, const sw_matrix* mx, const unsigned char* const* a, const int* alen,
+                const unsigned char* const* b, const int* blen, int npairs, int gap_init, int gap_ext,
+                const sw_alignment* out, const unsigned* cigar, long long cigar_cap, const long long* cigar_used) {
+    char m[200];
+    if (!mx || npairs < 0 || cigar_cap < 0 || !cigar_used || (cigar_cap > 0 && !cigar) ||
+        (npairs > 0 && (!a || !alen || !b || !blen || !out))) {
+        std::snprintf(m, sizeof m, "%s: invalid arguments", fn);
+        report_error(m);
+        return -1;
+    }
+    if (gap_init < 0 || gap_ext < 0 || gap_init > (1 << 20) || gap_ext > (1 << 20)) {
+        std::snprintf(m, sizeof m, "unsupported gap penalties (%d, %d): need 0 <= G_INIT, G_EXT <= 2^20", gap_init, gap_ext);
+        report_error(m);
+        return -1;
+    }
+    for (int k = 0; k < npairs; ++k) {
+        if (alen[k] < 0 || blen[k] < 0 || (alen[k] > 0 && !a[k]) || (blen[k] > 0 && !b[k]) || alen[k] > ALIGN_MAX_SEQ ||
+            blen[k] > ALIGN_MAX_SEQ) {
+            std::snprintf(m, sizeof m, "pair %d: invalid sequence pointer or length", k);
+            report_error(m);
+            return -1;
+        }
+        if (alen[k] == 0 || blen[k] == 0) continue;
+        if (!align_range_ok(mx, alen[k], blen[k], "pair", k)) return -1;
+        for (int s = 0; s < 2; ++s) {
+            const unsigned char* p = s ? b[k] : a[k];
+            const long long bad = matrix_first_bad(mx, p, s ? blen[k] : alen[k]);
+            if (bad >= 0) {
+                std::snprintf(m, sizeof m, "pair %d: seq%d position %lld: byte 0x%02x is outside the matrix alphabet", k,
+                              s + 1, bad, p[bad]);
+                report_error(m);
+                return -1;
+            }
+        }
+    }
+    return 0;
+}
+
+bool align_range_ok(const sw_matrix* mx, int alen, int blen, const char* what, int idx) {
+    if ((long long)std::min(alen, blen) * std::max(mx->max_entry, 0) >= (1LL << 28)) {
+        char m[160];
+        std::snprintf(m, sizeof m, "%s %d: score range exceeds the int32 engine (min length * largest entry >= 2^28)", what, idx);
+        report_error(m);
+        return false;
+    }
+    return true;
+}
+
+// ops_rev[0, nops): the walk's operations, last first.  Appends the run-length encoded entries
+// ((length << 4) | op), first operation first, to out; returns how many.  A run longer than
+// 2^28 - 1 is split.
+int encode_ops(const unsigned char* ops_rev, long long nops, std::vector<unsigned>& out) {
+    int added = 0;
+    long long k = nops - 1;
+    while (k >= 0) {
+        const unsigned op = ops_rev[k];
+        unsigned run = 0;
+        while (k >= 0 && ops_rev[k] == op && run < (1u << 28) - 1) {
+            ++run;
+            --k;
+        }
+        out.push_back((run << 4) | (op & 15u));
+        ++added;
+    }
+    return added;
+}
+
+void AlignSink::set(int k, int score, int beg1, int end1, int beg2, int end2, const unsigned char* ops_rev, long long nops) {
+    sw_alignment& o = out[k];
+    o.score = score;
+    o.beg1 = beg1;
+    o.end1 = end1;
+    o.beg2 = beg2;
+    o.end2 = end2;
+    o.cigar_off = (long long)cig.size();
+    o.ncigar = encode_ops(ops_rev, nops, cig);
+}
+
+void AlignSink::set_empty(int k) {
+    sw_alignment& o = out[k];
+    o.score = o.beg1 = o.end1 = o.beg2 = o.end2 = o.ncigar = 0;
+    o.cigar_off = (long long)cig.size();
+}
+
+int AlignSink::finish(unsigned* cigar, long long cigar_cap, long long* cigar_used) {
+    *cigar_used = (long long)cig.size();
+    if ((long long)cig.size() > cigar_cap) {
+        char m[160];
+        std::snprintf(m, sizeof m, "cigar buffer too small: %lld entries needed, cigar_cap is %lld", (long long)cig.size(),
+                      cigar_cap);
+        report_error(m);
+        return -1;
+    }
+    if (!cig.empty()) std::memcpy(cigar, cig.data(), cig.size() * sizeof(unsigned));
+    return 0;
+}
+
+namespace {
+
+// One pair, both lengths > 0.  cell[j * n + i]: bits 0-1 where H came from (0 none: H = 0, 1 diagonal,
+// 2 E, 3 F), bit 2 E extended a gap (else opened one), bit 3 the same for F; E runs along seq1
+// (operation I), F along seq2 (operation D).  The clamped form of the kernel: E and F are kept as
+// max(E, 0), max(F, 0), which changes no H and no decision at a cell the walk can visit.
+void align_pair(const sw_matrix* mx, const unsigned char* a, int n, const unsigned char* b, int m, int go, int ge,
+                std::vector<unsigned char>& cell, std::vector<int>& hup, std::vector<int>& fup,
+                std::vector<unsigned char>& ops, int k, AlignSink& sink) {
+    cell.assign((size_t)n * (size_t)m, 0);
+    hup.assign((size_t)n, 0);
+    fup.assign((size_t)n, 0);
+    int best = 0, bi = 0, bj = 0;
+    for (int j = 0; j < m; ++j) {
+        const int cb = mx->code[b[j]];
+        int hleft = 0, eleft = 0, hdiag = 0;
+        unsigned char* row = cell.data() + (size_t)j * (size_t)n;
+        for (int i = 0; i < n; ++i) {
+            const int eo = hleft - go, ee = eleft - ge;
+            const int fo = hup[(size_t)i] - go, fe = fup[(size_t)i] - ge;
+            const int E = std::max(std::max(eo, ee), 0);
+            const int F = std::max(std::max(fo, fe), 0);
+            const int t = hdiag + mx->sc[mx->code[a[i]] * mx->k + cb];
+            const int H = std::max(t, std::max(E, F));
+            row[i] = (unsigned char)((H == 0 ? 0 : t == H ? 1 : E == H ? 2 : 3) | (ee > eo ? 4 : 0) | (fe > fo ? 8 : 0));
+            // the end cell: largest t, then smallest i + j, then smallest j
+            if (t > best || (t == best && t > 0 && (i + j < bi + bj || (i + j == bi + bj && j < bj)))) {
+                best = t;
+                bi = i;
+                bj = j;
+            }
+            hdiag = hup[(size_t)i];
+            hup[(size_t)i] = H;
+            fup[(size_t)i] = F;
+            hleft = H;
+            eleft = E;
+        }
+    }
+    if (best <= 0) {
+        sink.set_empty(k);
+        return;
+    }
+    // the walk: from the end cell in state H, operations last first
+    ops.resize((size_t)n + (size_t)m);
+    long long nops = 0;
+    int i = bi, j = bj, state = 0;   // 0 H, 1 E, 2 F
+    while (i >= 0 && j >= 0 && nops < (long long)n + m) {
+        const int c = cell[(size_t)j * (size_t)n + (size_t)i];
+        if (state == 0) {
+            const int src = c & 3;
+            if (src == 0) break;
+            if (src == 1) {
+                ops[(size_t)nops++] = 0;
+                --i;
+                --j;
+            } else {
+                state = src == 2 ? 1 : 2;
+            }
+        } else if (state == 1) {
+            ops[(size_t)nops++] = 1;
+            state = (c & 4) ? 1 : 0;
+            --i;
+        } else {
+            ops[(size_t)nops++] = 2;
+            state = (c & 8) ? 2 : 0;
+            --j;
+        }
+    }
+    sink.set(k, best, i + 1, bi + 1, j + 1, bj + 1, ops.data(), nops);
+}
+
+}  // namespace
+}  // namespace swmi
+
+using namespace swmi;
+
+extern "C" {
+
+int sw_align_matrix_cpu(const sw_matrix* mx, const unsigned char* const* a, const int* alen,
+                        const unsigned char* const* b, const int* blen, int npairs, int gap_init, int gap_ext,
+                        sw_alignment* out, unsigned* cigar, long long cigar_cap, long long* cigar_used) {
+    if (align_check("sw_align_matrix_cpu", mx, a, alen, b, blen, npairs, gap_init, gap_ext, out, cigar, cigar_cap, cigar_used))
+        return -1;
+    for (int k = 0; k < npairs; ++k)
+        if ((long long)alen[k] * blen[k] > CPU_MAX_CELLS) {
+            char m[160];
+            std::snprintf(m, sizeof m, "pair %d: %lld cells are more than the CPU aligner's full matrix holds (2^32)", k,
+                          (long long)alen[k] * blen[k]);
+            report_error(m);
+            return -1;
+        }
+    AlignSink sink{out, {}};
+    std::vector<unsigned char> cell, ops;
+    std::vector<int> hup, fup;
+    for (int k = 0; k < npairs; ++k) {
+        if (alen[k] == 0 || blen[k] == 0) sink.set_empty(k);
+        else align_pair(mx, a[k], alen[k], b[k], blen[k], gap_init, gap_ext, cell, hup, fup, ops, k, sink);
+    }
+    return sink.finish(cigar, cigar_cap, cigar_used);
+}
+
+}  // extern "C"

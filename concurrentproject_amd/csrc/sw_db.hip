@@ -264,6 +264,33 @@ int search_matrix(sw_db* db, const sw_matrix* mx, const unsigned char* query, in
     return 0;
 }
 
+// the query (seq1, across the lanes) aligned with the chosen records, out of the device arena
+int align_matrix(sw_db* db, const sw_matrix* mx, const unsigned char* query, int qlen, const int* record_idx, int nidx,
+                 int gap_init, int gap_ext, AlignSink& sink) {
+    const int nrec = (int)db->len.size();
+    for (int k = 0; k < nidx; ++k)
+        if (record_idx[k] < 0 || record_idx[k] >= nrec) {
+            char m[120];
+            std::snprintf(m, sizeof m, "sw_db_align_matrix: record index %d (entry %d) is outside [0, %d)", record_idx[k], k, nrec);
+            report_error(m);
+            return -1;
+        }
+    if (nidx == 0) return 0;
+    if (check_records(db, mx) || check_query(db, mx, query, qlen, 0)) return -1;
+    sw_db::Dev* v = nullptr;
+    if (device_arena(db, qlen, &v)) return -1;
+    const int64_t qoff = (int64_t)db->res.size();
+    if (qlen > 0) DBCHK(hipMemcpy(v->arena + qoff, query, (size_t)qlen, hipMemcpyHostToDevice));
+    std::vector<int64_t> a_off((size_t)nidx, qoff), b_off((size_t)nidx);
+    std::vector<int> alen((size_t)nidx, qlen), blen((size_t)nidx);
+    for (int k = 0; k < nidx; ++k) {
+        b_off[(size_t)k] = db->off[(size_t)record_idx[k]];
+        blen[(size_t)k] = db->len[(size_t)record_idx[k]];
+    }
+    return matrix_align_device(mx, v->arena, a_off.data(), alen.data(), b_off.data(), blen.data(), record_idx, nidx,
+                               gap_init, gap_ext, "record", sink);
+}
+
 }  // namespace
 }  // namespace swmi
 
@@ -297,6 +324,20 @@ int sw_db_search_db_matrix(sw_db* db, const sw_db* queries, const sw_matrix* mx,
                           scores_out + q * nrec, longest, (int)q))
             return -1;
     return 0;
+}
+
+int sw_db_align_matrix(sw_db* db, const sw_matrix* mx, const unsigned char* query, int qlen, const int* record_idx,
+                       int nidx, int gap_init, int gap_ext, sw_alignment* out, unsigned* cigar, long long cigar_cap,
+                       long long* cigar_used) {
+    if (!db || !mx || qlen < 0 || (qlen > 0 && !query) || nidx < 0 || cigar_cap < 0 || !cigar_used ||
+        (cigar_cap > 0 && !cigar) || (nidx > 0 && (!record_idx || !out))) {
+        report_error("sw_db_align_matrix: invalid arguments");
+        return -1;
+    }
+    std::lock_guard<std::mutex> g(db->mu);
+    AlignSink sink{out, {}};
+    if (align_matrix(db, mx, query, qlen, record_idx, nidx, gap_init, gap_ext, sink)) return -1;
+    return sink.finish(cigar, cigar_cap, cigar_used);
 }
 
 int sw_db_search(sw_db* db, const unsigned char* query, int qlen, int* scores_out) {

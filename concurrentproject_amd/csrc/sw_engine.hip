@@ -66,7 +66,7 @@ std::atomic<long long> g_opt_W{0}, g_opt_C{0}, g_opt_bytes{0}, g_opt_timeout{30}
     g_opt_mode{-1}, g_opt_trace{0}, g_opt_duo_f16{1}, g_opt_f2stream{0}, g_opt_ring{-1}, g_opt_ring_rows{4096}, g_opt_f2_wgs{0}, g_opt_f2w{0}, g_opt_f2pwg{-1},
     g_opt_linear{-1}, g_opt_f3{1}, g_opt_slab_plain{0}, g_opt_duo_lds{1}, g_opt_duo_tab{1}, g_opt_duo_roles{1}, g_opt_f3hl{1},
     g_opt_f3rhl{0}, g_opt_f3a{1}, g_opt_f3slab{1}, g_opt_duo_prio{-1}, g_opt_f3pool{0},
-    g_opt_stall_item{-1}, g_opt_f3pwg{1}, g_opt_duo_raw{1}, g_opt_hep{1};
+    g_opt_stall_item{-1}, g_opt_f3pwg{1}, g_opt_duo_raw{1}, g_opt_hep{1}, g_opt_trace_mb{1024};
 
 // Longest sequence the engine takes: granule buffers of m rows keep m * 16 in the
 // 32-bit record count of a buffer resource (sw_device.h linear_edge).
@@ -1970,7 +1970,12 @@ int sw_stream_status(void* stream) {
     if (!c) return -1;
     hipStream_t s = stream ? (hipStream_t)stream : c->own;
     if (!c->ctrl.p) return 0;
-    return check_ctrl(c, s);
+    const int rc = check_ctrl(c, s);   // synchronises s
+    // Nothing of this context is pending on a caller's stream any more, so the next call need not
+    // wait for it -- and must not: the caller may destroy the stream now (sw_db_close destroys the
+    // database's after sw_db_search_db), and launch_host would synchronise a dead handle.
+    if (c->last == s && s != c->own) c->last = nullptr;
+    return rc;
 }
 
 int sw_set_option(const char* key, long long v) {
@@ -2004,6 +2009,9 @@ int sw_set_option(const char* key, long long v) {
         g_opt_blocks = v;
     } else if (k == "trace") {   // device buffer of 4 u64 per strip (tools only), 0 = off
         g_opt_trace = v;
+    } else if (k == "trace_mb") {   // MiB of trace memory a traced matrix launch may hold (sw_matrix.hip)
+        if (v < 1 || v > 3072) return -1;
+        g_opt_trace_mb = v;
     } else if (k == "orient") {
         if (v < 0 || v > 2) return -1;
         g_opt_orient = v;
@@ -2089,6 +2097,7 @@ long long sw_get_option(const char* key) {
     if (k == "blocks") return g_opt_blocks;
     if (k == "orient") return g_opt_orient;
     if (k == "trace") return g_opt_trace;
+    if (k == "trace_mb") return g_opt_trace_mb;
     if (k == "mode") return g_opt_mode;
     if (k == "duo16") return g_opt_duo_f16;
     if (k == "f2stream") return g_opt_f2stream;

@@ -27,6 +27,15 @@
 // has seq1 across the lanes, table 1 (the transpose) seq2.
 //
 // Waves claim pairs in order from Ctrl::next_item; the host orders them longest first.
+//
+// ALIGNMENTS.  Tracing is a template parameter of the strip step, the pair loop and the kernel; the
+// score-only instantiations are the code they were.  The traced variant (W = 8, seq1 always across
+// the lanes) stores 4 bits a cell, a dword a lane a step, to a per-pair trace buffer (WalkPair below)
+// and reports the end cell with the maximum; sw_matrix_walk_kernel then follows the recorded
+// decisions from the end cell, one lane a pair, and the host reverses and run-length encodes
+// (sw_align_host.cpp).  The end-cell rule and the walk priorities are in include/algoGPU.h.  A launch
+// holds at most option "trace_mb" MiB of trace; a pair that does not fit alone is refused:
+// linear-space alignment of very long pairs is not built.
 #include "sw_device.h"
 #include "sw_matrix_host.h"
 #include "../../include/algoGPU.h"
@@ -51,6 +60,8 @@ constexpr int MAT_TAB_BYTES = MAT_ROWS * MAT_STRIDE; // one orientation
 constexpr int MAT_SENT = -127;                       // s of a cell without a row
 constexpr int MAT_C = 64;                            // rows per inflow / outflow chunk
 constexpr int MODE_MATRIX = 6;
+constexpr int MODE_MATRIX_TRACE = 7;                 // the traced launches (alignments)
+constexpr int TRACE_W = 8;                           // the traced variant's columns per lane: a step is a dword a lane
 
 struct MatPair {
     uint64_t col_off;   // the sequence across the lanes
@@ -59,6 +70,25 @@ struct MatPair {
     int out_idx;
     int swapped;        // 1: the columns are seq2 (table 1)
 };
+
+// Traced launches.  A cell's 4 bits: bits 0-1 where H came from (0 none: H = 0, 1 the diagonal, 2 E,
+// 3 F), bit 2 E extended a gap (clear: opened one), bit 3 the same for F.  A step's 8 cells of a lane
+// (its columns p = 0..7 at nibble p) are one dword, and the pair's buffer is [strip][step][lane]
+// dwords: a step's 64 lanes store 256 contiguous bytes.  A strip has `steps` = 64 * chunks steps, so
+// cell (i, j) -- i in seq1, across the lanes -- is nibble i & 7 of dword
+// ((i >> 9) * steps + j + (i & 511)) * 64 + ((i & 511) >> 3).
+struct WalkPair {
+    uint64_t trace_off;     // bytes, from MatArgs::trace
+    uint64_t ops_off;       // bytes, from WalkArgs::ops: n + m bytes, the operations last first
+    unsigned trace_bytes;   // strips * steps * 256
+    int steps;              // per strip
+};
+struct TraceRes {
+    int score, ei, ej, pad;    // the fill kernel: the maximum and its end cell (one 16-B store)
+    int bi, bj, nops, err;     // the walk kernel: the begin cell, operations written, WALK_* error
+};
+constexpr int WALK_OVERRUN = 1;   // more than n + m operations
+constexpr int WALK_RANGE = 2;     // a cell outside the pair or its trace buffer
 
 struct MatArgs {
     const unsigned char* seq;
@@ -73,17 +103,23 @@ struct MatArgs {
     int k;                    // symbols: code k is the sentinel / dead code
     unsigned code[64];        // the byte-to-code map, 256 bytes
     unsigned tab[2 * MAT_TAB_BYTES / 4];
+    // traced launches only
+    const WalkPair* walk;     // per item
+    unsigned char* trace;
+    TraceRes* res;            // nscores entries
 };
 static_assert(sizeof(MatArgs) <= 4096, "kernel arguments");
 static_assert(MAT_TAB_BYTES % 4 == 0, "table words");
 
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
-template <int W>
+template <int W, bool TRACE>
 struct MStrip {
+    static_assert(!TRACE || W == TRACE_W, "a traced step stores one dword a lane");
     int cb[W], tb[W];                       // LDS offset of the column's table row / bias
     int hgA[W], hgB[W], eh[W], r[W], fh[W]; // DP state, as Strip (sw_kernels.hip)
     int L0, M, IOH, IOE, IOR;
+    int Mkp, kp8;                           // TRACE: step * 8 + p at which M was reached; this step * 8
 
     __device__ __forceinline__ void setup(const MatArgs& a, const MatPair& pd, int strip, int lane,
                                           const unsigned char* s_code) {
@@ -110,8 +146,12 @@ struct MStrip {
     }
 
     // One anti-diagonal step (Strip::step with the score from the LDS table).
+    // TRACE: the step's cells go to trc at byte toff (the lane's dword of this step), and M is
+    // updated strictly, so that a lane keeps the first step (anti-diagonal) that reached its
+    // maximum and, within a step, the largest p: the smallest row.
     __device__ __forceinline__ void step(int (&hgCur)[W], const int (&hgPrev)[W], const bool l63, const int go,
-                                         const int ge, const signed char* s_tab) {
+                                         const int ge, const signed char* s_tab, const __amdgpu_buffer_rsrc_t trc,
+                                         unsigned& toff) {
         const int ioh = dpp_rol1(IOH), ioe = dpp_rol1(IOE), ior = dpp_rol1(IOR);
         const int hgL0 = dpp_shr1(IOH, hgPrev[W - 1]);
         const int ehL0 = dpp_shr1(IOE, eh[W - 1]);
@@ -120,6 +160,7 @@ struct MStrip {
         int sv[W];
 #pragma unroll
         for (int p = 0; p < W; ++p) sv[p] = (int)s_tab[cb[p] + (p > 0 ? r[p - 1] : rL0)];   // ds_read_i8
+        unsigned bits = 0;
 #pragma unroll
         for (int p = W - 1; p >= 0; --p) {
             const int q = p > 0 ? p - 1 : 0;
@@ -131,7 +172,15 @@ struct MStrip {
             const int E = max3i(ehL, hgL, 0);            // clamped E
             const int F = max3i(fh[p], hgPrev[p], 0);    // clamped F
             const int H = vmax3(t, E, F);
-            M = max(M, t);
+            if constexpr (TRACE) {
+                const bool up = t > M;
+                M = up ? t : M;
+                Mkp = up ? kp8 + p : Mkp;
+                const unsigned src = H == 0 ? 0u : (t == H ? 1u : (E == H ? 2u : 3u));
+                bits |= (src | (ehL > hgL ? 4u : 0u) | (fh[p] > hgPrev[p] ? 8u : 0u)) << (4 * p);
+            } else {
+                M = max(M, t);
+            }
             hgCur[p] = H - go;
             eh[p] = E - ge;
             fh[p] = F - ge;
@@ -141,13 +190,19 @@ struct MStrip {
         IOH = l63 ? hgCur[W - 1] : ioh;   // lane 63 <- this step's right-edge output
         IOE = l63 ? eh[W - 1] : ioe;
         IOR = ior;
+        if constexpr (TRACE) {
+            __builtin_amdgcn_raw_buffer_store_b32(bits, trc, toff, 0, 0);
+            toff += 256u;
+            kp8 += 8;
+        }
     }
 
-    __device__ __forceinline__ void run(const bool l63, const int go, const int ge, const signed char* s_tab) {
+    __device__ __forceinline__ void run(const bool l63, const int go, const int ge, const signed char* s_tab,
+                                        const __amdgpu_buffer_rsrc_t trc, unsigned& toff) {
 #pragma unroll 2
         for (int s = 0; s < MAT_C; s += 2) {
-            step(hgA, hgB, l63, go, ge, s_tab);
-            step(hgB, hgA, l63, go, ge, s_tab);
+            step(hgA, hgB, l63, go, ge, s_tab, trc, toff);
+            step(hgB, hgA, l63, go, ge, s_tab, trc, toff);
         }
     }
 };
@@ -162,9 +217,11 @@ __device__ __forceinline__ u32x2 mat_fetch_edge(const __amdgpu_buffer_rsrc_t scr
 }
 
 // All strips of one pair on this wave; scr: the wave's scratch (at least m entries when the pair has
-// more than one strip).
-template <int W>
-__device__ void matrix_pair(const MatArgs& a, const MatPair& pd, const int lane, uint2* scr,
+// more than one strip).  TRACE: wp is the pair's trace buffer; the result is the maximum with its end
+// cell -- among the cells whose t equals the maximum, the smallest i + j, then the smallest row j
+// (include/algoGPU.h) -- so each strip starts its own M and the strips are merged by that rule.
+template <int W, bool TRACE>
+__device__ void matrix_pair(const MatArgs& a, const MatPair& pd, const WalkPair& wp, const int lane, uint2* scr,
                             const signed char* s_tab, const unsigned char* s_code) {
     constexpr int SW = 64 * W, C = MAT_C;
     const int m = pd.m;
@@ -177,10 +234,21 @@ __device__ void matrix_pair(const MatArgs& a, const MatPair& pd, const int lane,
     const __amdgpu_buffer_rsrc_t scr_rsrc =
         __builtin_amdgcn_make_buffer_rsrc(scr, 0, strips > 1 ? (int)((unsigned)m * 8u) : 0, RSRC_FLAGS);
     const int nchunks = (m + SW - 1 + C - 1) / C;
-    MStrip<W> S;
+    // every store of a step is inside the buffer by construction (strips * steps * 256 bytes); the
+    // resource drops whatever is not
+    const __amdgpu_buffer_rsrc_t trc =
+        TRACE ? __builtin_amdgcn_make_buffer_rsrc(a.trace + wp.trace_off, 0, (int)wp.trace_bytes, RSRC_FLAGS) : scr_rsrc;
+    unsigned toff = (unsigned)lane * 4u;
+    int bM = 0, bD = 0, bJ = 0;   // TRACE: the best of the strips so far: t, i + j, j
+    MStrip<W, TRACE> S;
     S.M = 0;
     for (int strip = 0; strip < strips; ++strip) {
         S.setup(a, pd, strip, lane, s_code);
+        if constexpr (TRACE) {
+            S.M = 0;
+            S.Mkp = 0;
+            S.kp8 = 0;
+        }
         const bool has_in = strip > 0;
         const bool has_out = strip < strips - 1;
         unsigned raw_nxt = mat_fetch_raw(row_rsrc, 0, lane, m);
@@ -196,7 +264,7 @@ __device__ void matrix_pair(const MatArgs& a, const MatPair& pd, const int lane,
             S.IOR = live ? (int)s_code[raw & 0xFFu] : a.k;
             S.IOH = has_in && live ? (int)g.x : -go;
             S.IOE = has_in && live ? (int)g.y : -ge;
-            S.run(l63, go, ge, s_tab);
+            S.run(l63, go, ge, s_tab, trc, toff);
             if (has_out) {   // lane l holds the right edge of row k0 + l - (SW - 1)
                 const int row_out = k0 + lane - (SW - 1);
                 const bool st = row_out >= 0 && row_out < m;
@@ -206,6 +274,30 @@ __device__ void matrix_pair(const MatArgs& a, const MatPair& pd, const int lane,
         }
         // the next strip (or the next pair's) reads what this one stored
         if (has_out) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
+        if constexpr (TRACE) {   // the lane's cell of this strip: column lane * W + p, reached at step k
+            const int k = S.Mkp >> 3, cl = lane * W + (S.Mkp & 7);
+            const int j = k - cl, d = strip * SW + k;
+            const bool better = S.M > bM || (S.M == bM && (d < bD || (d == bD && j < bJ)));
+            bM = better ? S.M : bM;
+            bD = better ? d : bD;
+            bJ = better ? j : bJ;
+        }
+    }
+    if constexpr (TRACE) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const int oM = __shfl_xor(bM, off), oD = __shfl_xor(bD, off), oJ = __shfl_xor(bJ, off);
+            const bool better = oM > bM || (oM == bM && (oD < bD || (oD == bD && oJ < bJ)));
+            bM = better ? oM : bM;
+            bD = better ? oD : bD;
+            bJ = better ? oJ : bJ;
+        }
+        // lane 0's store without a branch on the lane (below)
+        const __amdgpu_buffer_rsrc_t res_rsrc =
+            __builtin_amdgcn_make_buffer_rsrc(a.res, 0, (int)((unsigned)a.nscores * (unsigned)sizeof(TraceRes)), RSRC_FLAGS);
+        __builtin_amdgcn_raw_buffer_store_b128(u32x4{(unsigned)bM, (unsigned)(bD - bJ), (unsigned)bJ, 0u}, res_rsrc,
+                                               lane == 0 ? (unsigned)pd.out_idx * (unsigned)sizeof(TraceRes) : OOR, 0, 0);
+        return;
     }
     int M = S.M;
 #pragma unroll
@@ -218,7 +310,7 @@ __device__ void matrix_pair(const MatArgs& a, const MatPair& pd, const int lane,
     __builtin_amdgcn_raw_buffer_store_b32(M, sc_rsrc, lane == 0 ? (unsigned)pd.out_idx * 4u : OOR, 0, 0);
 }
 
-template <int W>
+template <int W, bool TRACE = false>
 __global__ void __launch_bounds__(256) sw_matrix_kernel(MatArgs a) {
     __shared__ unsigned s_tabw[2 * MAT_TAB_BYTES / 4];
     __shared__ unsigned s_codew[64];
@@ -243,8 +335,80 @@ __global__ void __launch_bounds__(256) sw_matrix_kernel(MatArgs a) {
         pd.m = __builtin_amdgcn_readfirstlane(raw.m);
         pd.out_idx = __builtin_amdgcn_readfirstlane(raw.out_idx);
         pd.swapped = __builtin_amdgcn_readfirstlane(raw.swapped);
-        matrix_pair<W>(a, pd, lane, scr, s_tab, s_code);
+        WalkPair wp{};
+        if constexpr (TRACE) {
+            const WalkPair wraw = a.walk[item];
+            wp.trace_off = uniform64(wraw.trace_off);
+            wp.trace_bytes = __builtin_amdgcn_readfirstlane(wraw.trace_bytes);
+        }
+        matrix_pair<W, TRACE>(a, pd, wp, lane, scr, s_tab, s_code);
     }
+}
+
+// The walk: one lane a pair, from the end cell in state H along the recorded decisions, the
+// operations (0 M, 1 I, 2 D) written last first.  Priorities (include/algoGPU.h): a cell with
+// H = 0 ends the walk before anything else; in H the diagonal, then E, then F; in E and F opening
+// before extending (both already decided by the fill: the bits say which).  Every iteration writes
+// one operation and there are at most n + m; every cell read is checked against the pair and its
+// buffer.  Nothing here waits for anything.
+struct WalkArgs {
+    const MatPair* pairs;
+    const WalkPair* walk;
+    const unsigned char* trace;
+    unsigned char* ops;
+    TraceRes* res;
+    int npairs;
+};
+
+__global__ void __launch_bounds__(64) sw_matrix_walk_kernel(WalkArgs w) {
+    const int item = (int)(blockIdx.x * 64 + threadIdx.x);
+    if (item >= w.npairs) return;
+    const MatPair pd = w.pairs[item];
+    const WalkPair wp = w.walk[item];
+    TraceRes* r = w.res + pd.out_idx;
+    int i = r->ei, j = r->ej, state = 0, err = 0, nops = 0;
+    const long long limit = (long long)pd.n + pd.m;
+    if (r->score > 0) {
+        const unsigned* tr = reinterpret_cast<const unsigned*>(w.trace + wp.trace_off);
+        unsigned char* ops = w.ops + wp.ops_off;
+        if (i >= pd.n || j >= pd.m) err = WALK_RANGE;
+        while (err == 0 && i >= 0 && j >= 0) {
+            const int cl = i & (64 * TRACE_W - 1);
+            const unsigned long long dw =
+                ((unsigned long long)(i / (64 * TRACE_W)) * (unsigned)wp.steps + (unsigned)(j + cl)) * 64u + (unsigned)(cl >> 3);
+            if (dw * 4u >= wp.trace_bytes) {
+                err = WALK_RANGE;
+                break;
+            }
+            const unsigned nib = (tr[dw] >> (4 * (cl & 7))) & 15u;
+            if (state == 0) {
+                const unsigned src = nib & 3u;
+                if (src == 0) break;
+                if (src != 1) state = (int)src - 1;   // E: 1, F: 2
+            }
+            if (nops >= limit) {
+                err = WALK_OVERRUN;
+                break;
+            }
+            if (state == 0) {
+                ops[nops++] = 0;
+                --i;
+                --j;
+            } else if (state == 1) {
+                ops[nops++] = 1;
+                state = (nib & 4u) ? 1 : 0;
+                --i;
+            } else {
+                ops[nops++] = 2;
+                state = (nib & 8u) ? 2 : 0;
+                --j;
+            }
+        }
+    }
+    r->bi = i + 1;
+    r->bj = j + 1;
+    r->nops = nops;
+    r->err = err;
 }
 
 // ---- host ------------------------------------------------------------------------------------
@@ -264,12 +428,13 @@ __global__ void __launch_bounds__(256) sw_matrix_kernel(MatArgs a) {
 struct MatCtx {
     int cus = 256;
     hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    void* buf[5] = {};      // pairs, ctrl, scratch, arena, scores
-    size_t cap[5] = {};
-    int wgs[4] = {0, 0, 0, 0};   // resident workgroups per CU per W variant
+    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
+    void* buf[9] = {};      // pairs, ctrl, scratch, arena, scores; traced launches: walk pairs, trace, results, operations
+    size_t cap[9] = {};
+    int wgs[5] = {0, 0, 0, 0, 0};   // resident workgroups per CU per W variant; [4]: the traced kernel
 };
-enum { B_PAIRS = 0, B_CTRL, B_SCRATCH, B_ARENA, B_SCORES };
+enum { B_PAIRS = 0, B_CTRL, B_SCRATCH, B_ARENA, B_SCORES, B_WALK, B_TRACE, B_RES, B_OPS };
+thread_local float t_fill_ms = 0.f, t_walk_ms = 0.f;   // sw_last_align_ms
 thread_local std::map<int, MatCtx*> t_mctx;
 
 MatCtx* get_mctx() {
@@ -284,7 +449,8 @@ MatCtx* get_mctx() {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, dev) != hipSuccess ||
         hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess) {
+        hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess ||
+        hipEventCreate(&c->ev2) != hipSuccess) {
         report_error("matrix scoring: device properties / stream / event creation failed");
         delete c;
         return nullptr;
@@ -342,6 +508,21 @@ struct DevSeq {
     int64_t a_off, b_off;
     int alen, blen, idx;
 };
+
+// the byte-to-code map and both orientations of the table, as the kernel stages them in LDS
+void stage_matrix(MatArgs& a, const sw_matrix* mx) {
+    a.k = mx->k;
+    std::memcpy(a.code, mx->code, 256);
+    signed char tab[2 * MAT_TAB_BYTES];
+    std::memset(tab, 0, sizeof tab);
+    for (int o = 0; o < 2; ++o)
+        for (int i = 0; i <= mx->k; ++i) {
+            signed char* row = tab + o * MAT_TAB_BYTES + i * MAT_STRIDE;
+            for (int j = 0; j < mx->k && i < mx->k; ++j) row[j] = o == 0 ? mx->sc[i * mx->k + j] : mx->sc[j * mx->k + i];
+            row[mx->k] = (signed char)MAT_SENT;
+        }
+    std::memcpy(a.tab, tab, sizeof tab);
+}
 
 // act: the pairs to launch (both lengths > 0); d_scores[idx] receives each score, every other
 // entry of d_scores[0, nscores) is zeroed.
@@ -425,17 +606,7 @@ int launch(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, std::ve
     a.nscores = nscores;
     a.gap_init = gap_init;
     a.gap_ext = gap_ext;
-    a.k = mx->k;
-    std::memcpy(a.code, mx->code, 256);
-    signed char tab[2 * MAT_TAB_BYTES];
-    std::memset(tab, 0, sizeof tab);
-    for (int o = 0; o < 2; ++o)
-        for (int i = 0; i <= mx->k; ++i) {
-            signed char* row = tab + o * MAT_TAB_BYTES + i * MAT_STRIDE;
-            for (int j = 0; j < mx->k && i < mx->k; ++j) row[j] = o == 0 ? mx->sc[i * mx->k + j] : mx->sc[j * mx->k + i];
-            row[mx->k] = (signed char)MAT_SENT;
-        }
-    std::memcpy(a.tab, tab, sizeof tab);
+    stage_matrix(a, mx);
 
     MCHK(hipEventRecord(c->ev0, c->stream));
     const dim3 grid((unsigned)blocks), block(256);
@@ -526,7 +697,190 @@ int score_host(const sw_matrix* mx, const unsigned char* const* a, const int* al
     return 0;
 }
 
+// trace bytes of one pair: strips * steps * 256 (WalkPair)
+long long trace_steps(long long m) { return (m + 64 * TRACE_W - 1 + MAT_C - 1) / MAT_C * MAT_C; }
+long long trace_bytes(long long n, long long m) { return (n + 64 * TRACE_W - 1) / (64 * TRACE_W) * trace_steps(m) * 256; }
+
+// One traced launch: fill, then walk.  act: the pairs (both lengths > 0, idx = the slot of res and
+// of ops_off), in input order.  res[idx] and the operations (ops, at ops_off[idx]) come back to the host.
+struct TracedOut {
+    std::vector<TraceRes> res;
+    std::vector<unsigned char> ops;
+    std::vector<uint64_t> ops_off;
+    long long trace_total = 0;
+    int blocks = 0;
+};
+int launch_traced(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, const std::vector<DevSeq>& act,
+                  int gap_init, int gap_ext, TracedOut& o) {
+    constexpr int SW = 64 * TRACE_W;
+    const size_t np = act.size();
+    // longest first: the waves claim in order
+    std::vector<int> order(np);
+    std::iota(order.begin(), order.end(), 0);
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) {
+        return (long long)act[x].alen * act[x].blen > (long long)act[y].alen * act[y].blen;
+    });
+    std::vector<MatPair> pairs(np);
+    std::vector<WalkPair> walk(np);
+    o.ops_off.assign(np, 0);
+    uint64_t ops_total = 0;
+    for (size_t k = 0; k < np; ++k) {   // the operations in input order
+        o.ops_off[k] = ops_total;
+        ops_total += (uint64_t)act[k].alen + (uint64_t)act[k].blen;
+    }
+    long long scratch_rows = 0, trace_total = 0;
+    for (size_t s = 0; s < np; ++s) {
+        const DevSeq& p = act[(size_t)order[s]];
+        MatPair& d = pairs[s];
+        d.col_off = (uint64_t)p.a_off;
+        d.row_off = (uint64_t)p.b_off;
+        d.n = p.alen;
+        d.m = p.blen;
+        d.out_idx = order[s];
+        d.swapped = 0;
+        if (d.n > SW) scratch_rows = std::max<long long>(scratch_rows, d.m);
+        WalkPair& w = walk[s];
+        w.trace_off = (uint64_t)trace_total;
+        w.ops_off = o.ops_off[(size_t)order[s]];
+        w.trace_bytes = (unsigned)trace_bytes(p.alen, p.blen);
+        w.steps = (int)trace_steps(p.blen);
+        trace_total += trace_bytes(p.alen, p.blen);
+    }
+    if (c->wgs[4] == 0) {
+        int nb = 0;
+        MCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)sw_matrix_kernel<TRACE_W, true>, 256, 0));
+        c->wgs[4] = std::max(1, std::min(nb, 8));
+    }
+    long long blocks = sw_get_option("blocks");
+    if (blocks <= 0) blocks = (long long)c->cus * c->wgs[4];
+    blocks = std::max<long long>(1, std::min<long long>(blocks, ((long long)np + 3) / 4));
+    scratch_rows = (scratch_rows + 63) / 64 * 64;
+    if (scratch_rows > 0) blocks = std::max<long long>(1, std::min<long long>(blocks, (1LL << 30) / (scratch_rows * 8 * 4)));
+    const size_t scratch_bytes = (size_t)scratch_rows * 8 * 4 * (size_t)blocks;
+    if (ensure(c, B_PAIRS, np * sizeof(MatPair)) || ensure(c, B_CTRL, sizeof(Ctrl)) || ensure(c, B_SCRATCH, scratch_bytes) ||
+        ensure(c, B_WALK, np * sizeof(WalkPair)) || ensure(c, B_TRACE, (size_t)trace_total) ||
+        ensure(c, B_RES, np * sizeof(TraceRes)) || ensure(c, B_OPS, (size_t)ops_total))
+        return -1;
+    MCHK(hipMemcpyAsync(c->buf[B_PAIRS], pairs.data(), np * sizeof(MatPair), hipMemcpyHostToDevice, c->stream));
+    MCHK(hipMemcpyAsync(c->buf[B_WALK], walk.data(), np * sizeof(WalkPair), hipMemcpyHostToDevice, c->stream));
+    MCHK(hipMemsetAsync(c->buf[B_CTRL], 0, sizeof(Ctrl), c->stream));
+    MCHK(hipMemsetAsync(c->buf[B_RES], 0, np * sizeof(TraceRes), c->stream));
+
+    MatArgs a{};
+    a.seq = d_arena;
+    a.pairs = (const MatPair*)c->buf[B_PAIRS];
+    a.ctrl = (Ctrl*)c->buf[B_CTRL];
+    a.scores = nullptr;
+    a.scratch = (uint2*)c->buf[B_SCRATCH];
+    a.scratch_rows = scratch_rows;
+    a.npairs = (int)np;
+    a.nscores = (int)np;
+    a.gap_init = gap_init;
+    a.gap_ext = gap_ext;
+    stage_matrix(a, mx);
+    a.walk = (const WalkPair*)c->buf[B_WALK];
+    a.trace = (unsigned char*)c->buf[B_TRACE];
+    a.res = (TraceRes*)c->buf[B_RES];
+    WalkArgs w{a.pairs, a.walk, a.trace, (unsigned char*)c->buf[B_OPS], a.res, (int)np};
+
+    MCHK(hipEventRecord(c->ev0, c->stream));
+    hipLaunchKernelGGL((sw_matrix_kernel<TRACE_W, true>), dim3((unsigned)blocks), dim3(256), 0, c->stream, a);
+    MCHK(hipGetLastError());
+    MCHK(hipEventRecord(c->ev1, c->stream));
+    hipLaunchKernelGGL(sw_matrix_walk_kernel, dim3((unsigned)((np + 63) / 64)), dim3(64), 0, c->stream, w);
+    MCHK(hipGetLastError());
+    MCHK(hipEventRecord(c->ev2, c->stream));
+    o.res.resize(np);
+    o.ops.resize((size_t)ops_total);
+    MCHK(hipMemcpyAsync(o.res.data(), c->buf[B_RES], np * sizeof(TraceRes), hipMemcpyDeviceToHost, c->stream));
+    MCHK(hipMemcpyAsync(o.ops.data(), c->buf[B_OPS], (size_t)ops_total, hipMemcpyDeviceToHost, c->stream));
+    MCHK(hipStreamSynchronize(c->stream));
+    float fill = 0.f, wk = 0.f;
+    MCHK(hipEventElapsedTime(&fill, c->ev0, c->ev1));
+    MCHK(hipEventElapsedTime(&wk, c->ev1, c->ev2));
+    t_fill_ms += fill;
+    t_walk_ms += wk;
+    o.trace_total = trace_total;
+    o.blocks = (int)blocks;
+    return 0;
+}
+
 }  // namespace
+
+int matrix_align_device(const sw_matrix* mx, const unsigned char* d_arena, const int64_t* a_off, const int* alen,
+                        const int64_t* b_off, const int* blen, const int* name_idx, int npairs, int gap_init,
+                        int gap_ext, const char* what, AlignSink& sink) {
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!gaps_ok(gap_init, gap_ext)) return -1;
+    const long long budget = sw_get_option("trace_mb") << 20;
+    for (int k = 0; k < npairs; ++k) {   // refused before anything is launched
+        if (alen[k] == 0 || blen[k] == 0) continue;
+        const long long need = trace_bytes(alen[k], blen[k]);
+        if (need > budget) {
+            char m[240];
+            std::snprintf(m, sizeof m,
+                          "%s %d: a %d x %d alignment needs %lld bytes of trace memory, more than option trace_mb = %lld MiB "
+                          "(linear-space alignment is not built)",
+                          what, name_idx ? name_idx[k] : k, alen[k], blen[k], need, budget >> 20);
+            report_error(m);
+            return -1;
+        }
+    }
+    MatCtx* c = get_mctx();
+    if (!c) return -1;
+    t_fill_ms = t_walk_ms = 0.f;
+    sw_stats st{};
+    st.mode = MODE_MATRIX_TRACE;
+    st.W = TRACE_W;
+    st.C = MAT_C;
+    st.items = npairs;
+    std::vector<DevSeq> act;
+    TracedOut o;
+    int lo = 0;
+    while (lo < npairs) {   // pairs [lo, hi): as many as fit the budget, in input order
+        int hi = lo;
+        long long sum = 0;
+        act.clear();
+        for (; hi < npairs; ++hi) {
+            if (alen[hi] == 0 || blen[hi] == 0) continue;
+            const long long need = trace_bytes(alen[hi], blen[hi]);
+            if (!act.empty() && sum + need > budget) break;
+            sum += need;
+            act.push_back(DevSeq{a_off[hi], b_off[hi], alen[hi], blen[hi], hi});
+            st.cells += (long long)alen[hi] * blen[hi];
+        }
+        if (!act.empty()) {
+            if (launch_traced(c, mx, d_arena, act, gap_init, gap_ext, o)) return -1;
+            st.variant += 1;
+            st.blocks = o.blocks;
+            st.waves_per_cu = 4 * c->wgs[4];
+            st.boundary_bytes = std::max(st.boundary_bytes, o.trace_total);
+        }
+        size_t s = 0;
+        for (int k = lo; k < hi; ++k) {
+            if (alen[k] == 0 || blen[k] == 0) {
+                sink.set_empty(k);
+                continue;
+            }
+            const TraceRes& r = o.res[s];
+            if (r.err != 0 || r.nops < 0 || r.nops > alen[k] + (long long)blen[k]) {
+                char m[200];
+                std::snprintf(m, sizeof m, "%s %d: the traceback walk failed (%s)", what, name_idx ? name_idx[k] : k,
+                              r.err == WALK_OVERRUN ? "more than n + m operations" : "a cell outside the trace buffer");
+                report_error(m);
+                return -1;
+            }
+            if (r.score <= 0) sink.set_empty(k);
+            else sink.set(k, r.score, r.bi, r.ei + 1, r.bj, r.ej + 1, o.ops.data() + o.ops_off[s], r.nops);
+            ++s;
+        }
+        lo = hi;
+    }
+    st.kernel_ms = t_fill_ms;
+    st.total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    report_stats(st);
+    return 0;
+}
 
 int matrix_score_device(const sw_matrix* mx, const unsigned char* d_arena, const int64_t* a_off, const int* alen,
                         const int64_t* b_off, const int* blen, int npairs, int gap_init, int gap_ext, int* d_scores,
@@ -566,6 +920,46 @@ int sw_score_matrix(const sw_matrix* mx, const unsigned char* seq1, const unsign
     int out = 0;
     if (score_host(mx, &seq1, &n, &seq2, &m, 1, gap_init, gap_ext, &out)) return -1;
     return out;
+}
+
+int sw_align_matrix_batch(const sw_matrix* mx, const unsigned char* const* a, const int* alen,
+                          const unsigned char* const* b, const int* blen, int npairs, int gap_init, int gap_ext,
+                          sw_alignment* out, unsigned* cigar, long long cigar_cap, long long* cigar_used) {
+    if (align_check("sw_align_matrix_batch", mx, a, alen, b, blen, npairs, gap_init, gap_ext, out, cigar, cigar_cap,
+                    cigar_used))
+        return -1;
+    AlignSink sink{out, {}};
+    if (npairs == 0) return sink.finish(cigar, cigar_cap, cigar_used);
+    MatCtx* c = get_mctx();
+    if (!c) return -1;
+    // the sequences of the pairs with both lengths > 0, as score_host lays them out
+    std::vector<int64_t> a_off((size_t)npairs, 0), b_off((size_t)npairs, 0);
+    size_t total = 0;
+    for (int k = 0; k < npairs; ++k) {
+        if (alen[k] == 0 || blen[k] == 0) continue;
+        a_off[(size_t)k] = (int64_t)total;
+        total += ((size_t)alen[k] + 15) / 16 * 16;
+        b_off[(size_t)k] = (int64_t)total;
+        total += ((size_t)blen[k] + 15) / 16 * 16;
+    }
+    std::vector<unsigned char> arena(total);
+    for (int k = 0; k < npairs; ++k) {
+        if (alen[k] == 0 || blen[k] == 0) continue;
+        std::memcpy(arena.data() + a_off[(size_t)k], a[k], (size_t)alen[k]);
+        std::memcpy(arena.data() + b_off[(size_t)k], b[k], (size_t)blen[k]);
+    }
+    if (ensure(c, B_ARENA, total)) return -1;
+    // (synchronous: a refusal below returns before anything is launched or waited for)
+    if (total) MCHK(hipMemcpy(c->buf[B_ARENA], arena.data(), total, hipMemcpyHostToDevice));
+    if (matrix_align_device(mx, (const unsigned char*)c->buf[B_ARENA], a_off.data(), alen, b_off.data(), blen, nullptr,
+                            npairs, gap_init, gap_ext, "pair", sink))
+        return -1;
+    return sink.finish(cigar, cigar_cap, cigar_used);
+}
+
+void sw_last_align_ms(float* fill_ms, float* walk_ms) {
+    if (fill_ms) *fill_ms = t_fill_ms;
+    if (walk_ms) *walk_ms = t_walk_ms;
 }
 
 }  // extern "C"

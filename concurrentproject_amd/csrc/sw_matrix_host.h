@@ -5,6 +5,9 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <vector>
+
+#include "../../include/algoGPU.h"
 
 constexpr int SW_MATRIX_MAX_K = 32;
 constexpr int SW_MATRIX_NOCODE = 0xFF;   // code[] of a byte outside the alphabet when other = -1
@@ -38,4 +41,38 @@ long long matrix_first_bad(const sw_matrix* m, const unsigned char* p, long long
 int matrix_score_device(const sw_matrix* m, const unsigned char* d_arena, const int64_t* a_off, const int* alen,
                         const int64_t* b_off, const int* blen, int npairs, int gap_init, int gap_ext,
                         int* d_scores, bool a_on_lanes);
+
+// ---- alignments (sw_align_host.cpp: host only; the traced launch is in sw_matrix.hip) ----
+
+// the argument, gap, length, score-range and alphabet checks of sw_align_matrix_batch / _cpu, with
+// the messages of sw_score_matrix_batch; fn names the entry point.  0 or -1.
+int align_check(const char* fn, const sw_matrix* m, const unsigned char* const* a, const int* alen,
+                const unsigned char* const* b, const int* blen, int npairs, int gap_init, int gap_ext,
+                const sw_alignment* out, const unsigned* cigar, long long cigar_cap, const long long* cigar_used);
+// the int32 engine's score range (min length * largest entry < 2^28); the message names `what idx`
+bool align_range_ok(const sw_matrix* m, int alen, int blen, const char* what, int idx);
+
+// reverse and run-length encode: ops_rev[0, nops) are a walk's operations (0 M, 1 I, 2 D), last
+// first; appends (length << 4) | op entries, first operation first, to out and returns how many
+int encode_ops(const unsigned char* ops_rev, long long nops, std::vector<unsigned>& out);
+
+// collects the alignments of one call: out[k] and the cigar entries of every pair, in the order
+// they are set (cigar_off); finish() hands the entries over, or returns -1 when cigar_cap is too
+// small (*cigar_used is what is needed either way)
+struct AlignSink {
+    sw_alignment* out;
+    std::vector<unsigned> cig;
+    void set(int k, int score, int beg1, int end1, int beg2, int end2, const unsigned char* ops_rev, long long nops);
+    void set_empty(int k);   // score 0 or an empty sequence: empty ranges at 0, no operations
+    int finish(unsigned* cigar, long long cigar_cap, long long* cigar_used);
+};
+
+// The traced launches of sw_matrix.hip over pairs resident in device memory (as matrix_score_device:
+// seq1 always across the lanes, bytes checked by the caller): sink.out[k] for every pair k, in order.
+// Pairs are packed greedily in input order into launches of at most option "trace_mb" MiB of trace
+// memory; a pair that does not fit alone is refused (-1; the message names it `what` name_idx[k], or
+// `what` k when name_idx is null).
+int matrix_align_device(const sw_matrix* m, const unsigned char* d_arena, const int64_t* a_off, const int* alen,
+                        const int64_t* b_off, const int* blen, const int* name_idx, int npairs, int gap_init,
+                        int gap_ext, const char* what, AlignSink& sink);
 }  // namespace swmi

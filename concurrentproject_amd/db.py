@@ -21,7 +21,7 @@ import os
 
 import numpy as np
 
-from . import SwError, _check, _ptr, _u8, lib
+from . import SwError, _align_call, _check, _ptr, _u8, lib
 
 
 class Database:
@@ -142,8 +142,27 @@ class Database:
         _check(lib().sw_db_search_db(self._h, queries._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
         return out
 
-    def top(self, query, k: int = 10, matrix=None, gap_init=None, gap_ext=None) -> list:
-        """The k best records: [(score, index, header)], score descending, index ascending on ties."""
+    def align(self, query, indices, matrix, gap_init: int, gap_ext: int) -> list:
+        """An :class:`Alignment` of ``query`` (seq1) with each record of ``indices``, out of the
+        database's device arena (sw_db_align_matrix): only the query is uploaded."""
+        q = _u8(query)
+        idx = [int(i) for i in indices]
+        n = len(idx)
+        if n == 0:
+            return []
+        IDX = (ctypes.c_int * n)(*idx)
+        return _align_call(lambda out, cig, cap, used: lib().sw_db_align_matrix(
+            self._h, matrix._handle(), _ptr(q), len(q), IDX, n, int(gap_init), int(gap_ext), out, cig, cap, used), n, 16 * n)
+
+    def top(self, query, k: int = 10, matrix=None, gap_init=None, gap_ext=None, alignments: bool = False) -> list:
+        """The k best records: [(score, index, header)], score descending, index ascending on ties.
+        With ``alignments=True`` (a matrix search) each tuple ends with the hit's :class:`Alignment`."""
         sc = self.search(query, matrix=matrix, gap_init=gap_init, gap_ext=gap_ext)
         idx = np.lexsort((np.arange(len(sc)), -sc.astype(np.int64)))[:k]
-        return [(int(sc[i]), int(i), self.header(int(i))) for i in idx]
+        hits = [(int(sc[i]), int(i), self.header(int(i))) for i in idx]
+        if not alignments:
+            return hits
+        if matrix is None:
+            raise SwError("alignments=True needs matrix= (Matrix.equality gives the table of an equality scoring)")
+        al = self.align(query, [h[1] for h in hits], matrix, gap_init, gap_ext)
+        return [h + (x,) for h, x in zip(hits, al)]

@@ -98,7 +98,9 @@ int sw_batch_gather_plan(int npairs, int ngpus, int* count, int* offset);
  * the engine's own stream, and then the call is synchronous).
  * flags: SW_FLAG_DNA asserts every byte is in {A,C,G,T} (skips the alphabet
  * scan), SW_FLAG_BYTES forces the raw-byte path.  After an asynchronous call,
- * sw_stream_status(stream) synchronises and reports kernel-side failures. */
+ * sw_stream_status(stream) synchronises and reports kernel-side failures; it is also
+ * the point after which the engine no longer refers to the caller's stream, so call it
+ * before destroying a stream that such a call ran on. */
 #define SW_FLAG_DNA   1
 #define SW_FLAG_BYTES 2
 int sw_score_batch_device(const unsigned char* d_arena,
@@ -238,6 +240,72 @@ int  sw_db_search_matrix(sw_db*, const sw_matrix*, const unsigned char* query, i
 int  sw_db_search_db_matrix(sw_db*, const sw_db* queries, const sw_matrix*,
                             int gap_init, int gap_ext, int* scores_out);
 
+/* ---- alignments under a substitution matrix (no reference counterpart: the reference
+ * scores only) -------------------------------------------------------------------
+ * Per pair: the score (the one sw_score_matrix returns), the half-open ranges
+ * [beg1, end1) of seq1 and [beg2, end2) of seq2 that the alignment covers, and its
+ * operations, run-length encoded, first operation first, as ncigar entries
+ * (length << 4) | op at cigar[cigar_off]: op 0 = M (a residue of seq1 aligned with one
+ * of seq2), 1 = I (a residue of seq1 against a gap), 2 = D (a residue of seq2 against a
+ * gap).  The M entries' table scores minus gap_init + (L-1) * min(gap_ext, gap_init) for
+ * every maximal run of L equal gap operations add up to the score exactly (where extending
+ * costs more than opening, the recurrence itself opens a new gap for every residue).
+ *
+ * Which alignment, where several reach the score -- stated in sequence positions only,
+ * so it does not depend on the kernel's tiling, the grid or the rest of the batch:
+ *   END CELL.  Positions i in seq1 and j in seq2 (0-based), t(i, j) = H[i-1][j-1] +
+ *     s(seq1[i], seq2[j]) the diagonal arrival.  Among the cells with t(i, j) == score
+ *     the end cell is the one with the smallest i + j and, among those, the smallest j.
+ *     (t, not H: with gap_init = 0 a cell can reach the score through a free gap, and an
+ *     alignment does not end in a gap.)  end1 = i + 1, end2 = j + 1.
+ *   WALK.  From the end cell in state H, backwards.  In state H: a cell with H = 0 ends
+ *     the walk (tested before anything else, so the first and the last operation are M);
+ *     else H = t takes the diagonal (M), else H = E enters state E, else state F.  State E
+ *     emits I and steps to i - 1, state F emits D and steps to j - 1; each returns to
+ *     state H if the gap was opened there (E = H[i-1][j] - gap_init) and stays if it was
+ *     extended, OPENING BEFORE EXTENDING on a tie.  An I may therefore stand next to a D
+ *     (the gap opened from a cell whose H came from the other gap state): they are two
+ *     gaps and cost two openings.
+ * A pair with score 0 or an empty sequence yields score 0, the four coordinates 0 and no
+ * operations (cigar_off still points into the buffer's used part).
+ *
+ * sw_align_matrix_batch: the GPU path: the traced variant of the matrix kernel records 4
+ *   bits a cell (sw_matrix.hip), a second kernel walks them, the host reverses and encodes.
+ *   seq1 always lies across the lanes: no per-pair swap.  Trace memory is about n * m / 2
+ *   bytes a pair plus 128 KiB per strip of 512 seq1 positions, and a launch holds at most
+ *   option "trace_mb" MiB of it (default 1024): a batch that does not fit runs as several
+ *   launches, packed greedily in input order; ONE PAIR THAT DOES NOT FIT ALONE IS REFUSED
+ *   (-1, sw_last_error names the pair and the bytes).  Linear-space alignment of very long
+ *   pairs is not built.  Arguments, gap penalties, the score range and the alphabet are
+ *   checked as sw_score_matrix_batch checks them.  cigar_cap: entries of cigar;
+ *   *cigar_used receives the entries needed, and too small a cigar_cap returns -1 (out is
+ *   filled, cigar is not).  Option "W" is not honoured (one traced instantiation, W = 8);
+ *   "blocks" is.  sw_last_stats: mode 7, boundary_bytes = trace bytes of the largest
+ *   launch, blocks = workgroups of the last, variant = launches, kernel_ms = the fill
+ *   kernels; sw_last_align_ms splits the device time into fill and walk.
+ * sw_align_matrix_cpu: the same result from a plain full-matrix aligner on the host (n * m
+ *   bytes a pair, at most 2^32 cells): the checker of the GPU path, and a fallback.
+ * sw_db_align_matrix: the query (seq1) against records record_idx[0, nidx) of the
+ *   database, out of its device arena: only the query is uploaded.  out[k] belongs to
+ *   record_idx[k]; an index may repeat.
+ * Limits: one wave fills one pair and one lane walks it, so this is for the hits of a
+ * search, not for every pair of it. */
+typedef struct { int score, beg1, end1, beg2, end2, ncigar; long long cigar_off; } sw_alignment;
+int  sw_align_matrix_batch(const sw_matrix*, const unsigned char* const* a, const int* alen,
+                           const unsigned char* const* b, const int* blen, int npairs,
+                           int gap_init, int gap_ext, sw_alignment* out,
+                           unsigned* cigar, long long cigar_cap, long long* cigar_used);
+int  sw_align_matrix_cpu(const sw_matrix*, const unsigned char* const* a, const int* alen,
+                         const unsigned char* const* b, const int* blen, int npairs,
+                         int gap_init, int gap_ext, sw_alignment* out,
+                         unsigned* cigar, long long cigar_cap, long long* cigar_used);
+int  sw_db_align_matrix(sw_db*, const sw_matrix*, const unsigned char* query, int qlen,
+                        const int* record_idx, int nidx, int gap_init, int gap_ext,
+                        sw_alignment* out, unsigned* cigar, long long cigar_cap, long long* cigar_used);
+/* device time of this thread's last sw_align_matrix_batch / sw_db_align_matrix call, summed
+ * over its launches (either pointer may be NULL) */
+void sw_last_align_ms(float* fill_ms, float* walk_ms);
+
 /* Tuning knobs (process-wide).  Keys:
  *   "W"        columns per lane: 0 = auto, 1, 2, 4, 8
  *   "C"        rows per strip hand-off chunk: 0 = auto, 16, 32, 64
@@ -254,7 +322,9 @@ int  sw_db_search_db_matrix(sw_db*, const sw_db* queries, const sw_matrix*,
  *                  LDS / granule hand-offs; the automatic plan for single long pairs, column
  *                  slabs and batches whose scores need int32)
  *              (sw_last_stats also reports mode 6 = wave per pair, substitution matrix: the
- *              sw_*_matrix entry points, which honour "blocks" and "W" only)
+ *              sw_*_matrix entry points, which honour "blocks" and "W" only; and mode 7 = the
+ *              traced launches of sw_align_matrix_batch / sw_db_align_matrix: "blocks", "trace_mb")
+ *   "trace_mb" MiB of trace memory one traced launch may hold, 1..3072 (default 1024)
  *   "duo16"    1 = (default) packed duos take max3 through v_pk_maximum3_f16 when every
  *              value stays below 0x7C00 (MATCH*(min(n,m)+1) <= 31743), 0 = u16 max only
  *   "linear"   -1 = (default) the exact linear-gap step when G_INIT == G_EXT

@@ -9,8 +9,13 @@ the 20 amino-acid letters (SwissProt-style; the engine's byte path, duo kernels 
 wave-per-pair kernel of sw_matrix.hip): FILE in the NCBI text format, or "random": a seeded random table over the
 alphabet's letters with diagonal entries in [4, 11] and off-diagonal entries in [-4, 3].
 
+--alignments K (with --matrix): a second line: the search plus aligning its top K (Database.top(alignments=True):
+sw_db_align_matrix, the traced kernel and the walk) next to the search alone, the traced kernel against the
+score-only kernel at the same W on those K pairs, the walk's time and the trace bytes.  --plant P replaces P records
+by mutated copies of the query, so that the top hits have real alignments (with neither, nothing changes).
+
     python tools/bench_db.py [--records R] [--qlen Q] [--lo L] [--hi H] [--steps K] [--alphabet dna|protein]
-                             [--opt k=v ...] [--matrix random|FILE --gaps G_INIT,G_EXT]
+                             [--opt k=v ...] [--matrix random|FILE --gaps G_INIT,G_EXT] [--alignments K] [--plant P]
 """
 import argparse
 import json
@@ -37,9 +42,13 @@ def main():
     ap.add_argument("--opt", action="append", default=[], help="engine option k=v (sw_set_option), repeatable")
     ap.add_argument("--matrix", default=None, help="'random' or a matrix file: search under a substitution matrix")
     ap.add_argument("--gaps", default=None, help="G_INIT,G_EXT of a --matrix search")
+    ap.add_argument("--alignments", type=int, default=0, help="also time the search plus aligning its top K (--matrix)")
+    ap.add_argument("--plant", type=int, default=0, help="records replaced by mutated copies of the query")
     a = ap.parse_args()
     if (a.matrix is None) != (a.gaps is None):
         ap.error("--matrix and --gaps go together")
+    if a.alignments and a.matrix is None:
+        ap.error("--alignments needs --matrix")
     import concurrentproject_amd as sw
     for kv in a.opt:
         k, v = kv.split("=")
@@ -50,8 +59,22 @@ def main():
     parts = []
     for i, n in enumerate(lens):
         parts.append(b">r%d\n" % i + acgt[rng.integers(0, len(acgt), size=n)].tobytes() + b"\n")
-    db = Database.from_fasta(b"".join(parts))
     q = acgt[rng.integers(0, len(acgt), size=a.qlen)]
+    if a.plant:   # (after every draw above, so that a run without --plant has the inputs it always had)
+        prng = np.random.default_rng(5)
+        for i in prng.choice(a.records, a.plant, replace=False):
+            h = q.copy()
+            sub = prng.random(len(h)) < 0.3
+            h[sub] = acgt[prng.integers(0, len(acgt), int(sub.sum()))]
+            for _ in range(4):
+                at = int(prng.integers(1, len(h) - 8))
+                h = np.delete(h, slice(at, at + int(prng.integers(1, 8))))
+            n = int(lens[i])
+            pad = acgt[prng.integers(0, len(acgt), size=max(n - len(h), 0))]
+            cut = int(prng.integers(0, len(pad) + 1))
+            rec = np.concatenate([pad[:cut], h, pad[cut:]])[:n]
+            parts[i] = b">r%d\n" % i + rec.tobytes() + b"\n"
+    db = Database.from_fasta(b"".join(parts))
     kw, extra = {}, {}
     if a.matrix is not None:
         if a.matrix == "random":
@@ -77,6 +100,41 @@ def main():
                       "unit": "GCUPS", "ms_per_search": round(dt * 1e3, 3), "records": a.records,
                       "residues": int(lens.sum()), "qlen": a.qlen, "len_range": [a.lo, a.hi],
                       "max_score": int(sc.max())}))
+    if a.alignments:
+        K = a.alignments
+        top = db.top(q, k=K, **kw, alignments=True)   # warm: the trace buffers are allocated here
+        t0 = time.perf_counter()
+        for _ in range(a.steps):
+            top = db.top(q, k=K, **kw, alignments=True)
+        dta = (time.perf_counter() - t0) / a.steps
+        t0 = time.perf_counter()
+        for _ in range(a.steps):
+            db.top(q, k=K, **kw)
+        dts = (time.perf_counter() - t0) / a.steps
+        idx = [t[1] for t in top]
+        fills, walks = [], []
+        for _ in range(a.steps):
+            al = db.align(q, idx, mx, gi, ge)
+            sta = sw.last_stats()
+            f, w = sw.last_align_ms()
+            fills.append(f)
+            walks.append(w)
+        pairs = [(q, np.frombuffer(db.record(i)[1], np.uint8)) for i in idx]
+        sw.set_option("W", sta["W"])                     # the score-only kernel at the traced kernel's W, same pairs
+        plain = []
+        for _ in range(a.steps + 1):
+            assert sw.score_matrix_batch(pairs, mx, gi, ge) == [x.score for x in al]
+            plain.append(sw.last_stats()["kernel_ms"])
+        sw.set_option("W", 0)
+        kcells = sum(len(y) for _, y in pairs) * a.qlen
+        fill, walk, score_ms = float(np.median(fills)), float(np.median(walks)), float(np.median(plain[1:]))
+        print(json.dumps({**extra, "metric": "db search + alignments of the top K (host API)", "alphabet": a.alphabet, "K": K,
+                          "planted": a.plant, "ms_search_top": round(dts * 1e3, 3), "ms_search_top_aligned": round(dta * 1e3, 3),
+                          "W": sta["W"], "launches": sta["variant"], "trace_bytes": sta["boundary_bytes"], "cells": kcells,
+                          "fill_kernel_ms": round(fill, 4), "fill_GCUPS": round(kcells / fill / 1e6, 2),
+                          "score_kernel_ms_same_W": round(score_ms, 4), "score_GCUPS_same_W": round(kcells / score_ms / 1e6, 2),
+                          "walk_kernel_ms": round(walk, 4), "cigar_ops_mean": round(float(np.mean([len(x.ops) for x in al])), 1),
+                          "aligned_span_mean": round(float(np.mean([x.end1 - x.beg1 for x in al])), 1)}))
     if a.queries:
         from concurrentproject_amd.db import Database as D
         qrecs = [("q%d" % k, acgt[rng.integers(0, len(acgt), size=a.qlen)].tobytes()) for k in range(a.queries)]
