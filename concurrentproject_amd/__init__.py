@@ -139,6 +139,9 @@ def lib() -> ctypes.CDLL:
     vp = ctypes.c_void_p
     L.sw_slab_bounds.argtypes = [ctypes.c_longlong, i, i, i, ctypes.POINTER(ctypes.c_longlong)]
     L.sw_slab_bounds.restype = i
+    if hasattr(L, "sw_split_bounds"):   # (absent from older builds that SWMI355_LIB may name for an A/B)
+        L.sw_split_bounds.argtypes = [i, ctypes.POINTER(i), ctypes.POINTER(i)]
+        L.sw_split_bounds.restype = i
     L.sw_score_slab_device.argtypes = [vp, ctypes.c_int64, i, ctypes.c_int64, i, vp, vp, ctypes.c_uint, vp, i, vp]
     L.sw_score_slab_device.restype = i
     L.sw_slab_alloc.argtypes = [i, ctypes.POINTER(vp), ctypes.c_char_p]
@@ -337,6 +340,14 @@ def slab_bounds(n: int, m: int, nslabs: int, flags: int) -> list:
     out = (ctypes.c_longlong * (nslabs + 1))()
     _check(lib().sw_slab_bounds(int(n), int(m), int(nslabs), int(flags), out))
     return [int(x) for x in out]
+
+
+def split_bounds(n: int):
+    """Where option f3split cuts one pair of n columns: (cut, lead, strips of both halves), or
+    None when n is too narrow (each half needs two strips of 126 new columns)."""
+    c, lead = ctypes.c_int(), ctypes.c_int()
+    strips = _check(lib().sw_split_bounds(int(n), ctypes.byref(c), ctypes.byref(lead)))
+    return (c.value, lead.value, strips) if strips else None
 
 
 class SlabBuffer:

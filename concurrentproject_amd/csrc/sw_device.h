@@ -79,6 +79,8 @@ __device__ __forceinline__ PairDesc load_pair(const KParams& kp, int idx) {
     pd.m = __builtin_amdgcn_readfirstlane(raw.m);
     pd.strips = __builtin_amdgcn_readfirstlane(raw.strips);
     pd.out_idx = __builtin_amdgcn_readfirstlane(raw.out_idx);
+    pd.flags = __builtin_amdgcn_readfirstlane(raw.flags);
+    pd.lead = __builtin_amdgcn_readfirstlane(raw.lead);
     return pd;
 }
 

@@ -66,7 +66,7 @@ std::atomic<long long> g_opt_W{0}, g_opt_C{0}, g_opt_bytes{0}, g_opt_timeout{30}
     g_opt_mode{-1}, g_opt_trace{0}, g_opt_duo_f16{1}, g_opt_f2stream{0}, g_opt_ring{-1}, g_opt_ring_rows{4096}, g_opt_f2_wgs{0}, g_opt_f2w{0}, g_opt_f2pwg{-1},
     g_opt_linear{-1}, g_opt_f3{1}, g_opt_slab_plain{0}, g_opt_duo_lds{1}, g_opt_duo_tab{1}, g_opt_duo_roles{1}, g_opt_f3hl{1},
     g_opt_f3rhl{0}, g_opt_f3a{1}, g_opt_f3slab{1}, g_opt_duo_prio{-1}, g_opt_f3pool{0},
-    g_opt_stall_item{-1}, g_opt_f3pwg{1}, g_opt_duo_raw{1}, g_opt_hep{1}, g_opt_trace_mb{1024};
+    g_opt_stall_item{-1}, g_opt_f3pwg{1}, g_opt_duo_raw{1}, g_opt_hep{1}, g_opt_trace_mb{1024}, g_opt_f3split{-1};
 
 // Longest sequence the engine takes: granule buffers of m rows keep m * 16 in the
 // 32-bit record count of a buffer resource (sw_device.h linear_edge).
@@ -537,6 +537,57 @@ bool hep_launchable(const Job& job, const Params& prm) {
     return !lin && g_opt_f3a.load() != 0 && (job.C == 32 || job.C == 16) && flow3_fits(max_m, job.C, true);
 }
 
+// One pair on flow3's staged two-column linear-gap kernel, cut at a column and scored from both ends at
+// once: the left half, columns [0, c), runs forward; the right half, columns
+// [c, n), runs on both sequences mirrored, with `lead` dead columns in front so that its last strip's
+// last new column is the cut column too.  With one value per grid node the pair's score is the larger of
+// the halves' maxima and of max over i of H_L[i][c] + H_R[m - i][n - c] (sw_flow3.hip
+// sw_flow3_combine_kernel), so the two chains of half the strips run side by side.  c and
+// n - c + lead are multiples of 126; each half gets at least two strips, hence n >= 379.
+bool split_cols(int n, int* c, int* lead) {
+    const int kl = std::max(2, (n + 125) / 126 / 2);   // half the strips, the odd one to the right
+    if ((long long)n - 126LL * kl < 127) return false;
+    *c = 126 * kl;
+    *lead = (126 - (n - *c) % 126) % 126;
+    return true;
+}
+// Narrowest pair the automatic plan cuts (option f3split = -1)
+constexpr int F3_SPLIT_AUTO_N = 4096;
+
+// Cuts a planned single-pair job in two PairDesc entries sharing one score slot when its launch is the
+// staged flow3 linear-gap kernel with rotating loops (the conditions enqueue derives use_f3 from, less
+// ring mode, streamed rows, slabs, batches, the pool loops and traced launches).  Items stay in claim
+// order, the left half's groups first: every group waits on a lower item only, whatever the grid.
+bool plan_split(Job& job, const Params& prm) {
+    const long long o = g_opt_f3split.load();
+    if (o == 0 || job.pairs.size() != 1 || job.mode != MODE_FLOW2 || !job.dna || !job.f2w2 || job.f2w3 || job.pwg ||
+        job.f3pwg || job.ring || job.f2_stream || job.slab || (job.C != 32 && job.C != 16))
+        return false;
+    if (g_opt_f3.load() == 0 || g_opt_f3pool.load() != 0 || g_opt_trace.load() != 0 || g_opt_linear.load() == 0 ||
+        prm.gap_init != prm.gap_ext)
+        return false;
+    const PairDesc whole = job.pairs[0];
+    int c = 0, lead = 0;
+    if (!flow3_fits(whole.m, job.C) || !split_cols(whole.n, &c, &lead)) return false;
+    if (o < 0 && whole.n < F3_SPLIT_AUTO_N) return false;
+    PairDesc left = whole, right = whole;
+    left.n = c;
+    left.strips = c / 126;
+    left.flags = PAIR_HALF;
+    right.col_off = whole.col_off + (uint64_t)c;
+    right.n = whole.n - c;
+    right.strips = (right.n + lead) / 126;
+    right.flags = PAIR_HALF | PAIR_REV;
+    right.lead = lead;
+    // a granule edge behind every group, the last one's for the combine kernel
+    left.bnd_off = 0;
+    right.bnd_off = (uint64_t)((left.strips + 3) / 4) * (uint64_t)whole.m;
+    job.bnd_granules = right.bnd_off + (uint64_t)((right.strips + 3) / 4) * (uint64_t)whole.m;
+    job.pairs = {left, right};
+    job.item_base = {0, (left.strips + 3) / 4, (left.strips + 3) / 4 + (right.strips + 3) / 4};
+    return true;
+}
+
 int finalize_mode(Job& job, const Params& prm, int cus);
 
 // finalize_mode, and for a seven-letter job (planned as DNA) the check that it lands on the staged flow3
@@ -798,6 +849,8 @@ int enqueue(Ctx* c, Job& job, const Params& prm, const unsigned char* d_seq, int
         return -1;
     }
     const bool duo = job.mode == MODE_DUO;
+    // one long pair on the staged flow3 linear-gap kernel: two half pairs from here on (plan_split)
+    const bool cut = edge == nullptr && plan_split(job, prm);
     const size_t np = duo ? job.duos.size() : job.pairs.size();
     // staging buffers may still be read by the previous call's async copies
     if (c->staged_pending) {
@@ -1030,6 +1083,10 @@ int enqueue(Ctx* c, Job& job, const Params& prm, const unsigned char* d_seq, int
     }
     cfg.duo_wrap = duo_wrap;
     cfg.duo_tab = duo_tab;
+    if (cut && !(cfg.f3 && !cfg.f3p && !cfg.f3a && !f2s && !job.ring)) {
+        set_err("internal: a pair was cut at a column for a launch that is not flow3's staged linear-gap kernel");
+        return -1;
+    }
     if (cfg.f2_w2 && job.C == 16 && !use_f3) {
         set_err("flow2: two columns per lane at C = 16 runs on flow3 only (rows staged in LDS, one GPU)");
         return -1;
@@ -1157,6 +1214,13 @@ int enqueue(Ctx* c, Job& job, const Params& prm, const unsigned char* d_seq, int
     if (time_kernel) HIPCHK(hipEventRecord(c->ev0, s));
     HIPCHK(cfg.f3 || cfg.f3a || cfg.f3ra ? launch_sw_flow3(cfg, kp, s)
            : job.mode == MODE_FLOW2 ? launch_sw_flow2(cfg, kp, s) : launch_sw_strip(cfg, kp, s));
+    if (cut) {   // the crossing term from the halves' final edges (inside the timed span)
+        const PairDesc& l = job.pairs[0];
+        const PairDesc& r = job.pairs[1];
+        const Granule* gl = c->bnd.p + l.bnd_off + (uint64_t)((l.strips + 3) / 4 - 1) * (uint64_t)l.m;
+        const Granule* gr = c->bnd.p + r.bnd_off + (uint64_t)((r.strips + 3) / 4 - 1) * (uint64_t)r.m;
+        HIPCHK(launch_sw_flow3_combine(gl, gr, l.m, prm.gap_init, kp.epoch, c->ctrl.p, d_scores + l.out_idx, s));
+    }
     if (time_kernel) HIPCHK(hipEventRecord(c->ev1, s));
 
     t_stats = sw_stats{};
@@ -1172,7 +1236,7 @@ int enqueue(Ctx* c, Job& job, const Params& prm, const unsigned char* d_seq, int
                       (cfg.f2_w2 ? 16 : 0) | (cfg.f2_pwg ? 32 : 0) | (cfg.f3 ? 64 : 0) | (cfg.duo_wrap > 0 ? 128 : 0) |
                       (cfg.duo_tab > 0 ? 256 : 0) | (cfg.f3_hl ? 512 : 0) | (cfg.f3a || cfg.f3ra ? 1024 : 0) |
                       (cfg.f3_slab ? 2048 : 0) | (cfg.f3p ? 4096 : 0) | (cfg.f3_w3 ? 8192 : 0) |
-                      (cfg.f3_w45 ? 16384 : 0) | (cfg.f3_pwg ? 32768 : 0) | (cfg.hep ? 65536 : 0);
+                      (cfg.f3_w45 ? 16384 : 0) | (cfg.f3_pwg ? 32768 : 0) | (cfg.hep ? 65536 : 0) | (cut ? 1 << 17 : 0);
     t_stats.boundary_bytes = (long long)(job.bnd_granules * sizeof(Granule));
     c->last = s;
     return 0;
@@ -1183,8 +1247,11 @@ int check_ctrl(Ctx* c, hipStream_t s) {
     HIPCHK(hipMemcpyAsync(c->hctrl.p, c->ctrl.p, sizeof(Ctrl), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     if (c->hctrl.p->error) {
-        set_err("strip hand-off timed out (error %u, strip %u): a producer strip never published", c->hctrl.p->error,
-                c->hctrl.p->err_item);
+        if (c->hctrl.p->error == ERR_EDGE)
+            set_err("a cut pair's final edge held a row that this launch never wrote (error %u)", c->hctrl.p->error);
+        else
+            set_err("strip hand-off timed out (error %u, strip %u): a producer strip never published",
+                    c->hctrl.p->error, c->hctrl.p->err_item);
         HIPCHK(hipMemsetAsync(c->ctrl.p, 0, sizeof(Ctrl), s));
         HIPCHK(hipStreamSynchronize(s));
         return -1;
@@ -1842,6 +1909,18 @@ int sw_slab_bounds(long long n, int m, int nslabs, int flags, long long* bounds)
     return q;
 }
 
+int sw_split_bounds(int n, int* cut, int* lead) {
+    if (n <= 0 || !cut || !lead) {
+        set_err("sw_split_bounds: invalid arguments");
+        return -1;
+    }
+    int c = 0, l = 0;
+    if (!split_cols(n, &c, &l)) return 0;
+    *cut = c;
+    *lead = l;
+    return c / 126 + (n - c + l) / 126;
+}
+
 int sw_score_slab_device(const unsigned char* d_arena, int64_t col_off, int n, int64_t row_off, int m,
                          void* d_inflow, void* d_outflow, unsigned epoch, int* d_score, int flags, void* stream) {
     const auto t0 = std::chrono::steady_clock::now();
@@ -2001,6 +2080,10 @@ int sw_set_option(const char* key, long long v) {
     } else if (k == "duo_raw") {   // 1 (default): byte batches on the duo kernels (RAW penalty), 0: byte strip kernels
         if (v < 0 || v > 1) return -1;
         g_opt_duo_raw = v;
+    } else if (k == "f3split") {   // one pair on flow3's staged linear-gap kernel cut at a column and scored from both
+        // ends: -1 auto (pairs of F3_SPLIT_AUTO_N columns or more), 0 off, 1 whenever each half gets two strips
+        if (v < -1 || v > 1) return -1;
+        g_opt_f3split = v;
     } else if (k == "stall_item") {   // tests only: flow2's compute waves skip this item (-1 = none)
         if (v < -1) return -1;
         g_opt_stall_item = v;
@@ -2094,6 +2177,7 @@ long long sw_get_option(const char* key) {
     if (k == "f3pwg") return g_opt_f3pwg;
     if (k == "duo_raw") return g_opt_duo_raw;
     if (k == "hep") return g_opt_hep;
+    if (k == "f3split") return g_opt_f3split;
     if (k == "blocks") return g_opt_blocks;
     if (k == "orient") return g_opt_orient;
     if (k == "trace") return g_opt_trace;

@@ -17,7 +17,14 @@ struct PairDesc {
     int m;              // rows    (> 0)
     int strips;         // ceil(n / (64*W))
     int out_idx;        // slot in the score array
+    // One half of a pair cut at a column (sw_engine.hip plan_split; flow3's staged linear-gap
+    // kernel only, 0 elsewhere).  PAIR_HALF: the last strip publishes its outflow as granules
+    // into edge (strips + 3) / 4 - 1 for the combine kernel.  PAIR_REV: columns and rows are
+    // read mirrored (column j is byte col_off + n - 1 - j, row r byte row_off + m - 1 - r).
+    int flags;
+    int lead;           // dead columns in front of column 0 (strip s, lane l: column 126 s + 2 l - lead)
 };
+enum : int { PAIR_HALF = 1, PAIR_REV = 2 };
 
 // Two pairs scored in lock step by the packed-u16 "duo" kernel: lane values
 // hold pair 0 in the low and pair 1 in the high 16 bits.  Both are padded to
@@ -40,7 +47,7 @@ struct Ctrl {
     unsigned int pad;
 };
 
-enum : unsigned { ERR_TIMEOUT = 1u };
+enum : unsigned { ERR_TIMEOUT = 1u, ERR_EDGE = 2u };   // EDGE: a cut pair's final edge held an unwritten row
 
 // A strip boundary hand-off granule: written ONCE per launch with a single
 // 16-byte write-through (sc1) store by the producer wave, read with sc1 loads
@@ -229,6 +236,10 @@ hipError_t launch_sw_flow2(const LaunchCfg& cfg, const KParams& kp, hipStream_t 
 // flow3 (sw_flow3.hip): flow2's staged W2 linear-gap kernel with hand-scheduled chunk loops
 hipError_t launch_sw_flow3(const LaunchCfg& cfg, const KParams& kp, hipStream_t stream);
 bool flow3_fits(int max_m, int C, bool aff = false);
+// the crossing term of a pair cut at a column (sw_flow3.hip): max over rows r of gl[r] + gr[m - 2 - r] + 2 G
+// from the two halves' final edges (8-B granules keyed with the launch epoch), atomicMax into *score
+hipError_t launch_sw_flow3_combine(const Granule* gl, const Granule* gr, int m, int gap, unsigned epoch, Ctrl* ctrl,
+                                   int* score, hipStream_t stream);
 // workgroups per CU resident for a flow3 ring-mode launch (its LDS pad of cfg.f2_wgs), -1 on error
 int flow3_ring_resident(const LaunchCfg& cfg);
 int flow2_waves_per_cu(int C);

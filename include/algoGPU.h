@@ -136,6 +136,12 @@ int sw_stream_status(void* stream);
  * sw_ipc_open / sw_ipc_close: map / unmap another process's buffer. */
 #define SW_IPC_HANDLE_BYTES 64
 int sw_slab_bounds(long long n, int m, int nslabs, int flags, long long* bounds);
+/* sw_split_bounds: where option "f3split" cuts one pair of n columns that runs the staged two-column
+ *   linear-gap kernel: the left half is columns [0, *cut), the right half columns [*cut, n) read
+ *   mirrored behind *lead dead columns; *cut and n - *cut + *lead are multiples of 126.  Returns the
+ *   strips of both halves together, 0 when n is too narrow for two strips each (n < 379; outputs
+ *   untouched), -1 on bad arguments.  Needs no device. */
+int sw_split_bounds(int n, int* cut, int* lead);
 int sw_score_slab_device(const unsigned char* d_arena, int64_t col_off, int n, int64_t row_off, int m,
                          void* d_inflow, void* d_outflow, unsigned epoch, int* d_score, int flags, void* stream);
 int sw_slab_alloc(int m, void** d_buf, void* ipc_handle);
@@ -354,6 +360,11 @@ void sw_last_align_ms(float* fill_ms, float* walk_ms);
  *              0 = (default) whole-chunk links (measured faster on C5)
  *   "f3a"      1 = (default) the general affine step runs on flow3 (staged: sw_flow3a_kernel, one
  *              column per lane, C2 with G_INIT != G_EXT; ring: sw_flow3ra(3)_kernel, C5), 0 = flow2
+ *   "f3split"  one pair on the staged two-column linear-gap flow3 kernel (C2) cut at a column and scored
+ *              from both ends at once, the right half on both sequences mirrored, joined by a small
+ *              combine kernel (sw_split_bounds): -1 = (default) automatic, for pairs at least the
+ *              measured threshold wide; 0 = never; 1 = whenever each half gets two strips (n >= 379).
+ *              Traced launches (option trace), ring mode, slabs, batches and the affine step run uncut
  *   "f3pwg"    1 = (default) DNA batches on a pair-per-workgroup plan (scores that need int32, or 1-2
  *              pairs per CU) run flow3's three-column ring step (sw_flow3r3p / ra3p_kernel), 0 = flow2's
  *   "f3slab"   1 = (default) column slabs run flow3's ring kernel with slab roles
@@ -408,7 +419,9 @@ typedef struct {
                                bit 15: flow3 three-column ring step with a pair per workgroup
                                        (sw_flow3r3p_kernel / sw_flow3ra3p_kernel: int32 batches);
                                bit 16: a pair over up to seven byte values on flow3's staged kernels
-                                       (option hep; dna = 2 then) */
+                                       (option hep; dna = 2 then);
+                               bit 17: one pair cut at a column, both halves in one launch (option f3split;
+                                       items and blocks count both halves) */
 } sw_stats;
 int sw_last_stats(sw_stats* out);
 

@@ -9,7 +9,8 @@ rooflines) whose roofline names a profiles/pmc_*.json and carries its sha256
     achieved = valu_insts_per_launch * 64 / kernel time, frac = achieved / peak
 from that file and the line's own kernel time, and require the line's values to
 match to 3 significant digits.  A line whose profile file has changed since (another
-sha256) is reported STALE; a line of this round (the default set) must be neither
+sha256) is checked against the archived copy of the profile it cites, profiles/rNN_pmc_*.json
+with that sha256, when one is committed, and is reported STALE otherwise; a line of this round (the default set) must be neither
 stale nor carry frac: null.  Exit status 1 on any failure."""
 import glob
 import hashlib
@@ -65,6 +66,13 @@ def check(path, strict):
                 bad.append("%s %s: %s missing" % (path, label, src))
                 continue
             sha = hashlib.sha256(open(pmc, "rb").read()).hexdigest()
+            if rf.get("pmc_sha256") != sha:
+                # the profile was re-taken for a later build: the line is checked against the archived
+                # copy of the profile it cites (profiles/rNN_pmc_*.json, byte for byte: the same sha256)
+                for old in sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9]*_" + os.path.basename(src)))):
+                    if hashlib.sha256(open(old, "rb").read()).hexdigest() == rf.get("pmc_sha256"):
+                        pmc, sha, src = old, rf["pmc_sha256"], os.path.relpath(old, ROOT)
+                        break
             if rf.get("pmc_sha256") != sha:
                 if strict:
                     bad.append("%s %s: STALE (%s changed since the line was taken)" % (path, label, src))
