@@ -296,8 +296,11 @@ bool duo_raw_ok(const Params& p) {
     return g_opt_duo_raw.load() != 0 && p.mismatch < 0 && p.match - p.mismatch <= 127;
 }
 
-// Packed-u16 duo mode: exact when every H + MATCH fits 16 bits (H <= MATCH*min(n,m)).
+// Packed-u16 duo mode: exact when every H + MATCH fits 16 bits (H <= MATCH*min(n,m)).  MATCH < 0 is
+// out: A = H + MATCH lives in an unsigned half, and the border's 0 + MATCH would read as 65535 (a NaN
+// on the f16 max3 variant); such constants (every score 0) run the int32 kernels.
 bool duo_fits(const Job& job, const Params& p) {
+    if (p.match < 0) return false;
     if ((!job.dna && !duo_raw_ok(p)) || p.gap_init + p.match > 65535 || p.gap_ext > 65535 || p.match - p.mismatch > 254)
         return false;
     for (auto& d : job.pairs)
@@ -403,11 +406,13 @@ bool plan_w45(Job& job, int slots) {
         // W5 strips after s4 W4 strips: the last one's columns reach n - 1
         s5 = (int)std::max(1LL, (n - 320 - 252LL * s4 + 314) / 315 + 1);
     } else {
-        // four columns cover it: the fewest W4 strips (no W5 strip, so s4 may be any count)
+        // four columns cover it: the fewest W4 strips (no W5 strip, so the count may be anything)
         s4 = (int)std::max(1LL, (n - 256 + 251) / 252 + 1);
     }
     d.strips = s4 + s5;
-    job.w45_s4 = s5 > 0 ? s4 : d.strips;
+    // the kernel takes a split index that is a multiple of 4 (a group's strips share a width): with W4
+    // strips only, the next multiple of 4 at or above their count, so every strip stays below it
+    job.w45_s4 = s5 > 0 ? s4 : (d.strips + 3) / 4 * 4;
     job.item_base[1] = job.item_base[0] + (d.strips + 3) / 4;
     return true;
 }
@@ -742,7 +747,7 @@ int finalize_mode(Job& job, const Params& prm, int cus) {
             return 0;
         }
         if (forced_duo) {
-            set_err("duo mode needs a batch whose scores fit 16 bits (MATCH*min(n,m)+MATCH <= 65535) and, for bytes "
+            set_err("duo mode needs MATCH >= 0, a batch whose scores fit 16 bits (MATCH*min(n,m)+MATCH <= 65535) and, for bytes "
                     "outside {A,C,G,T}, MISMATCH < 0 and MATCH - MISMATCH <= 127");
             return -1;
         }

@@ -640,7 +640,8 @@ __global__ void __launch_bounds__(256) sw_flow_kernel(KParams kp) {
 // high half, so each v_pk_* instruction updates two cells.  Saturating
 // (clamped) arithmetic throughout, exact for the same reasons as the int32
 // path (Arithmetic), with
-//   A  = H + MATCH            exact (the host guarantees MATCH*min(n,m)+MATCH <= 65535)
+//   A  = H + MATCH            exact (the host guarantees MATCH >= 0 and MATCH*min(n,m)+MATCH <= 65535:
+//                             a negative MATCH would make the border's A = 0 + MATCH read as 65535)
 //   Hg = max(H - G_INIT, 0),  Eh = max(E - G_EXT, 0),  Fh = max(F - G_EXT, 0)
 //   t  = max(A_diag - pen, 0) with pen = MATCH - s(q, d) from one v_perm_b32
 //        over both pairs' 4-byte column profiles (selector 13 -> 0xFF: dead

@@ -54,7 +54,9 @@ int SmithDiagonalGPU(unsigned char* seq1, unsigned char* seq2, int n, int m);
 
 /* Scoring constants for later calls from ANY thread (process-wide).
  * Supported: 0 <= gap_init, gap_ext <= 1<<20; -127 <= mismatch <= 0;
- * mismatch <= match <= 127.  Returns 0, or -1 if unsupported. */
+ * mismatch <= match <= 127.  match <= 0 is supported: every score is then 0
+ * (match < 0 never runs the packed 16-bit duos, whose H + match is unsigned).
+ * Returns 0, or -1 if unsupported. */
 int sw_set_params(int match, int mismatch, int gap_init, int gap_ext);
 void sw_get_params(int* match, int* mismatch, int* gap_init, int* gap_ext);
 
@@ -321,7 +323,7 @@ void sw_last_align_ms(float* fill_ms, float* walk_ms);
  *   "orient"   0 = auto, 1 = seq1 spread across lanes, 2 = seq2 across lanes
  *   "mode"     -1 = auto, 0 = independent strip waves, 1 = workgroup per pair,
  *              2 = lock-step strip groups (single long pairs),
- *              3 = packed 16-bit pair duos (batches with scores < 65535: DNA, and any bytes
+ *              3 = packed 16-bit pair duos (MATCH >= 0, batches with scores < 65535: DNA, and any bytes
  *                  when MISMATCH < 0 and MATCH - MISMATCH <= 127, option duo_raw),
  *              4 = free-running strip groups, rows staged in LDS (long DNA pairs),
  *              5 = the flow2 / flow3 wavefront step (DNA, one column per lane or more, chunked

@@ -46,15 +46,36 @@ REFVAR_PARAMS = (Params(2, -3, 5, 2), Params(1, -1, 3, 1))
 _lib = None
 
 
+def corner_params() -> tuple:
+    """The constant sets of tests/golden/params_corners.json (the corners of the scoring domain)."""
+    import json
+    path = os.path.join(HERE, "..", "tests", "golden", "params_corners.json")
+    if not os.path.exists(path):
+        return ()
+    with open(path) as f:
+        return tuple(Params(*s["params"]) for s in json.load(f)["sets"])
+
+
+def build_refvar(prm: Params) -> bool:
+    """The reference's main.cpp + lazySmith.cpp built with `prm` into oracle/_ref (oracle/Makefile
+    refvar; up to date: nothing runs).  False where the reference sources are absent."""
+    if not os.path.isdir("/root/reference"):
+        return False
+    if prm != DEFAULT:   # the defaults are the plain `ref` build
+        subprocess.run(["make", "-s", "-C", HERE, "refvar", "MA=%d" % prm.match, "MI=%d" % prm.mismatch,
+                        "GI=%d" % prm.gap_init, "GE=%d" % prm.gap_ext], check=True, stderr=subprocess.DEVNULL)
+    return True
+
+
 def build() -> None:
     """Compile the C restatement (and, when /root/reference exists, oracle/_ref)."""
     subprocess.run(["make", "-s", "-C", HERE, "all"], check=True)
     if os.path.isdir("/root/reference"):
         subprocess.run(["make", "-s", "-C", HERE, "ref"], check=True)
-        # param-substituted reference builds (G_INIT != G_EXT), for the long-pair pins
-        for prm in REFVAR_PARAMS:
-            subprocess.run(["make", "-s", "-C", HERE, "refvar", "MA=%d" % prm.match, "MI=%d" % prm.mismatch,
-                            "GI=%d" % prm.gap_init, "GE=%d" % prm.gap_ext], check=True)
+        # param-substituted reference builds: G_INIT != G_EXT for the long-pair pins, and the corners
+        # of the scoring domain (tests/test_corners_cpu.py)
+        for prm in REFVAR_PARAMS + tuple(p for p in corner_params() if p not in REFVAR_PARAMS):
+            build_refvar(prm)
         # the reference harness linked against the MI355X library (needs it built)
         if os.path.exists(os.path.join(HERE, "..", "concurrentproject_amd", "libswmi355.so")):
             subprocess.run(["make", "-s", "-C", HERE, "harness"], check=True)

@@ -43,7 +43,8 @@ def _plan(n, blocks):
 
 def test_w45_ring_parity(engine, oracle_mod):
     """f2w = 4 forced with small grids: pairs cut into W4 strips only, W5 strips only and both (the
-    W4 -> W5 hand-off), a grid too small for five columns (three then), rows around the 64-row
+    W4 -> W5 hand-off), W4 strips whose count is no multiple of 4 (6 and 10: the split index the kernel takes
+    is rounded up to one), a grid too small for five columns (three then), rows around the 64-row
     chunks and 512-row rings; similar pairs put long diagonals through every strip edge."""
     rng = np.random.default_rng(45)
     engine.set_option("orient", 1)
@@ -51,10 +52,10 @@ def test_w45_ring_parity(engine, oracle_mod):
     engine.set_option("ring", 1)
     engine.set_option("f2w", 4)
     op = oracle_mod.Params(1, -1, 1, 1)
-    seen = set()
+    seen, odd = set(), 0
     for n, m, blocks, rows in ((1100, 700, 1, 512), (2000, 1000, 2, 512), (2100, 2049, 2, 512), (2300, 600, 2, 4096),
                                (3500, 1500, 3, 512), (3500, 3001, 2, 1024), (5000, 2000, 4, 512), (6000, 129, 5, 512),
-                               (4100, 640, 4, 512)):
+                               (4100, 640, 4, 512), (1500, 700, 2, 512), (2400, 600, 3, 512)):
         a = _rand_dna(rng, n)
         b = _similar(rng, a, m) if rng.random() < 0.6 else _rand_dna(rng, m)
         engine.set_option("blocks", blocks)
@@ -70,9 +71,11 @@ def test_w45_ring_parity(engine, oracle_mod):
             assert st["variant"] & 16384 and st["variant"] & 4 and not st["variant"] & 8192, (n, blocks, st)
             assert st["items"] == (s4 + s5 + 3) // 4, (n, blocks, plan, st)
             seen.add(("w4" if s4 else "") + ("w5" if s5 else ""))
+            odd += s5 == 0 and s4 % 4 == 2
         assert got == exp, (n, m, blocks, rows, plan, got, exp)
     # W4 alone, W5 alone and the mixed cut were all exercised
     assert seen == {"w4", "w5", "w4w5"}, seen
+    assert odd == 2
 
 
 def test_w45_matches_w3(engine):
