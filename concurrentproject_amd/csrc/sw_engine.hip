@@ -62,11 +62,110 @@ struct Params {
 std::mutex g_param_mu;
 Params g_params;
 
-std::atomic<long long> g_opt_W{0}, g_opt_C{0}, g_opt_bytes{0}, g_opt_timeout{30}, g_opt_blocks{0}, g_opt_orient{0},
-    g_opt_mode{-1}, g_opt_trace{0}, g_opt_duo_f16{1}, g_opt_f2stream{0}, g_opt_ring{-1}, g_opt_ring_rows{4096}, g_opt_f2_wgs{0}, g_opt_f2w{0}, g_opt_f2pwg{-1},
-    g_opt_linear{-1}, g_opt_f3{1}, g_opt_slab_plain{0}, g_opt_duo_lds{1}, g_opt_duo_tab{1}, g_opt_duo_roles{1}, g_opt_f3hl{1},
-    g_opt_f3rhl{0}, g_opt_f3a{1}, g_opt_f3slab{1}, g_opt_duo_prio{-1}, g_opt_f3pool{0},
-    g_opt_stall_item{-1}, g_opt_f3pwg{1}, g_opt_duo_raw{1}, g_opt_hep{1}, g_opt_trace_mb{1024}, g_opt_f3split{-1};
+// ---- options (include/algoGPU.h "Tuning knobs") -----------------------------
+// Every process-wide option once: X(key, default, lowest, highest, further test or nullptr, stored as 0 / 1).
+// sw_set_option takes v in [lowest, highest] that passes the test; ANY: every value.
+constexpr long long ANY_LO = INT64_MIN, ANY_HI = INT64_MAX;
+bool opt_W_ok(long long v) { return v == 0 || v == 1 || v == 2 || v == 4 || v == 8; }
+bool opt_C_ok(long long v) { return v == 0 || v == 16 || v == 32 || v == 64; }
+bool opt_prio_ok(long long v) { return v <= 0 || v >= 6; }
+bool opt_pow2_ok(long long v) { return (v & (v - 1)) == 0; }
+#define SW_OPTIONS(X)                                                                                                 \
+    X(W, 0, 0, 8, opt_W_ok, false)                                                                                    \
+    X(C, 0, 0, 64, opt_C_ok, false)                                                                                   \
+    X(bytes, 0, ANY_LO, ANY_HI, nullptr, true)                                                                        \
+    X(timeout, 30, 1, 3600, nullptr, false)                                                                           \
+    X(blocks, 0, 0, ANY_HI, nullptr, false)                                                                           \
+    X(orient, 0, 0, 2, nullptr, false)                                                                                \
+    X(mode, -1, -1, 5, nullptr, false)                                                                                \
+    /* device buffer of 4 u64 per strip (tools only), 0 = off */                                                      \
+    X(trace, 0, ANY_LO, ANY_HI, nullptr, false)                                                                       \
+    /* MiB of trace memory a traced matrix launch may hold (sw_matrix.hip) */                                         \
+    X(trace_mb, 1024, 1, 3072, nullptr, false)                                                                        \
+    /* 1 = duo max3 through v_pk_maximum3_f16 when exact, 0 = u16 max only */                                         \
+    X(duo16, 1, ANY_LO, ANY_HI, nullptr, true)                                                                        \
+    /* 1 = flow2 streams row codes even when they fit in LDS (tests) */                                               \
+    X(f2stream, 0, ANY_LO, ANY_HI, nullptr, true)                                                                     \
+    /* flow2 one-pair group edges: -1 auto (rings above 1 GB of edges), 0 off, 1 on */                                \
+    X(ring, -1, -1, 1, nullptr, false)                                                                                \
+    /* rows per within-round ring: a power of two in [512, 2^20] */                                                   \
+    X(ring_rows, 4096, 512, 1 << 20, opt_pow2_ok, false)                                                              \
+    /* flow2 streamed kernel: workgroups per CU, 0 = auto, 1..F2_WGS_MAX */                                           \
+    X(f2_wgs, 0, 0, F2_WGS_MAX, nullptr, false)                                                                       \
+    /* flow2 columns per lane: 0 auto, 1, 2 (2: the linear-gap step only), 3 (flow3 ring mode: single long pairs    \
+       and column slabs; auto there), 4 (four / five in that ring mode, one pair, every group in one round) */        \
+    X(f2w, 0, 0, 4, nullptr, false)                                                                                   \
+    /* int32 DNA batches on flow2, a pair per workgroup: -1 auto, 0 off, 1 forced */                                  \
+    X(f2pwg, -1, -1, 1, nullptr, false)                                                                               \
+    /* G_INIT == G_EXT: -1 auto (the linear-gap step), 0 = the affine step */                                         \
+    X(linear, -1, -1, 0, nullptr, false)                                                                              \
+    /* 1: staged W2 linear-gap launches on flow3 (sw_flow3.hip), 0: flow2 */                                          \
+    X(f3, 1, 0, 1, nullptr, false)                                                                                    \
+    /* 1: staged affine-step launches on flow3 (sw_flow3a_kernel), 0: flow2 */                                        \
+    X(f3a, 1, 0, 1, nullptr, false)                                                                                   \
+    /* 1: flow3 staged launches at C = 32 with half-chunk in-workgroup links (auto C: 32) */                          \
+    X(f3hl, 1, 0, 1, nullptr, false)                                                                                  \
+    /* 1: flow3 ring launches at C = 64 with half-chunk in-workgroup links */                                         \
+    X(f3rhl, 0, 0, 1, nullptr, false)                                                                                 \
+    /* 1: column slabs on flow3's ring kernel (sw_flow3rs_kernel), 0: flow2 */                                        \
+    X(f3slab, 1, 0, 1, nullptr, false)                                                                                \
+    /* 1: flow3 staged C = 32 half-chunk launches on the pool loops (slower) */                            \
+    X(f3pool, 0, 0, 1, nullptr, false)                                                                                \
+    /* 1: int32 batches on flow3's three-column ring step, a pair per workgroup (sw_flow3r3p / ra3p_kernel);         \
+       0: flow2's pair-per-workgroup kernel */                                                                        \
+    X(f3pwg, 1, ANY_LO, ANY_HI, nullptr, true)                                                                        \
+    /* one pair on flow3's staged linear-gap kernel cut at a column and scored from both ends: -1 auto (pairs of     \
+       F3_SPLIT_AUTO_N columns or more), 0 off, 1 whenever each half gets two strips */                               \
+    X(f3split, -1, -1, 1, nullptr, false)                                                                             \
+    /* 1: one pair over up to seven byte values on flow3's seven-letter kernels, 0: byte path */                      \
+    X(hep, 1, 0, 1, nullptr, false)                                                                                   \
+    /* 1: duo strip hand-offs in LDS when the wrap buffer fits, 0: HBM granules */                                    \
+    X(duo_lds, 1, 0, 1, nullptr, false)                                                                               \
+    /* duo LDS kernel row codes from an LDS table: 1 for one-pass batches, 2 whenever it fits, 0 carried by DPP */    \
+    X(duo_tab, 1, 0, 2, nullptr, false)                                                                               \
+    /* 1: duo strip roles complementary per SIMD across a CU's workgroups */                                          \
+    X(duo_roles, 1, 0, 1, nullptr, false)                                                                             \
+    /* 1: byte batches on the duo kernels (RAW penalty), 0: byte strip kernels */                                     \
+    X(duo_raw, 1, 0, 1, nullptr, false)                                                                               \
+    /* duo LDS kernel: -1 auto, 0 off, k in 6..20: a CU's workgroups alternate priority every 2^k ticks (10 ns) */    \
+    X(duo_prio, -1, -1, 20, opt_prio_ok, false)                                                                       \
+    /* 1: exported slab buffers may fall back to plain device memory */                                               \
+    X(slab_plain, 0, 0, 1, nullptr, false)                                                                            \
+    /* tests only: flow2's compute waves skip this item (-1 = none) */                                                \
+    X(stall_item, -1, -1, ANY_HI, nullptr, false)
+
+#define X(key, def, lo, hi, ok, flag) O_##key,
+enum Opt : int { SW_OPTIONS(X) OPT_COUNT };
+#undef X
+struct OptRow {
+    const char* key;
+    long long def, lo, hi;
+    bool (*ok)(long long);
+    bool flag;
+};
+#define X(key, def, lo, hi, ok, flag) {#key, def, lo, hi, ok, flag},
+constexpr OptRow OPT_ROWS[OPT_COUNT] = {SW_OPTIONS(X)};
+#undef X
+#define X(key, def, lo, hi, ok, flag) {def},
+std::atomic<long long> g_opt[OPT_COUNT] = {SW_OPTIONS(X)};
+#undef X
+
+// The options as one call sees them: every entry point that plans or launches takes one snapshot and
+// hands it down, so a sw_set_option from another thread never splits a launch between two values.
+struct Opts {
+    long long v[OPT_COUNT];
+    long long operator[](Opt o) const { return v[o]; }
+};
+Opts snapshot_opts() {
+    Opts o;
+    for (int i = 0; i < OPT_COUNT; ++i) o.v[i] = g_opt[i].load();
+    return o;
+}
+int find_opt(const char* key) {
+    for (int i = 0; i < OPT_COUNT; ++i)
+        if (std::strcmp(key, OPT_ROWS[i].key) == 0) return i;
+    return -1;
+}
 
 // Longest sequence the engine takes: granule buffers of m rows keep m * 16 in the
 // 32-bit record count of a buffer resource (sw_device.h linear_edge).
@@ -75,8 +174,8 @@ constexpr long long MAX_SEQ = (1LL << 27) - 1;
 constexpr long long RING_AUTO_BYTES = 1LL << 30;
 
 // orientation: 0 = engine policy, 1 = seq1 across lanes (columns), 2 = seq2 across lanes
-bool want_swap(bool single, long long len1, long long len2) {
-    const long long o = g_opt_orient.load();
+bool want_swap(const Opts& opt, bool single, long long len1, long long len2) {
+    const long long o = opt[O_orient];
     if (o == 1) return false;
     if (o == 2) return true;
     return single ? (len2 > len1) : (len1 > len2);
@@ -221,8 +320,17 @@ bool all_dna(const unsigned char* s, int len) {
     return true;
 }
 
-int pick_W(const std::vector<PairDesc>& pairs, bool single) {
-    long long forced = g_opt_W.load();
+int max_rows(const Job& job) {
+    int m = 0;
+    for (const PairDesc& d : job.pairs) m = std::max(m, d.m);
+    return m;
+}
+
+// G_INIT == G_EXT: the exact linear-gap step (sw_flow2.hip LIN), unless option linear = 0
+bool linear_gap(const Params& p, const Opts& opt) { return p.gap_init == p.gap_ext && opt[O_linear] != 0; }
+
+int pick_W(const Opts& opt, const std::vector<PairDesc>& pairs, bool single) {
+    long long forced = opt[O_W];
     if (forced) return (int)forced;
     if (single) {
         // single pair: enough strips to put ~1-2 waves on every SIMD while
@@ -246,16 +354,16 @@ int pick_W(const std::vector<PairDesc>& pairs, bool single) {
     return 1;
 }
 
-int pick_C(int W) {
-    long long forced = g_opt_C.load();
+int pick_C(const Opts& opt, int W) {
+    long long forced = opt[O_C];
     if (forced) return (int)forced;
     return W <= 2 ? 32 : 64;   // measured: C=32 beats 16 at W=1 (per-chunk overhead vs lag)
 }
 
 // Build descriptors for `np` pairs given their (col, row) lengths and arena
 // offsets.  `single` selects the single-pair orientation policy.
-int pick_mode(const std::vector<PairDesc>& pairs, bool single) {
-    const long long forced = g_opt_mode.load();
+int pick_mode(const Opts& opt, const std::vector<PairDesc>& pairs, bool single) {
+    const long long forced = opt[O_mode];
     if (forced >= 0) return (int)forced;
     if (single) return pairs[0].strips >= 2 ? MODE_CHAIN : MODE_STRIP;
     std::vector<int> st;
@@ -265,11 +373,11 @@ int pick_mode(const std::vector<PairDesc>& pairs, bool single) {
     return st[st.size() / 2] >= 4 ? MODE_PAIRWG : MODE_STRIP;
 }
 
-void plan(Job& job, int W, int C, bool single, int mode = -1) {
+void plan(const Opts& opt, Job& job, int W, int C, bool single, int mode = -1) {
     job.W = W;
     job.C = C;
     for (auto& d : job.pairs) d.strips = (d.n + 64 * W - 1) / (64 * W);
-    job.mode = mode >= 0 ? mode : pick_mode(job.pairs, single);
+    job.mode = mode >= 0 ? mode : pick_mode(opt, job.pairs, single);
     job.item_base.assign(job.pairs.size() + 1, 0);
     uint64_t g = 0;
     long long cells = 0;
@@ -292,16 +400,16 @@ void plan(Job& job, int W, int C, bool single, int mode = -1) {
 // SENT_RAW): its sentinel encoding needs MATCH - MISMATCH <= 127 and MISMATCH < 0 (dead and sentinel
 // cells then score as mismatches, below the true maximum).  Option duo_raw = 0 keeps such batches on
 // the byte-path strip kernels.
-bool duo_raw_ok(const Params& p) {
-    return g_opt_duo_raw.load() != 0 && p.mismatch < 0 && p.match - p.mismatch <= 127;
+bool duo_raw_ok(const Params& p, const Opts& opt) {
+    return opt[O_duo_raw] != 0 && p.mismatch < 0 && p.match - p.mismatch <= 127;
 }
 
 // Packed-u16 duo mode: exact when every H + MATCH fits 16 bits (H <= MATCH*min(n,m)).  MATCH < 0 is
 // out: A = H + MATCH lives in an unsigned half, and the border's 0 + MATCH would read as 65535 (a NaN
 // on the f16 max3 variant); such constants (every score 0) run the int32 kernels.
-bool duo_fits(const Job& job, const Params& p) {
+bool duo_fits(const Job& job, const Params& p, const Opts& opt) {
     if (p.match < 0) return false;
-    if ((!job.dna && !duo_raw_ok(p)) || p.gap_init + p.match > 65535 || p.gap_ext > 65535 || p.match - p.mismatch > 254)
+    if ((!job.dna && !duo_raw_ok(p, opt)) || p.gap_init + p.match > 65535 || p.gap_ext > 65535 || p.match - p.mismatch > 254)
         return false;
     for (auto& d : job.pairs)
         if ((long long)std::max(p.match, 1) * std::min(d.n, d.m) + p.match > 65535) return false;
@@ -311,8 +419,8 @@ bool duo_fits(const Job& job, const Params& p) {
 // The duo kernel's f16-max3 variant reads u16 values as f16 bit patterns, exact
 // below 0x7C00 (no Inf/NaN encodings): every t, E, F, H and running max is at
 // most max H + MATCH <= MATCH*(min(n,m)+1).
-bool duo_f16_fits(const Job& job, const Params& p) {
-    if (!g_opt_duo_f16.load()) return false;
+bool duo_f16_fits(const Job& job, const Params& p, const Opts& opt) {
+    if (!opt[O_duo16]) return false;
     for (auto& d : job.pairs)
         if ((long long)std::max(p.match, 1) * (std::min(d.n, d.m) + 1) > 0x7BFF) return false;
     return true;
@@ -364,8 +472,8 @@ bool flow2_fits(const Job& job, const Params& p) {
     return job.dna && job.W == 1 && flow2_variant_exists(job.C) && p.match + p.gap_init <= 127 &&
            p.mismatch + p.gap_init >= -127;
 }
-bool flow2_staged(const Job& job, int max_m) {
-    return g_opt_f2stream.load() == 0 && flow2_stage_bytes(max_m, job.C) <= flow2_stage_max(job.C);
+bool flow2_staged(const Job& job, const Opts& opt, int max_m) {
+    return opt[O_f2stream] == 0 && flow2_stage_bytes(max_m, job.C) <= flow2_stage_max(job.C);
 }
 
 // Two columns per lane (sw_flow2.hip W2) whenever the linear-gap step runs (G_INIT ==
@@ -373,17 +481,12 @@ bool flow2_staged(const Job& job, int max_m) {
 // Measured (kernel ms, W = 1 -> 2): C2 3.46 -> 3.17 (half the strip hops and half the
 // wavefront's column term at a 25 instead of 17 ns step), C5 222 -> 181 (4.5 instead
 // of 5.5 VALU per 64 cells, throughput-bound).
-bool flow2_w2_wanted(const Job& job, const Params& p) {
-    const long long o = g_opt_f2w.load();
+bool flow2_w2_wanted(const Job& job, const Params& p, const Opts& opt) {
     // (C = 16: flow3's staged kernel only, sw_flow3.hip; flow2 has no such two-column variant,
     // so streamed rows at C = 16 keep one column per lane)
-    int max_m = 0;
-    for (const PairDesc& d : job.pairs) max_m = std::max(max_m, d.m);
-    const bool c16 = g_opt_f3.load() != 0 && !job.slab && flow2_staged(job, max_m) && flow3_fits(max_m, 16);
-    const bool lin = p.gap_init == p.gap_ext && g_opt_linear.load() != 0 && (job.C != 16 || c16) &&
-                     (g_opt_C.load() == 0 || g_opt_C.load() == 32 || g_opt_C.load() == 64 ||
-                      (g_opt_C.load() == 16 && c16));
-    return lin && o != 1;
+    const int max_m = max_rows(job);
+    const bool c16 = opt[O_f3] != 0 && !job.slab && flow2_staged(job, opt, max_m) && flow3_fits(max_m, 16);
+    return linear_gap(p, opt) && (job.C != 16 || c16) && (opt[O_C] != 16 || c16) && opt[O_f2w] != 1;
 }
 
 // Four and five columns per lane (flow3 ring mode, linear-gap step, one pair): when the three-column
@@ -420,7 +523,7 @@ bool plan_w45(Job& job, int slots) {
 // Re-plan a grouped job for MODE_FLOW2: strips of 64 columns overlapping by one
 // (w2: 128 columns overlapping by two).  pwg: one item per pair, whose workgroup runs all
 // of its strips with LDS hand-offs only (no granule edges).
-void plan_flow2(Job& job, bool w2, bool pwg = false, bool w3 = false) {
+void plan_flow2(const Opts& opt, Job& job, bool w2, bool pwg = false, bool w3 = false) {
     job.mode = MODE_FLOW2;
     job.f2w2 = w2 || w3;
     job.f2w3 = w3;
@@ -441,20 +544,18 @@ void plan_flow2(Job& job, bool w2, bool pwg = false, bool w3 = false) {
     // progress words are compared as serial numbers, and a slot's previous position
     // differs from the current one by the ring size (< 2^25), which the checksum's
     // 25 position bits always see.  Hence rows <= 2^24.
-    const long long opt = g_opt_ring.load();
-    if (job.pairs.size() == 1 && opt != 0 && job.item_base[1] > 1) {
+    if (job.pairs.size() == 1 && opt[O_ring] != 0 && job.item_base[1] > 1) {
         const PairDesc& d = job.pairs[0];
         const bool ok = d.m <= (1 << 24);
-        job.ring = ok && (opt == 1 || (long long)(g * sizeof(Granule)) > RING_AUTO_BYTES);
+        job.ring = ok && (opt[O_ring] == 1 || (long long)(g * sizeof(Granule)) > RING_AUTO_BYTES);
     }
 }
 
 // The pair-per-workgroup kernel keeps a round's rows of its longest pair in LDS: at least
 // `wgs` such workgroups must fit a CU (automatic choice: 2, m up to ~8.5k rows).
-bool pwg_fits(const Job& job, const Params& prm, int wgs) {
-    int max_m = 0;
-    for (const PairDesc& d : job.pairs) max_m = std::max(max_m, d.m);
-    const bool lin = flow2_w2_wanted(job, prm);
+bool pwg_fits(const Job& job, const Params& prm, const Opts& opt, int wgs) {
+    const int max_m = max_rows(job);
+    const bool lin = flow2_w2_wanted(job, prm, opt);
     // the round buffer must also pass the launch's dynamic-LDS limit (sw_flow2.hip flow2_dyn_lds)
     return flow2_pwg_wgs(max_m, 64, lin) >= wgs &&
            flow2_pwg_row_bytes(lin) * flow2_pwg_rows(max_m, 64) <= flow2_stream_dyn_max(64);
@@ -463,10 +564,10 @@ bool pwg_fits(const Job& job, const Params& prm, int wgs) {
 // A batch on the pair-per-workgroup flow2 kernel: W = 1 strips, 64-row chunks, streamed
 // codes; two columns per lane with the linear-gap step (G_INIT == G_EXT), else the affine
 // step at one column per lane.
-void plan_pwg(Job& job, const Params& prm) {
+void plan_pwg(Job& job, const Params& prm, const Opts& opt) {
     job.W = 1;
     job.C = 64;
-    plan_flow2(job, flow2_w2_wanted(job, prm), true);
+    plan_flow2(opt, job, flow2_w2_wanted(job, prm, opt), true);
     job.f2_stream = true;
 }
 
@@ -478,37 +579,33 @@ void plan_pwg(Job& job, const Params& prm) {
 // The general affine step takes the same organisation on the three-column affine ring step
 // (sw_flow3ra3p_kernel, option f3a not 0) where `affine` allows it: C3-shaped at (2, -3, 5, 2) on int32
 // flow2's PWG (one column per lane) runs 21.1 ms.
-bool pwg3_fits(const Job& job, const Params& prm, bool affine = false) {
-    int max_m = 0;
-    for (const PairDesc& d : job.pairs) max_m = std::max(max_m, d.m);
-    const bool lin = prm.gap_init == prm.gap_ext && g_opt_linear.load() != 0;
-    return g_opt_f3pwg.load() != 0 && job.dna && (lin ? g_opt_f3.load() != 0 : affine && g_opt_f3a.load() != 0) &&
-           prm.match + prm.gap_init <= 127 && prm.mismatch + prm.gap_init >= -127 &&
-           max_m <= (1 << 16) && (g_opt_C.load() == 0 || g_opt_C.load() == 64) && g_opt_f2w.load() != 1 &&
-           g_opt_f2w.load() != 2;
+bool pwg3_fits(const Job& job, const Params& prm, const Opts& opt, bool affine = false) {
+    return opt[O_f3pwg] != 0 && job.dna && (linear_gap(prm, opt) ? opt[O_f3] != 0 : affine && opt[O_f3a] != 0) &&
+           prm.match + prm.gap_init <= 127 && prm.mismatch + prm.gap_init >= -127 && max_rows(job) <= (1 << 16) &&
+           (opt[O_C] == 0 || opt[O_C] == 64) && opt[O_f2w] != 1 && opt[O_f2w] != 2;
 }
-void plan_pwg3(Job& job) {
+void plan_pwg3(Job& job, const Opts& opt) {
     job.W = 1;
     job.C = 64;
-    plan_flow2(job, true, true, true);
+    plan_flow2(opt, job, true, true, true);
     job.f3pwg = true;
     job.f2_stream = true;
 }
 
 // A DNA batch on the flow2 item claim: a pair's strip groups spread over many CUs (W = 1
 // strips, 64-row chunks, streamed codes, 2 workgroups per CU from 4 groups per CU).
-void plan_claim(Job& job, const Params& prm) {
+void plan_claim(Job& job, const Params& prm, const Opts& opt) {
     job.W = 1;
     job.C = 64;
-    plan_flow2(job, flow2_w2_wanted(job, prm));
+    plan_flow2(opt, job, flow2_w2_wanted(job, prm, opt));
     job.f2_stream = true;
 }
 
 // A pair's byte set (256 bits) -> job.hep / job.hsym: at most seven values, not all within {A,C,G,T}
 // (those take the DNA path), symbols in byte order.  Option hep = 0: never.
-bool set_hep(Job& job, const uint32_t set[8]) {
+bool set_hep(Job& job, const Opts& opt, const uint32_t set[8]) {
     job.hep = 0;
-    if (g_opt_hep.load() == 0) return false;
+    if (opt[O_hep] == 0) return false;
     int k = 0;
     unsigned char sym[256] = {};
     for (int b = 0; b < 256; ++b)
@@ -526,20 +623,125 @@ void byte_set(const unsigned char* p, int len, uint32_t set[8]) {
     for (int i = 0; i < len; ++i) set[p[i] >> 5] |= 1u << (p[i] & 31);
 }
 
-// The flow3 launch enqueue would make of a planned single-pair job, when it is one of the kernels with
-// seven-letter alphabets (HEP): staged (use_f3 without ring or streamed rows, or use_f3a), or ring mode at
-// three columns per lane, whole-chunk links (sw_flow3r3h / ra3h_kernel)
-bool hep_launchable(const Job& job, const Params& prm) {
-    if (job.mode != MODE_FLOW2 || job.slab || job.pwg || job.f3pwg || job.pairs.size() != 1) return false;
-    const int max_m = job.pairs[0].m;
-    const bool lin = prm.gap_init == prm.gap_ext && g_opt_linear.load() != 0 &&
-                     (job.C == 32 || job.C == 64 || (job.C == 16 && job.f2w2));
-    if (job.ring)
-        return job.f2w2 && job.f2w3 && job.w45_s4 < 0 && job.C == 64 && g_opt_f3rhl.load() == 0 &&
-               g_opt_f3slab.load() != 0 && (lin ? g_opt_f3.load() != 0 : g_opt_f3a.load() != 0);
-    if (job.f2_stream || g_opt_f3pool.load() != 0) return false;
-    if (job.f2w2) return lin && g_opt_f3.load() != 0 && flow3_fits(max_m, job.C);
-    return !lin && g_opt_f3a.load() != 0 && (job.C == 32 || job.C == 16) && flow3_fits(max_m, job.C, true);
+// ---- the launch a planned job makes -----------------------------------------
+// Decided here and nowhere else: every field of LaunchCfg but the two that wait for the residency query
+// (f2_wgs and blocks: size_grid), whether it is a ring launch, whether the pair was cut (plan_split), and
+// the reason when the plan asks for a kernel that does not exist.
+struct Variant {
+    LaunchCfg cfg;
+    bool ring = false;
+    bool cut = false;
+    const char* err = nullptr;
+};
+
+// Duo batches at C = 64: strip hand-offs in LDS when the wrap buffer (a round's rows of both pairs) fits
+// the default dynamic-LDS limit; no boundary buffers in HBM then.  And, at 4 or 8 columns per lane, the
+// row codes from an LDS table when both fit two workgroups per CU and the duos run in one pass at that
+// (C3, 512 duos: 6.80 -> 6.54 ms), or rows are 8192 or more; more duos of shorter rows keep the
+// table-less kernel, whose smaller LDS admits 4 per CU.  With the CU's two workgroups taking turns at
+// priority (duo_prio) the table wins at 8192 rows: 8192 pairs of 8192 51.8 -> 50.5 ms, 2048 pairs 13.2 ->
+// 12.6, 4096 pairs of 1024 x 8192 4.59 -> 4.46; it loses at 4096 rows (4096 pairs of 4096: 7.88 -> 8.03)
+// and on the ragged DB search (17.9 -> 19.7), r05_duo_prio.md
+void select_duo_lds(const Job& job, const Opts& opt, int cus, LaunchCfg& cfg) {
+    if (job.mode != MODE_DUO || job.C != 64 || opt[O_duo_lds] == 0) return;
+    int max_mp = 0;
+    for (const DuoDesc& d : job.duos) max_mp = std::max(max_mp, d.m_pad);
+    const int slots = duo_wrap_slots(max_mp);
+    const long long wrap_b = (long long)slots * (cfg.f2_lin ? 4 : 8);
+    const int tab_w = DUO_TAB_OFF + max_mp + DUO_TAB_TAIL;
+    const bool one_pass = (long long)job.duos.size() <= 2LL * cus || opt[O_duo_tab] == 2 || max_mp >= 8192;
+    if (opt[O_duo_tab] != 0 && one_pass && job.W % 4 == 0 && wrap_b + 4LL * tab_w + 16 <= duo_lds_fit(cfg.f2_lin)) {
+        cfg.duo_wrap = slots;
+        cfg.duo_tab = tab_w;
+    } else if (wrap_b <= 64 * 1024) {
+        cfg.duo_wrap = slots;
+    }
+}
+
+Variant select_variant(const Job& job, const Params& prm, const Opts& opt, int cus) {
+    const bool flow2 = job.mode == MODE_FLOW2, slab = job.slab, ring = job.ring;
+    Variant v;
+    v.ring = ring;
+    v.cut = !job.pairs.empty() && (job.pairs[0].flags & PAIR_HALF) != 0;
+    LaunchCfg& cfg = v.cfg = LaunchCfg{job.W, job.C, job.dna, 0, job.mode, max_rows(job)};
+    // flow2's ring and slab kernels always stream the row codes (sw_flow2.hip launch_v)
+    const bool f2s = flow2 && (job.f2_stream || ring || slab);
+    // the linear-gap step; the pair-per-workgroup kernel is built with it exactly at two columns per lane
+    const bool lin = linear_gap(prm, opt);
+    const bool f2_lin = job.f3pwg ? lin
+                      : job.pwg   ? job.f2w2
+                                  : lin && ((flow2 && (job.C == 32 || job.C == 64 || (job.C == 16 && job.f2w2))) ||
+                                            (job.mode == MODE_DUO && job.duo_f16));
+    // flow3 (sw_flow3.hip, hand-scheduled chunk loops) for the two-column linear-gap launches it
+    // implements: the staged single-pair kernel (C = 16 / 32, rows in LDS: C2) and ring mode (C = 64
+    // / 32, streamed rows, one pair: C5); option f3 = 0 keeps flow2
+    const bool f3_base = opt[O_f3] != 0 && flow2 && job.f2w2 && f2_lin && !job.pwg;
+    const bool f3_slab_ok = !slab || (opt[O_f3slab] != 0 && job.C == 64);
+    const bool use_f3 = f3_base && ((!f2s && !ring && flow3_fits(cfg.max_m, job.C)) ||
+                                    (ring && f3_slab_ok && (job.C == 64 || job.C == 32)));
+    // the general affine step (G_INIT != G_EXT, or option linear = 0) on flow3's staged kernel: one
+    // column per lane, rows in LDS, linear edges (C2 with affine constants); option f3a = 0 keeps flow2
+    const bool use_f3a = opt[O_f3a] != 0 && flow2 && !job.f2w2 && !f2_lin && !job.pwg && !f2s && !ring && !slab &&
+                         (job.C == 32 || job.C == 16) && flow3_fits(cfg.max_m, job.C, true);
+    // ... and in ring mode at two columns per lane (finalize_mode planned the strips for it)
+    const bool use_f3ra = opt[O_f3a] != 0 && flow2 && job.f2w2 && !f2_lin && !job.pwg && ring && f3_slab_ok && job.C == 64;
+    cfg.duo_f16 = job.mode == MODE_DUO && job.duo_f16;
+    cfg.f2_stream = f2s;
+    cfg.f2_lin = f2_lin;
+    cfg.f2_w2 = flow2 && job.f2w2;
+    cfg.f2_pwg = flow2 && job.pwg;
+    cfg.f3 = use_f3;
+    // half-chunk links: staged at C = 32 (option f3hl), ring at C = 64 (f3rhl; the slab roles and the affine
+    // ring step exist with whole-chunk links only)
+    cfg.f3_hl = (use_f3 && !slab && ((!ring && job.C == 32 && opt[O_f3hl] != 0) || (ring && job.C == 64 && opt[O_f3rhl] != 0))) ||
+                (use_f3a && job.C == 32 && opt[O_f3hl] != 0);
+    cfg.f3a = use_f3a;
+    cfg.f3ra = use_f3ra;
+    cfg.f3_slab = (use_f3 || use_f3ra) && slab;
+    // the pool loops (no I/O rotation, tools/gen_flow3.py gen_pool) for staged launches with half-chunk
+    // links at C = 32, both steps, when option f3pool = 1 (default 0: measured slower)
+    cfg.f3p = opt[O_f3pool] != 0 && cfg.f3_hl && job.C == 32 && !ring && (use_f3 || use_f3a);
+    cfg.f3_w3 = job.f2w3 && job.w45_s4 < 0;
+    cfg.f3_w45 = job.w45_s4 >= 0;
+    cfg.hep = job.hep > 0;
+    cfg.f3_pwg = job.f3pwg;
+    select_duo_lds(job, opt, cus, cfg);
+    const bool f3_ring = (use_f3 || use_f3ra) && ring;
+    if (job.f3pwg && (slab || ring || !job.f2w3))
+        v.err = "the pair-per-workgroup three-column kernel takes batches only";
+    else if (cfg.hep && !((use_f3 && !f2s && !ring) || use_f3a || (f3_ring && cfg.f3_w3 && !slab && !job.f3pwg)))
+        v.err = "a seven-letter alphabet runs flow3's staged kernels or its three-column ring kernels only (one pair)";
+    else if (cfg.f3_w45 && !(use_f3 && ring && !slab))
+        v.err = "four / five columns per lane run on flow3's linear-gap ring kernel only (one pair, not a slab)";
+    else if (job.f2w3 && !job.f3pwg && !(f3_ring && job.C == 64 && !cfg.f3_hl))
+        v.err = "three columns per lane run on flow3's ring kernel only (linear-gap step, C = 64, whole-chunk links)";
+    else if (cfg.f2_w2 && job.C == 16 && !use_f3)
+        v.err = "flow2: two columns per lane at C = 16 runs on flow3 only (rows staged in LDS, one GPU)";
+    else if (cfg.f2_w2 && !f2_lin && !use_f3ra && !job.f3pwg)   // the strips were cut for two columns per lane
+        v.err = "flow2: two columns per lane needs the linear-gap step (or flow3's affine ring kernel)";
+    if (job.f3pwg) {   // the linear-gap ring step, or the affine one (sw_flow3ra3p_kernel)
+        cfg.f3 = f2_lin;
+        cfg.f3ra = !f2_lin;
+    }
+    return v;
+}
+
+// The variant word of sw_last_stats (include/algoGPU.h documents the bits)
+int variant_word(const Variant& v) {
+    const LaunchCfg& c = v.cfg;
+    const bool bits[18] = {c.duo_f16, c.f2_stream, v.ring,     c.f2_lin, c.f2_w2, c.f2_pwg, c.f3,    c.duo_wrap > 0, c.duo_tab > 0,
+                           c.f3_hl,   c.f3a || c.f3ra, c.f3_slab, c.f3p,  c.f3_w3, c.f3_w45, c.f3_pwg, c.hep,       v.cut};
+    int w = 0;
+    for (int b = 0; b < 18; ++b) w |= (bits[b] ? 1 : 0) << b;
+    return w;
+}
+
+// A seven-letter job (planned as DNA) launches one of the kernels with seven-letter forms: flow3's
+// staged kernels (not the pool loops), or ring mode at three columns per lane (sw_flow3r3h / ra3h_kernel)
+bool hep_launchable(const Job& job, const Params& prm, const Opts& opt, int cus) {
+    if (job.pairs.size() != 1) return false;
+    const Variant v = select_variant(job, prm, opt, cus);
+    return !v.err && !v.cfg.f3p;
 }
 
 // One pair on flow3's staged two-column linear-gap kernel, cut at a column and scored from both ends at
@@ -560,20 +762,17 @@ bool split_cols(int n, int* c, int* lead) {
 constexpr int F3_SPLIT_AUTO_N = 4096;
 
 // Cuts a planned single-pair job in two PairDesc entries sharing one score slot when its launch is the
-// staged flow3 linear-gap kernel with rotating loops (the conditions enqueue derives use_f3 from, less
-// ring mode, streamed rows, slabs, batches, the pool loops and traced launches).  Items stay in claim
-// order, the left half's groups first: every group waits on a lower item only, whatever the grid.
-bool plan_split(Job& job, const Params& prm) {
-    const long long o = g_opt_f3split.load();
-    if (o == 0 || job.pairs.size() != 1 || job.mode != MODE_FLOW2 || !job.dna || !job.f2w2 || job.f2w3 || job.pwg ||
-        job.f3pwg || job.ring || job.f2_stream || job.slab || (job.C != 32 && job.C != 16))
-        return false;
-    if (g_opt_f3.load() == 0 || g_opt_f3pool.load() != 0 || g_opt_trace.load() != 0 || g_opt_linear.load() == 0 ||
-        prm.gap_init != prm.gap_ext)
-        return false;
+// staged flow3 linear-gap kernel with rotating loops (not ring mode, streamed rows, a slab, a batch or the
+// pool loops) and is not traced.  Items stay in claim order, the left half's groups first: every group
+// waits on a lower item only, whatever the grid.
+bool plan_split(Job& job, const Params& prm, const Opts& opt, int cus) {
+    const long long o = opt[O_f3split];
+    if (o == 0 || job.pairs.size() != 1 || opt[O_trace] != 0) return false;
+    const Variant v = select_variant(job, prm, opt, cus);
+    if (v.err || !v.cfg.f3 || v.ring || v.cfg.f2_stream || v.cfg.f3p) return false;
     const PairDesc whole = job.pairs[0];
     int c = 0, lead = 0;
-    if (!flow3_fits(whole.m, job.C) || !split_cols(whole.n, &c, &lead)) return false;
+    if (!split_cols(whole.n, &c, &lead)) return false;
     if (o < 0 && whole.n < F3_SPLIT_AUTO_N) return false;
     PairDesc left = whole, right = whole;
     left.n = c;
@@ -593,70 +792,69 @@ bool plan_split(Job& job, const Params& prm) {
     return true;
 }
 
-int finalize_mode(Job& job, const Params& prm, int cus);
+int finalize_mode(Job& job, const Params& prm, const Opts& opt, int cus);
 
 // finalize_mode, and for a seven-letter job (planned as DNA) the check that it lands on the staged flow3
 // kernels; otherwise the job is re-planned on the byte path
-int finalize_alphabet(Job& job, const Params& prm, int cus, bool single) {
+int finalize_alphabet(Job& job, const Params& prm, const Opts& opt, int cus, bool single) {
     if (job.hep) job.dna = true;
-    if (finalize_mode(job, prm, cus)) return -1;
-    if (!job.hep || hep_launchable(job, prm)) return 0;
+    if (finalize_mode(job, prm, opt, cus)) return -1;
+    if (!job.hep || hep_launchable(job, prm, opt, cus)) return 0;
     // a fresh job (the DNA attempt left its ring / column / stream flags behind) on the byte path
     Job bytes;
     bytes.pairs = job.pairs;
     bytes.slab = job.slab;
     bytes.dna = false;
     job = std::move(bytes);
-    const int W = pick_W(job.pairs, single);
-    plan(job, W, pick_C(W), single);
-    return finalize_mode(job, prm, cus);
+    const int W = pick_W(opt, job.pairs, single);
+    plan(opt, job, W, pick_C(opt, W), single);
+    return finalize_mode(job, prm, opt, cus);
 }
 
-int finalize_mode(Job& job, const Params& prm, int cus) {
-    int max_m = 0;
-    for (const PairDesc& d : job.pairs) max_m = std::max(max_m, d.m);
+int finalize_mode(Job& job, const Params& prm, const Opts& opt, int cus) {
+    const int max_m = max_rows(job);
     // a single pair too wide for W = 1 under the 2048-strip rule: flow2 still runs it
     // fastest at W = 1 (its 10.7-VALU step, rows streamed when they exceed the LDS;
     // C5: 545 ms vs 894 ms for the W = 8 chain)
-    if (g_opt_mode.load() < 0 && g_opt_W.load() == 0 && job.mode == MODE_CHAIN && job.W > 1 &&
+    if (opt[O_mode] < 0 && opt[O_W] == 0 && job.mode == MODE_CHAIN && job.W > 1 &&
         job.pairs.size() == 1) {
         Job w1 = job;
-        plan(w1, 1, pick_C(1), true, MODE_CHAIN);
+        plan(opt, w1, 1, pick_C(opt, 1), true, MODE_CHAIN);
         if (flow2_fits(w1, prm)) job = w1;
     }
-    if (job.mode == MODE_FLOW2 && job.pairs.size() > 1 && g_opt_f2pwg.load() == 1) {
+    if (job.mode == MODE_FLOW2 && job.pairs.size() > 1 && opt[O_f2pwg] == 1) {
         Job w1 = job;   // a forced flow2 batch, a pair per workgroup (W = 1 strips, C = 64)
-        plan(w1, 1, 64, false, MODE_FLOW2);
-        if (flow2_fits(w1, prm) && pwg3_fits(w1, prm, true)) {
+        plan(opt, w1, 1, 64, false, MODE_FLOW2);
+        if (flow2_fits(w1, prm) && pwg3_fits(w1, prm, opt, true)) {
             job = w1;
-            plan_pwg3(job);
+            plan_pwg3(job, opt);
             return 0;
         }
-        if (flow2_fits(w1, prm) && pwg_fits(w1, prm, 1)) {
+        if (flow2_fits(w1, prm) && pwg_fits(w1, prm, opt, 1)) {
             job = w1;
-            plan_pwg(job, prm);
+            plan_pwg(job, prm, opt);
             return 0;
         }
     }
-    if (job.mode == MODE_FLOW2 || (g_opt_mode.load() < 0 && job.mode == MODE_CHAIN)) {
+    if (job.mode == MODE_FLOW2 || (opt[O_mode] < 0 && job.mode == MODE_CHAIN)) {
         if (flow2_fits(job, prm)) {
-            plan_flow2(job, flow2_w2_wanted(job, prm));
+            plan_flow2(opt, job, flow2_w2_wanted(job, prm, opt));
             // the affine step in ring mode runs flow3's two-column affine kernel (sw_flow3ra_kernel:
             // ring mode is throughput-bound, and two columns per lane issue 9 VALU per 64 cells
             // against 10.5 at one): re-plan with two-column strips when they still take ring mode
-            if (job.ring && !job.f2w2 && !job.slab && g_opt_f3a.load() != 0 && g_opt_f2w.load() != 1 &&
-                (g_opt_C.load() == 0 || g_opt_C.load() == 64)) {
+            if (job.ring && !job.f2w2 && !job.slab && opt[O_f3a] != 0 && opt[O_f2w] != 1 &&
+                (opt[O_C] == 0 || opt[O_C] == 64)) {
                 Job w2 = job;
-                plan_flow2(w2, true);
+                plan_flow2(opt, w2, true);
                 if (w2.ring) job = w2;
             }
             // a column slab (f-1) runs flow3's ring kernel with its slab roles (sw_flow3rs_kernel /
             // sw_flow3ras_kernel): two columns per lane, ring edges between its own groups (forced
             // for any size; with one group there are none), option f3slab = 0 keeps flow2's slab kernel
-            const bool lin = prm.gap_init == prm.gap_ext && g_opt_linear.load() != 0;
-            if (job.slab && g_opt_f3slab.load() != 0 && (lin ? g_opt_f3.load() != 0 : g_opt_f3a.load() != 0) &&
-                g_opt_f2w.load() != 1 && g_opt_ring.load() != 0 && (g_opt_C.load() == 0 || g_opt_C.load() == 64)) {
-                if (!job.f2w2) plan_flow2(job, true);
+            const bool lin = linear_gap(prm, opt);
+            if (job.slab && opt[O_f3slab] != 0 && (lin ? opt[O_f3] != 0 : opt[O_f3a] != 0) &&
+                opt[O_f2w] != 1 && opt[O_ring] != 0 && (opt[O_C] == 0 || opt[O_C] == 64)) {
+                if (!job.f2w2) plan_flow2(opt, job, true);
                 job.ring = true;
             }
             // three columns per lane (flow3 ring mode, linear-gap step, C = 64; option f2w = 0 or 3): a
@@ -664,27 +862,26 @@ int finalize_mode(Job& job, const Params& prm, int cus) {
             // slab 0 of 8 38.6 -> 33.1 ms (its 1041 two-column strips need 261 groups for 256 CUs, and
             // the 5 CUs running two pace the chain; 694 three-column strips fit 174 groups).  A slab
             // with f3slab = 0 stays on flow2's slab kernel, which has no three-column form.
-            if (job.ring && job.f2w2 && (!job.slab || g_opt_f3slab.load() != 0) && (lin ? g_opt_f3.load() != 0 && g_opt_f3rhl.load() == 0 : g_opt_f3a.load() != 0) &&
-                (g_opt_f2w.load() == 3 || g_opt_f2w.load() == 0 || g_opt_f2w.load() == 4) &&
-                (g_opt_C.load() == 0 || g_opt_C.load() == 64)) {
-                plan_flow2(job, true, false, true);
+            if (job.ring && job.f2w2 && (!job.slab || opt[O_f3slab] != 0) && (lin ? opt[O_f3] != 0 && opt[O_f3rhl] == 0 : opt[O_f3a] != 0) &&
+                (opt[O_f2w] == 3 || opt[O_f2w] == 0 || opt[O_f2w] == 4) &&
+                (opt[O_C] == 0 || opt[O_C] == 64)) {
+                plan_flow2(opt, job, true, false, true);
                 job.ring = true;
                 // ... or four and five with option f2w = 4 (every group resident in one round; measured
                 // slower on C5, 167 against 154 ms: plan_w45).  Its grid is F2_WGS_MAX blocks per CU, or
                 // option blocks (tests cut small pairs into both widths with it)
-                const long long w = g_opt_f2w.load();
-                const int slots = g_opt_blocks.load() > 0 ? (int)g_opt_blocks.load() : cus * F2_WGS_MAX;
-                if (lin && !job.slab && job.pairs.size() == 1 && w == 4) plan_w45(job, slots);
+                const int slots = opt[O_blocks] > 0 ? (int)opt[O_blocks] : cus * F2_WGS_MAX;
+                if (lin && !job.slab && job.pairs.size() == 1 && opt[O_f2w] == 4) plan_w45(job, slots);
             }
-            job.f2_stream = job.ring || !flow2_staged(job, max_m);   // ring mode runs with streamed codes
+            job.f2_stream = job.ring || !flow2_staged(job, opt, max_m);   // ring mode runs with streamed codes
             // ring mode (one pair of many groups per CU, C5): throughput-bound, so 64-row chunks
             // (half the per-chunk work per step) beat the shorter hand-off lag of 32 (C5 249 -> 220 ms)
-            if (job.ring && g_opt_C.load() == 0) job.C = 64;
+            if (job.ring && opt[O_C] == 0) job.C = 64;
             // the staged two-column kernel on flow3 (C2): 32-row chunks whose in-workgroup links hand
             // off every half chunk (option f3hl, default 1: C = 32's per-chunk work at a 63 + 16-step
             // lag, 2.645 -> 2.600 ms); with f3hl = 0, 16-row chunks (2.70 -> 2.65 ms against plain 32)
-            if (!job.ring && !job.f2_stream && !job.slab && job.f2w2 && g_opt_C.load() == 0 && g_opt_f3.load() != 0 &&
-                g_opt_f3hl.load() == 0 && flow3_fits(max_m, 16))
+            if (!job.ring && !job.f2_stream && !job.slab && job.f2w2 && opt[O_C] == 0 && opt[O_f3] != 0 &&
+                opt[O_f3hl] == 0 && flow3_fits(max_m, 16))
                 job.C = 16;
             return 0;
         }
@@ -695,12 +892,12 @@ int finalize_mode(Job& job, const Params& prm, int cus) {
         }
     }
     // single long DNA pairs: the barrier-free flow kernel when the row codes fit in LDS
-    if (job.mode == MODE_FLOW || (g_opt_mode.load() < 0 && job.mode == MODE_CHAIN)) {
+    if (job.mode == MODE_FLOW || (opt[O_mode] < 0 && job.mode == MODE_CHAIN)) {
         const bool fits = job.dna && flow_stage_rows(max_m, job.W, job.C) <= flow_stage_max(job.W, job.C);
         if (fits) {
             job.mode = MODE_FLOW;
         } else if (job.mode == MODE_FLOW) {
-            if (g_opt_mode.load() == MODE_FLOW) {
+            if (opt[O_mode] == MODE_FLOW) {
                 set_err("flow mode needs {A,C,G,T} rows that fit in LDS (m <= %d at W=%d)",
                         flow_stage_max(job.W, job.C) - 64 * job.W - 2 * job.C - 80, job.W);
                 return -1;
@@ -709,7 +906,7 @@ int finalize_mode(Job& job, const Params& prm, int cus) {
         }
     }
     const bool forced_duo = job.mode == MODE_DUO;
-    if (forced_duo || (g_opt_mode.load() < 0 && job.mode == MODE_PAIRWG)) {
+    if (forced_duo || (opt[O_mode] < 0 && job.mode == MODE_PAIRWG)) {
         // DNA batches by size (measured, DESIGN.md section 8, kernel ms for duo / PWG / item claim):
         //   fewer pairs than CUs: the flow2 item claim spreads each pair's strip groups
         //     (128 x 8192: 3.87 / 3.53 / 2.46; 128 x 16384: 14.2 / 12.1 / 8.9; 16 x 65536: pairwg
@@ -719,30 +916,30 @@ int finalize_mode(Job& job, const Params& prm, int cus) {
         //   more: the 16-bit duos when exact (512 x 8192: 4.02 / 5.40 / 8.83; C3: 7.29 / 9.95 /
         //     15.1), else a pair per workgroup, else the item claim.
         const int P = (int)job.pairs.size();
-        const bool flow2_auto = !forced_duo && P > 1 && job.dna && g_opt_f2pwg.load() != 0;
+        const bool flow2_auto = !forced_duo && P > 1 && job.dna && opt[O_f2pwg] != 0;
         Job w1 = job;
-        if (flow2_auto) plan(w1, 1, 64, false, MODE_CHAIN);
+        if (flow2_auto) plan(opt, w1, 1, 64, false, MODE_CHAIN);
         const bool f2ok = flow2_auto && flow2_fits(w1, prm);
         if (f2ok && P < cus) {
             job = w1;
-            plan_claim(job, prm);
+            plan_claim(job, prm, opt);
             return 0;
         }
         // (256 x 8192, kernel ms, flow2 PWG / flow3 PWG at three columns: 3.30 / 2.87; 384: 5.25 / 5.05;
         // 16384 rows, 256 pairs: 12.4 / 11.1; profiles/r06_pwg3_sweep.jsonl)
-        if (f2ok && P < 2 * cus && pwg3_fits(w1, prm)) {
+        if (f2ok && P < 2 * cus && pwg3_fits(w1, prm, opt)) {
             job = w1;
-            plan_pwg3(job);
+            plan_pwg3(job, opt);
             return 0;
         }
-        if (f2ok && P < 2 * cus && pwg_fits(w1, prm, 2)) {
+        if (f2ok && P < 2 * cus && pwg_fits(w1, prm, opt, 2)) {
             job = w1;
-            plan_pwg(job, prm);
+            plan_pwg(job, prm, opt);
             return 0;
         }
-        if (duo_fits(job, prm)) {
+        if (duo_fits(job, prm, opt)) {
             job.mode = MODE_DUO;
-            job.duo_f16 = duo_f16_fits(job, prm);
+            job.duo_f16 = duo_f16_fits(job, prm, opt);
             plan_duos(job);
             return 0;
         }
@@ -757,9 +954,9 @@ int finalize_mode(Job& job, const Params& prm, int cus) {
         // ms), else the item claim
         if (f2ok) {
             job = w1;
-            if (pwg3_fits(w1, prm, true)) plan_pwg3(job);
-            else if (pwg_fits(w1, prm, 2)) plan_pwg(job, prm);
-            else plan_claim(job, prm);
+            if (pwg3_fits(w1, prm, opt, true)) plan_pwg3(job, opt);
+            else if (pwg_fits(w1, prm, opt, 2)) plan_pwg(job, prm, opt);
+            else plan_claim(job, prm, opt);
         }
     }
     return 0;
@@ -772,7 +969,7 @@ int finalize_mode(Job& job, const Params& prm, int cus) {
 // Returns the column quantum a slab with an outflow edge must be a multiple
 // of -- 63 for flow2 (its last strip's lane 62 is then the slab's last column),
 // 64*W for chain / flow (no dead columns at the edge) -- or -1.
-int plan_slab(Job& job, int n, int m, bool dna, const Params& prm) {
+int plan_slab(Job& job, int n, int m, bool dna, const Params& prm, const Opts& opt) {
     job.pairs.assign(1, PairDesc{});
     PairDesc& d = job.pairs[0];
     d.n = n;
@@ -780,11 +977,11 @@ int plan_slab(Job& job, int n, int m, bool dna, const Params& prm) {
     d.out_idx = 0;
     job.dna = dna;
     job.slab = true;
-    const long long fw = g_opt_W.load();
+    const long long fw = opt[O_W];
     const int W = fw ? (int)fw : 1;
-    const long long fm = g_opt_mode.load();
-    plan(job, W, pick_C(W), true, fm >= 0 ? (int)fm : MODE_CHAIN);
-    if (finalize_mode(job, prm, 256)) return -1;   // one pair: the CU count plays no part
+    const long long fm = opt[O_mode];
+    plan(opt, job, W, pick_C(opt, W), true, fm >= 0 ? (int)fm : MODE_CHAIN);
+    if (finalize_mode(job, prm, opt, 256)) return -1;   // one pair: the CU count plays no part
     if (!grouped_mode(job.mode)) {
         set_err("a column slab needs a grouped kernel (chain, flow or flow2), not mode %d", job.mode);
         return -1;
@@ -794,8 +991,8 @@ int plan_slab(Job& job, int n, int m, bool dna, const Params& prm) {
 
 // Alphabet of a slab call: stated by the caller, never scanned, because every
 // rank must plan the same kernel family for its slab.
-int slab_dna(int flags, bool* dna) {
-    const bool bytes = (flags & SW_FLAG_BYTES) || g_opt_bytes.load();
+int slab_dna(const Opts& opt, int flags, bool* dna) {
+    const bool bytes = (flags & SW_FLAG_BYTES) || opt[O_bytes];
     if (!bytes && !(flags & SW_FLAG_DNA)) {
         set_err("column slabs need SW_FLAG_DNA or SW_FLAG_BYTES: every rank must plan the same kernel");
         return -1;
@@ -846,17 +1043,112 @@ __global__ void hep_rows_kernel(const unsigned char* rows, int m, unsigned char*
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < m; i += gridDim.x * blockDim.x) out[i] = t.sel[rows[i]];
 }
 
-// Enqueue the launch for a planned job whose sequences are in `d_seq`.
-int enqueue(Ctx* c, Job& job, const Params& prm, const unsigned char* d_seq, int* d_scores, int nscores,
-            hipStream_t s, bool time_kernel, const SlabEdge* edge = nullptr) {
-    if (job.mode == MODE_FLOW2 ? !flow2_variant_exists(job.C) : !variant_exists(job.W, job.C)) {
-        set_err("no kernel variant for W=%d C=%d", job.W, job.C);
+// ---- enqueue: the steps of one launch ---------------------------------------
+// What the residency query and the grid rules add to a Variant: workgroups per CU of the streamed flow2 /
+// flow3 kernels, the grid, and the ring rows of the wrap ring (ring mode) or of each block's edge ring
+// (a pair per workgroup at three columns)
+struct Grid {
+    int f2_wgs = 1, blocks = 0, wpc = 0, wrap_rows = 0;
+};
+
+// flow2 workgroups per CU: the staged kernel (C2) keeps one (a lone wave per SIMD: its step latency is
+// the critical path); the streamed kernel of a pair with many strip groups per CU (C5) is
+// throughput-bound, and more waves per SIMD hide each other's issue latency (sw_flow2.hip launch_c sizes
+// the LDS pad).  Measured (kernel ms, ring | linear edges, 1/2/3/4 per CU):
+//   N = 2^17 (520 groups)   9.8 9.7 9.6 9.6   | 9.4 10.8 12.5 12.8
+//   N = 2^18 (1040)         32.4 25.2 26.2 26.4 | 31.7 26.3 34.2 32.1
+//   N = 2^19 (2080)         116 83.9 80.1 78.9  | 117 83.2 88.5 96.2
+//   N = 2^20 (4162, C5)     437 312 287 283     | 454 307 299 -
+// ring: one per 2 CUs' worth of groups, up to 4, or one round of all groups when they fit (size_ring);
+// three columns per lane: 4 (C5's 1388 groups: 2 / 3 / 4 per CU 159.5 / 156.6 / 155.6 ms; 694 or 925
+// blocks 166.4 / 159.3); linear edges: 2 from 4 groups per CU
+int pick_f2_wgs(const Job& job, const Variant& v, const Opts& opt, int cus, int items) {
+    if (!v.cfg.f2_stream) return 1;
+    if (opt[O_f2_wgs] > 0) return (int)opt[O_f2_wgs];
+    const int per_cu = items / cus;
+    // a pair per workgroup: every pair resident in one pass when the LDS admits it
+    // (ceil: cus < P < 2 cus needs 2 per CU, not a second pass of P - cus pairs)
+    const int per_cu_ceil = (items + cus - 1) / cus;
+    if (v.ring) return items <= cus * F2_WGS_MAX || job.f2w3 ? F2_WGS_MAX : std::min(F2_WGS_MAX, std::max(1, per_cu / 2));
+    if (job.f3pwg) return std::min(F2_WGS_MAX, std::max(1, per_cu_ceil));
+    if (job.pwg) return std::min({F2_WGS_MAX, std::max(1, per_cu_ceil), flow2_pwg_wgs(v.cfg.max_m, job.C, job.f2w2)});
+    return per_cu >= 4 ? 2 : 1;
+}
+
+// Ring mode deals groups to blocks statically, so every block must be resident at once: ask the runtime
+// how many workgroups of the kernel this launch runs fit a CU (registers, waves and the LDS pad of
+// f2_wgs), take no more per CU than that, and size the grid (g.blocks) and the ring arena from it.
+int size_ring(Job& job, const Variant& v, const Opts& opt, int cus, int items, Grid& g) {
+    LaunchCfg probe = v.cfg;
+    int fit = 0;
+    for (;; --g.f2_wgs) {
+        probe.f2_wgs = g.f2_wgs;
+        fit = v.cfg.f3 || v.cfg.f3ra ? flow3_ring_resident(probe) : flow2_stream_resident(probe, true, job.slab);
+        if (fit >= g.f2_wgs || g.f2_wgs == 1) break;
+    }
+    if (fit < 1) {
+        set_err("flow2 ring mode: the runtime reports %d resident workgroups per CU for its kernel", fit);
         return -1;
     }
+    g.blocks = std::min(items, cus * g.f2_wgs);
+    if (opt[O_f2_wgs] <= 0 && items <= cus * g.f2_wgs) {
+        // every group in one round (one block each) when they fit the resident blocks:
+        // a second round of a few groups runs them alone on their SIMDs after the rest.
+        // Measured (column slab 0 alone): 1/8 of C5, 260 groups: 256 blocks (2 rounds)
+        // 51.7 ms -> 260 blocks 42.7 ms; 1/4, 520 groups: 512 blocks 77.8 -> 520 60.8 ms.
+        // More groups than that keep one block per 2 CUs' worth of groups, a multiple of
+        // the CU count (the dispatcher then loads every CU evenly: C5's 2081 groups on
+        // 1024 blocks 181.8 ms, on 1041 blocks at up to 5 per CU 205.7 ms).
+        g.blocks = items;
+        g.f2_wgs = std::max(1, (items + cus - 1) / cus);
+    }
+    if (opt[O_blocks] > 0) g.blocks = (int)std::min<long long>(opt[O_blocks], items);
+    if (g.blocks > cus * fit) {
+        set_err("flow2 ring mode needs all %d workgroups co-resident (%d fit per CU, %d CUs)", g.blocks, fit, cus);
+        return -1;
+    }
+    g.wrap_rows = 1;
+    while (g.wrap_rows < job.pairs[0].m) g.wrap_rows *= 2;
+    job.bnd_granules = (uint64_t)(g.blocks - 1) * (uint64_t)opt[O_ring_rows] + (uint64_t)g.wrap_rows;
+    return 0;
+}
+
+// The grid of a launch and, where the kernel keeps its edges in rings, their size (job.bnd_granules)
+int size_grid(Ctx* c, Job& job, Variant& v, const Opts& opt, size_t np, Grid& g) {
+    const int items = job.item_base[np];
+    g.f2_wgs = pick_f2_wgs(job, v, opt, c->cus, items);
+    if (v.cfg.duo_wrap > 0) job.bnd_granules = 0;   // strip hand-offs in LDS
+    if (v.ring && size_ring(job, v, opt, c->cus, items, g)) return -1;
+    v.cfg.f2_wgs = g.f2_wgs;
+    g.wpc = waves_per_cu(c, v.cfg);
+    long long blocks = opt[O_blocks];
+    if (blocks <= 0) {
+        const int wpb = job.mode == MODE_DUO ? DUO_WAVES : 4;   // waves per workgroup
+        const long long cap = (long long)c->cus * std::max(1, g.wpc / wpb);
+        // strip mode: 4 independent waves per block; chain: one block per group;
+        // pair-per-workgroup: one block per pair (grid-stride over pairs)
+        const long long want = job.mode == MODE_STRIP ? (items + 3) / 4 : grouped_mode(job.mode) ? items : (long long)np;   // pairwg/duo: np workgroups
+        blocks = std::min<long long>(want, cap);
+        // flow2 holds one workgroup per CU (its LDS size forces it); a grid larger than
+        // the CU count would only park extra workgroups until a CU frees up
+        if (job.mode == MODE_FLOW2) blocks = std::min<long long>(blocks, (long long)c->cus * g.f2_wgs);
+    }
+    if (v.ring) blocks = g.blocks;   // checked co-resident (size_ring)
+    if (job.f3pwg) {
+        // one edge ring per block (a pair's strip edge, >= max m rows); the grid: a block per pair up
+        // to f2_wgs per CU, blocks running further pairs in turn (no block waits on another)
+        blocks = std::min<long long>(np, opt[O_blocks] > 0 ? opt[O_blocks] : (long long)c->cus * g.f2_wgs);
+        g.wrap_rows = 64;
+        while (g.wrap_rows < v.cfg.max_m) g.wrap_rows *= 2;
+        job.bnd_granules = (uint64_t)blocks * (uint64_t)g.wrap_rows;
+    }
+    v.cfg.blocks = g.blocks = (int)std::max<long long>(1, blocks);
+    return 0;
+}
+
+// The job's descriptors into the pinned staging buffers, and device buffers for them
+int stage_descriptors(Ctx* c, const Job& job, size_t np, hipStream_t s) {
     const bool duo = job.mode == MODE_DUO;
-    // one long pair on the staged flow3 linear-gap kernel: two half pairs from here on (plan_split)
-    const bool cut = edge == nullptr && plan_split(job, prm);
-    const size_t np = duo ? job.duos.size() : job.pairs.size();
     // staging buffers may still be read by the previous call's async copies
     if (c->staged_pending) {
         HIPCHK(hipEventSynchronize(c->staged));
@@ -871,158 +1163,20 @@ int enqueue(Ctx* c, Job& job, const Params& prm, const unsigned char* d_seq, int
     // a fresh control block holds whatever the allocator recycled: clear the sticky
     // error fields once (afterwards only check_ctrl resets them, after reporting)
     if (c->ctrl.p != ctrl_before) HIPCHK(hipMemsetAsync(c->ctrl.p, 0, sizeof(Ctrl), s));
-    // ring mode: every block resident (one workgroup per CU for flow2), rings sized by the grid
-    // flow2 workgroups per CU: the staged kernel (C2) keeps one (a lone wave per
-    // SIMD: its step latency is the critical path); the streamed kernel of a pair
-    // with many strip groups per CU (C5) is throughput-bound, and more waves per
-    // SIMD hide each other's issue latency (sw_flow2.hip launch_c sizes the LDS pad)
-    const bool f2s = job.mode == MODE_FLOW2 && (job.f2_stream || job.ring || edge != nullptr);
-    int max_m_all = 0;
-    for (const PairDesc& d : job.pairs) max_m_all = std::max(max_m_all, d.m);
-    // Measured (kernel ms, ring | linear edges, 1/2/3/4 per CU):
-    //   N = 2^17 (520 groups)   9.8 9.7 9.6 9.6   | 9.4 10.8 12.5 12.8
-    //   N = 2^18 (1040)         32.4 25.2 26.2 26.4 | 31.7 26.3 34.2 32.1
-    //   N = 2^19 (2080)         116 83.9 80.1 78.9  | 117 83.2 88.5 96.2
-    //   N = 2^20 (4162, C5)     437 312 287 283     | 454 307 299 -
-    // ring: one per 2 CUs' worth of groups, up to 4, or one round of all groups when they fit
-    // (below); three columns per lane: 4 (C5's 1388 groups: 2 / 3 / 4 per CU 159.5 / 156.6 /
-    // 155.6 ms; 694 or 925 blocks 166.4 / 159.3); linear edges: 2 from 4 groups per CU
-    int f2_wgs = 1;
-    if (f2s) {
-        const long long o = g_opt_f2_wgs.load();
-        const int per_cu = job.item_base[np] / c->cus;
-        // a pair per workgroup: every pair resident in one pass when the LDS admits it
-        // (ceil: cus < P < 2 cus needs 2 per CU, not a second pass of P - cus pairs)
-        const int per_cu_ceil = (job.item_base[np] + c->cus - 1) / c->cus;
-        f2_wgs = o > 0           ? (int)o
-                 : job.ring      ? (job.item_base[np] <= c->cus * F2_WGS_MAX || job.f2w3 ? F2_WGS_MAX
-                                                                             : std::min(F2_WGS_MAX, std::max(1, per_cu / 2)))
-                 : job.f3pwg     ? std::min(F2_WGS_MAX, std::max(1, per_cu_ceil))
-                 : job.pwg       ? std::min({F2_WGS_MAX, std::max(1, per_cu_ceil),
-                                             flow2_pwg_wgs(max_m_all, job.C, job.f2w2)})
-                 : per_cu >= 4   ? 2
-                                 : 1;
-    }
-    // G_INIT == G_EXT: the exact linear-gap step (sw_flow2.hip LIN), unless disabled; the
-    // pair-per-workgroup kernel is built with it exactly at two columns per lane
-    const bool f2_lin = job.f3pwg ? prm.gap_init == prm.gap_ext && g_opt_linear.load() != 0
-                      : job.pwg   ? job.f2w2
-                                : ((job.mode == MODE_FLOW2 &&
-                                    (job.C == 32 || job.C == 64 || (job.C == 16 && job.f2w2))) ||
-                                   (job.mode == MODE_DUO && job.duo_f16)) &&
-                                      prm.gap_init == prm.gap_ext && g_opt_linear.load() != 0;
-    // flow3 (sw_flow3.hip, hand-scheduled chunk loops) for the two-column linear-gap launches it
-    // implements: the staged single-pair kernel (C = 16 / 32, rows in LDS: C2) and ring mode (C = 64
-    // / 32, streamed rows, one pair: C5); option f3 = 0 keeps flow2
-    int max_m_f3 = 0;
-    for (const PairDesc& d : job.pairs) max_m_f3 = std::max(max_m_f3, d.m);
-    const bool f3_base = g_opt_f3.load() != 0 && job.mode == MODE_FLOW2 && job.f2w2 && f2_lin && !job.pwg;
-    const bool f3_slab_ok = edge == nullptr || (g_opt_f3slab.load() != 0 && job.C == 64);
-    const bool use_f3 = f3_base && ((!f2s && !job.ring && flow3_fits(max_m_f3, job.C)) ||
-                                    (job.ring && f3_slab_ok && (job.C == 64 || job.C == 32)));
-    // the general affine step (G_INIT != G_EXT, or option linear = 0) on flow3's staged kernel:
-    // one column per lane, rows in LDS, linear edges (C2 with affine constants); option f3a = 0
-    // keeps flow2
-    const bool use_f3a = g_opt_f3a.load() != 0 && job.mode == MODE_FLOW2 && !job.f2w2 && !f2_lin && !job.pwg &&
-                         !f2s && !job.ring && edge == nullptr && (job.C == 32 || job.C == 16) &&
-                         flow3_fits(max_m_f3, job.C, true);
-    // ... and in ring mode at two columns per lane (finalize_mode planned the strips for it)
-    const bool use_f3ra = g_opt_f3a.load() != 0 && job.mode == MODE_FLOW2 && job.f2w2 && !f2_lin && !job.pwg &&
-                          job.ring && f3_slab_ok && job.C == 64;
-    // duo batches at C = 64: strip hand-offs in LDS when the wrap buffer (a round's rows of
-    // both pairs) fits the default dynamic-LDS limit; no boundary buffers in HBM then
-    // and, at 4 or 8 columns per lane, the row codes from an LDS table when both fit two workgroups per CU
-    // and the duos run in one pass at that (C3, 512 duos: 6.80 -> 6.54 ms), or rows are 8192 or more; more
-    // duos of shorter rows keep the table-less kernel, whose smaller LDS admits 4 per CU. With the CU's two
-    // workgroups taking turns at priority (duo_prio) the table wins at 8192 rows: 8192 pairs of 8192
-    // 51.8 -> 50.5 ms, 2048 pairs 13.2 -> 12.6, 4096 pairs of 1024 x 8192 4.59 -> 4.46; it loses at 4096 rows
-    // (4096 pairs of 4096: 7.88 -> 8.03) and on the ragged DB search (17.9 -> 19.7), r05_duo_prio.md
-    int duo_wrap = 0, duo_tab = 0;
-    if (duo && job.C == 64 && g_opt_duo_lds.load() != 0) {
-        int max_mp = 0;
-        for (const DuoDesc& d : job.duos) max_mp = std::max(max_mp, d.m_pad);
-        const int slots = duo_wrap_slots(max_mp);
-        const long long wrap_b = (long long)slots * (f2_lin ? 4 : 8);
-        const int tab_w = DUO_TAB_OFF + max_mp + DUO_TAB_TAIL;
-        const bool one_pass = (long long)job.duos.size() <= 2LL * c->cus || g_opt_duo_tab.load() == 2 || max_mp >= 8192;
-        if (g_opt_duo_tab.load() != 0 && one_pass && job.W % 4 == 0 && wrap_b + 4LL * tab_w + 16 <= duo_lds_fit(f2_lin)) {
-            duo_wrap = slots;
-            duo_tab = tab_w;
-        } else if (wrap_b <= 64 * 1024) {
-            duo_wrap = slots;
-        }
-        if (duo_wrap > 0) job.bnd_granules = 0;
-    }
-    // read once: it sizes the ring arena here and addresses it in the kernel (kp.ring_rows)
-    const long long ring_rows = g_opt_ring_rows.load();
-    int ring_blocks = 0, wrap_rows = 0;
-    if (job.ring) {
-        // the static deal needs every block resident at once: ask the runtime how many
-        // workgroups of the instantiation this launch runs fit a CU (registers, waves and
-        // the LDS pad of f2_wgs), and take no more per CU than that
-        LaunchCfg probe{1, job.C, true, 0, MODE_FLOW2, 0};
-        probe.f2_stream = true;
-        probe.f2_lin = f2_lin;
-        probe.f2_w2 = job.f2w2;
-        probe.f3_hl = use_f3 && job.C == 64 && g_opt_f3rhl.load() != 0;
-        probe.f3ra = use_f3ra;
-        probe.f3_w3 = (use_f3 || use_f3ra) && job.f2w3 && job.w45_s4 < 0;
-        probe.f3_w45 = use_f3 && job.w45_s4 >= 0;
-        probe.f3_slab = (use_f3 || use_f3ra) && edge != nullptr;
-        if (probe.f3_slab) probe.f3_hl = false;
-        probe.hep = job.hep > 0;
-        int fit = 0;
-        for (;; --f2_wgs) {
-            probe.f2_wgs = f2_wgs;
-            fit = use_f3 || use_f3ra ? flow3_ring_resident(probe) : flow2_stream_resident(probe, true, edge != nullptr);
-            if (fit >= f2_wgs || f2_wgs == 1) break;
-        }
-        if (fit < 1) {
-            set_err("flow2 ring mode: the runtime reports %d resident workgroups per CU for its kernel", fit);
-            return -1;
-        }
-        const int items_all = job.item_base[np];
-        ring_blocks = std::min(items_all, c->cus * f2_wgs);
-        if (g_opt_f2_wgs.load() <= 0 && items_all <= c->cus * f2_wgs) {
-            // every group in one round (one block each) when they fit the resident blocks:
-            // a second round of a few groups runs them alone on their SIMDs after the rest.
-            // Measured (column slab 0 alone): 1/8 of C5, 260 groups: 256 blocks (2 rounds)
-            // 51.7 ms -> 260 blocks 42.7 ms; 1/4, 520 groups: 512 blocks 77.8 -> 520 60.8 ms.
-            // More groups than that keep one block per 2 CUs' worth of groups, a multiple of
-            // the CU count (the dispatcher then loads every CU evenly: C5's 2081 groups on
-            // 1024 blocks 181.8 ms, on 1041 blocks at up to 5 per CU 205.7 ms).
-            ring_blocks = items_all;
-            f2_wgs = std::max(1, (items_all + c->cus - 1) / c->cus);
-        }
-        if (g_opt_blocks.load() > 0) ring_blocks = (int)std::min<long long>(g_opt_blocks.load(), job.item_base[np]);
-        if (ring_blocks > c->cus * fit) {
-            set_err("flow2 ring mode needs all %d workgroups co-resident (%d fit per CU, %d CUs)", ring_blocks, fit,
-                    c->cus);
-            return -1;
-        }
-        wrap_rows = 1;
-        while (wrap_rows < job.pairs[0].m) wrap_rows *= 2;
-        job.bnd_granules = (uint64_t)(ring_blocks - 1) * (uint64_t)ring_rows + (uint64_t)wrap_rows;
-        if (c->cons.ensure((size_t)ring_blocks * RING_CONS_STRIDE, s)) return -1;
-        HIPCHK(hipMemsetAsync(c->cons.p, 0, (size_t)ring_blocks * RING_CONS_STRIDE * sizeof(unsigned), s));
-    }
-    int pwg3_blocks = 0;
-    if (job.f3pwg) {
-        // one edge ring per block (a pair's strip edge, >= max m rows); the grid: a block per pair up
-        // to f2_wgs per CU, blocks running further pairs in turn (no block waits on another)
-        if (edge != nullptr || job.ring || !job.f2w3) {
-            set_err("the pair-per-workgroup three-column kernel takes batches only");
-            return -1;
-        }
-        pwg3_blocks = (int)std::min<long long>(np, (long long)c->cus * f2_wgs);
-        if (g_opt_blocks.load() > 0) pwg3_blocks = (int)std::min<long long>(g_opt_blocks.load(), np);
-        wrap_rows = 64;
-        while (wrap_rows < max_m_all) wrap_rows *= 2;
-        job.bnd_granules = (uint64_t)pwg3_blocks * (uint64_t)wrap_rows;
-    }
-    if (duo_wrap > 0 && g_opt_duo_roles.load() != 0) {   // one word per CU (XCC, SE, SH, CU of HW_ID)
-        if (c->cons.ensure(DUO_CU_WORDS, s)) return -1;
-        HIPCHK(hipMemsetAsync(c->cons.p, 0, DUO_CU_WORDS * sizeof(unsigned), s));
+    return 0;
+}
+
+// Device-side state of the launch, in stream order: progress / role words zeroed, the edge arena, the
+// descriptor copies, the control block and the scores zeroed, and a seven-letter ring launch's rows as
+// selectors (m bytes, before the timed kernel)
+int prepare_device(Ctx* c, const Job& job, const Variant& v, const Opts& opt, const unsigned char* d_seq, int* d_scores,
+                   int nscores, size_t np, hipStream_t s) {
+    // ring mode: a consumer progress word per block; duo roles: one word per CU (XCC, SE, SH, CU of HW_ID)
+    const size_t cons = v.ring ? (size_t)v.cfg.blocks * RING_CONS_STRIDE
+                        : v.cfg.duo_wrap > 0 && opt[O_duo_roles] != 0 ? (size_t)DUO_CU_WORDS : 0;
+    if (cons) {
+        if (c->cons.ensure(cons, s)) return -1;
+        HIPCHK(hipMemsetAsync(c->cons.p, 0, cons * sizeof(unsigned), s));
     }
     if (job.bnd_granules) {
         size_t freeb = 0, totb = 0;
@@ -1034,176 +1188,14 @@ int enqueue(Ctx* c, Job& job, const Params& prm, const unsigned char* d_seq, int
         }
         if (c->bnd.ensure(job.bnd_granules, s)) return -1;
     }
-    if (duo) HIPCHK(hipMemcpyAsync(c->duo.p, c->hduo.p, np * sizeof(DuoDesc), hipMemcpyHostToDevice, s));
+    if (job.mode == MODE_DUO) HIPCHK(hipMemcpyAsync(c->duo.p, c->hduo.p, np * sizeof(DuoDesc), hipMemcpyHostToDevice, s));
     else HIPCHK(hipMemcpyAsync(c->desc.p, c->hdesc.p, np * sizeof(PairDesc), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(c->ibase.p, c->hibase.p, (np + 1) * sizeof(int), hipMemcpyHostToDevice, s));
     HIPCHK(hipEventRecord(c->staged, s));
     c->staged_pending = true;
     HIPCHK(hipMemsetAsync(c->ctrl.p, 0, sizeof(unsigned), s));   // next_item only; error stays sticky
     HIPCHK(hipMemsetAsync(d_scores, 0, (size_t)nscores * sizeof(int), s));
-
-    int max_m = 0;
-    for (const PairDesc& d : job.pairs) max_m = std::max(max_m, d.m);
-    LaunchCfg cfg{job.W, job.C, job.dna, 0, job.mode, max_m};
-    cfg.duo_f16 = job.mode == MODE_DUO && job.duo_f16;
-    // flow2 ring and slab kernels always stream the row codes (sw_flow2.hip launch_v)
-    cfg.f2_stream = f2s;
-    cfg.f2_wgs = f2_wgs;
-    cfg.f2_lin = f2_lin;
-    cfg.f2_w2 = job.mode == MODE_FLOW2 && job.f2w2;
-    cfg.f2_pwg = job.mode == MODE_FLOW2 && job.pwg;
-    // the staged two-column linear-gap kernel with hand-scheduled chunk loops (sw_flow3.hip), unless
-    // option f3 = 0: C2
-    cfg.f3 = use_f3;
-    cfg.f3_hl = use_f3 && ((!job.ring && job.C == 32 && g_opt_f3hl.load() != 0) ||
-                           (job.ring && job.C == 64 && g_opt_f3rhl.load() != 0));
-    cfg.f3a = use_f3a;
-    cfg.f3ra = use_f3ra;
-    cfg.f3_slab = (use_f3 || use_f3ra) && edge != nullptr;
-    if (cfg.f3_slab) cfg.f3_hl = false;   // (the slab roles exist at C = 64, whole-chunk links)
-    if (use_f3a) cfg.f3_hl = job.C == 32 && g_opt_f3hl.load() != 0;
-    // the pool loops (no I/O rotation, tools/gen_flow3.py gen_pool) for staged launches with
-    // half-chunk links at C = 32, both steps, when option f3pool = 1 (default 0: measured slower)
-    cfg.f3p = g_opt_f3pool.load() != 0 && cfg.f3_hl && job.C == 32 && !job.ring && (use_f3 || use_f3a);
-    cfg.f3_w3 = job.f2w3 && job.w45_s4 < 0;
-    cfg.f3_w45 = job.w45_s4 >= 0;
-    cfg.hep = job.hep > 0;
-    if (cfg.hep && !((use_f3 && !f2s && !job.ring) || use_f3a ||
-                     ((use_f3 || use_f3ra) && job.ring && cfg.f3_w3 && edge == nullptr && !job.f3pwg))) {
-        set_err("a seven-letter alphabet runs flow3's staged kernels or its three-column ring kernels only (one pair)");
-        return -1;
-    }
-    cfg.f3_pwg = job.f3pwg;
-    if (job.f3pwg) {   // the linear-gap ring step, or the affine one (sw_flow3ra3p_kernel)
-        cfg.f3 = f2_lin;
-        cfg.f3ra = !f2_lin;
-    }
-    if (cfg.f3_w45 && !(use_f3 && job.ring && edge == nullptr)) {
-        set_err("four / five columns per lane run on flow3's linear-gap ring kernel only (one pair, not a slab)");
-        return -1;
-    }
-    if (job.f2w3 && !job.f3pwg && !((use_f3 || use_f3ra) && job.ring && job.C == 64 && !cfg.f3_hl)) {
-        set_err("three columns per lane run on flow3's ring kernel only (linear-gap step, C = 64, whole-chunk links)");
-        return -1;
-    }
-    cfg.duo_wrap = duo_wrap;
-    cfg.duo_tab = duo_tab;
-    if (cut && !(cfg.f3 && !cfg.f3p && !cfg.f3a && !f2s && !job.ring)) {
-        set_err("internal: a pair was cut at a column for a launch that is not flow3's staged linear-gap kernel");
-        return -1;
-    }
-    if (cfg.f2_w2 && job.C == 16 && !use_f3) {
-        set_err("flow2: two columns per lane at C = 16 runs on flow3 only (rows staged in LDS, one GPU)");
-        return -1;
-    }
-    if (cfg.f2_w2 && !f2_lin && !use_f3ra && !job.f3pwg) {   // the strips were cut for two columns per lane
-        set_err("flow2: two columns per lane needs the linear-gap step (or flow3's affine ring kernel)");
-        return -1;
-    }
-    const int wpc = waves_per_cu(c, cfg);
-    const int items = job.item_base[np];
-    long long blocks = g_opt_blocks.load();
-    if (blocks <= 0) {
-        const int wpb = job.mode == MODE_DUO ? DUO_WAVES : 4;   // waves per workgroup
-        const long long cap = (long long)c->cus * std::max(1, wpc / wpb);
-        // strip mode: 4 independent waves per block; chain: one block per group;
-        // pair-per-workgroup: one block per pair (grid-stride over pairs)
-        const long long want = job.mode == MODE_STRIP ? (items + 3) / 4 : grouped_mode(job.mode) ? items : (long long)np;   // pairwg/duo: np workgroups
-        blocks = std::min<long long>(want, cap);
-        // flow2 holds one workgroup per CU (its LDS size forces it); a grid larger than
-        // the CU count would only park extra workgroups until a CU frees up
-        if (job.mode == MODE_FLOW2) blocks = std::min<long long>(blocks, (long long)c->cus * f2_wgs);
-    }
-    if (job.ring) blocks = ring_blocks;   // checked co-resident above
-    if (job.f3pwg) blocks = pwg3_blocks;
-    cfg.blocks = (int)std::max<long long>(1, blocks);
-
-    KParams kp{};
-    kp.seq = d_seq;
-    kp.pairs = c->desc.p;
-    kp.duos = c->duo.p;
-    kp.item_base = c->ibase.p;
-    kp.bnd = c->bnd.p;
-    kp.ctrl = c->ctrl.p;
-    kp.scores = d_scores;
-    kp.npairs = (int)np;
-    kp.total_items = items;
-    // epochs are never 0 (tag of a zeroed granule), nor one that makes flow3's granule key
-    // k = epoch ^ 0x5BD1E995 zero in its low 5 bits: a zeroed 8-B granule passes its check when
-    // its second word equals k (staged) or k ^ (position << 5) (ring edges), which needs exactly that;
-    // the affine granules' E half is keyed k ^ 0x9E3779B9, held to the same rule
-    do ++c->epoch;
-    while (c->epoch == 0 || ((c->epoch ^ 0x5BD1E995u) & 31u) == 0 || ((c->epoch ^ 0x5BD1E995u ^ 0x9E3779B9u) & 31u) == 0);
-    kp.epoch = c->epoch;
-    kp.match = prm.match;
-    kp.mismatch = prm.mismatch;
-    kp.gap_init = prm.gap_init;
-    kp.gap_ext = prm.gap_ext;
-    profile_words(prm, kp.prof);
-    for (int q = 0; q < 4; ++q) {   // flow2: signed bytes s(q, r) + G_INIT
-        unsigned w = 0;
-        for (int r = 0; r < 4; ++r) w |= (unsigned)(((r == q ? prm.match : prm.mismatch) + prm.gap_init) & 0xFF) << (8 * r);
-        kp.prof2[q] = w;
-    }
-    for (int q = 0; q < 4; ++q) {   // flow2 W2 column B: signed bytes s(q, r)
-        unsigned w = 0;
-        for (int r = 0; r < 4; ++r) w |= (unsigned)((r == q ? prm.match : prm.mismatch) & 0xFF) << (8 * r);
-        kp.prof3[q] = w;
-    }
-    if (cfg.hep) {   // seven-letter alphabet: per column symbol c, row symbols 0..3 high, 4..6 low (sw_flow3.hip HEP)
-        std::memcpy(kp.hsym, job.hsym, sizeof kp.hsym);
-        for (int c = 0; c < 7; ++c) {
-            unsigned p2 = 0, q2 = 0x80u, p3 = 0, q3 = 0x80u;
-            for (int r = 0; r < 7; ++r) {
-                const int sc = r == c ? prm.match : prm.mismatch;
-                const unsigned b2 = (unsigned)((sc + prm.gap_init) & 0xFF), b3 = (unsigned)(sc & 0xFF);
-                if (r < 4) {
-                    p2 |= b2 << (8 * r);
-                    p3 |= b3 << (8 * r);
-                } else {
-                    q2 |= b2 << (8 * (r - 3));
-                    q3 |= b3 << (8 * (r - 3));
-                }
-            }
-            kp.hp2[c] = p2;
-            kp.hq2[c] = q2;
-            kp.hp3[c] = p3;
-            kp.hq3[c] = q3;
-        }
-    }
-    for (int q = 0; q < 4; ++q) {   // duo: penalty bytes MATCH - s(r, q)
-        unsigned w = 0;
-        for (int r = 0; r < 4; ++r) w |= (unsigned)(r == q ? 0 : prm.match - prm.mismatch) << (8 * r);
-        kp.pen[q] = w;
-    }
-    if (duo_wrap > 0) {
-        kp.wrap_rows = duo_wrap;
-        if (g_opt_duo_roles.load() != 0) kp.ring_cons = c->cons.p;   // per-CU role words (zeroed above)
-        // auto (-1): turn-taking in 1.3 ms slices whenever the LDS row-code table is used.  That is the
-        // one-pass batches (one duo per workgroup: the CU's two workgroups would otherwise end ~3 ms
-        // apart, C3 6.48 -> 6.30 ms) and, since the table also serves multi-pass batches of rows >= 8192,
-        // those too (8192 pairs of 8192: 51.8 -> 50.5 ms with table + turns); the table-less kernel runs
-        // without turns (profiles/r05_duo_prio.md)
-        const int dp = (int)g_opt_duo_prio.load();
-        kp.duo_prio = dp >= 0 ? dp : cfg.duo_tab > 0 ? 17 : 0;
-    }
-    kp.timeout_ticks = g_opt_timeout.load() * 100000000LL;   // s_memrealtime: 100 MHz
-    kp.stall_item = (int)g_opt_stall_item.load();
-    kp.w45_s4 = cfg.f3_w45 ? job.w45_s4 : -1;
-    kp.trace = reinterpret_cast<unsigned long long*>(g_opt_trace.load());
-    if (job.ring) {
-        kp.ring_rows = (int)ring_rows;
-        kp.wrap_rows = wrap_rows;
-        kp.ring_cons = c->cons.p;
-    }
-    if (job.f3pwg) kp.wrap_rows = wrap_rows;   // each block's edge ring (kp.ring_rows stays 0)
-    if (edge) {   // (flow2 then runs its slab kernel, which streams the row codes)
-        kp.slab_in = edge->in;
-        kp.slab_out = edge->out;
-        kp.slab_epoch = edge->epoch;
-    }
-
-    if (cfg.hep && job.ring) {   // the rows as selectors, once per launch (m bytes, before the timed kernel)
+    if (v.cfg.hep && v.ring) {
         const PairDesc& d = job.pairs[0];
         if (c->hrows.ensure((size_t)d.m, s)) return -1;
         HepSel t{};
@@ -1214,12 +1206,129 @@ int enqueue(Ctx* c, Job& job, const Params& prm, const unsigned char* d_seq, int
         hipLaunchKernelGGL(hep_rows_kernel, dim3((unsigned)std::min(1024, (d.m + 255) / 256)), dim3(256), 0, s,
                            d_seq + d.row_off, d.m, c->hrows.p, t);
         HIPCHK(hipGetLastError());
-        kp.hrows = c->hrows.p;
     }
+    return 0;
+}
+
+// The score words of the kernels' profile lookups: pure functions of the constants and, for a
+// seven-letter alphabet, of the byte-to-symbol map (hsym, else null)
+void fill_score_words(KParams& kp, const Params& prm, const unsigned char* hsym) {
+    kp.match = prm.match;
+    kp.mismatch = prm.mismatch;
+    kp.gap_init = prm.gap_init;
+    kp.gap_ext = prm.gap_ext;
+    profile_words(prm, kp.prof);
+    for (int q = 0; q < 4; ++q) {
+        unsigned w2 = 0, w3 = 0, pen = 0;
+        for (int r = 0; r < 4; ++r) {
+            const int sc = r == q ? prm.match : prm.mismatch;
+            w2 |= (unsigned)((sc + prm.gap_init) & 0xFF) << (8 * r);
+            w3 |= (unsigned)(sc & 0xFF) << (8 * r);
+            pen |= (unsigned)(prm.match - sc) << (8 * r);
+        }
+        kp.prof2[q] = w2;   // flow2: signed bytes s(q, r) + G_INIT
+        kp.prof3[q] = w3;   // flow2 W2 column B: signed bytes s(q, r)
+        kp.pen[q] = pen;    // duo: penalty bytes MATCH - s(r, q)
+    }
+    if (!hsym) return;
+    // seven-letter alphabet: per column symbol c, row symbols 0..3 high, 4..6 low (sw_flow3.hip HEP)
+    std::memcpy(kp.hsym, hsym, sizeof kp.hsym);
+    for (int c = 0; c < 7; ++c) {
+        unsigned p2 = 0, q2 = 0x80u, p3 = 0, q3 = 0x80u;
+        for (int r = 0; r < 7; ++r) {
+            const int sc = r == c ? prm.match : prm.mismatch;
+            const unsigned b2 = (unsigned)((sc + prm.gap_init) & 0xFF), b3 = (unsigned)(sc & 0xFF);
+            if (r < 4) {
+                p2 |= b2 << (8 * r);
+                p3 |= b3 << (8 * r);
+            } else {
+                q2 |= b2 << (8 * (r - 3));
+                q3 |= b3 << (8 * (r - 3));
+            }
+        }
+        kp.hp2[c] = p2;
+        kp.hq2[c] = q2;
+        kp.hp3[c] = p3;
+        kp.hq3[c] = q3;
+    }
+}
+
+KParams fill_kparams(Ctx* c, const Job& job, const Variant& v, const Grid& g, const Params& prm, const Opts& opt,
+                     const unsigned char* d_seq, int* d_scores, size_t np, const SlabEdge* edge) {
+    KParams kp{};
+    kp.seq = d_seq;
+    kp.pairs = c->desc.p;
+    kp.duos = c->duo.p;
+    kp.item_base = c->ibase.p;
+    kp.bnd = c->bnd.p;
+    kp.ctrl = c->ctrl.p;
+    kp.scores = d_scores;
+    kp.npairs = (int)np;
+    kp.total_items = job.item_base[np];
+    // epochs are never 0 (tag of a zeroed granule), nor one that makes flow3's granule key
+    // k = epoch ^ 0x5BD1E995 zero in its low 5 bits: a zeroed 8-B granule passes its check when
+    // its second word equals k (staged) or k ^ (position << 5) (ring edges), which needs exactly that;
+    // the affine granules' E half is keyed k ^ 0x9E3779B9, held to the same rule
+    do ++c->epoch;
+    while (c->epoch == 0 || ((c->epoch ^ 0x5BD1E995u) & 31u) == 0 || ((c->epoch ^ 0x5BD1E995u ^ 0x9E3779B9u) & 31u) == 0);
+    kp.epoch = c->epoch;
+    fill_score_words(kp, prm, v.cfg.hep ? job.hsym : nullptr);
+    if (v.cfg.duo_wrap > 0) {
+        kp.wrap_rows = v.cfg.duo_wrap;
+        if (opt[O_duo_roles] != 0) kp.ring_cons = c->cons.p;   // per-CU role words (zeroed by prepare_device)
+        // auto (-1): turn-taking in 1.3 ms slices whenever the LDS row-code table is used.  That is the
+        // one-pass batches (one duo per workgroup: the CU's two workgroups would otherwise end ~3 ms
+        // apart, C3 6.48 -> 6.30 ms) and, since the table also serves multi-pass batches of rows >= 8192,
+        // those too (8192 pairs of 8192: 51.8 -> 50.5 ms with table + turns); the table-less kernel runs
+        // without turns (profiles/r05_duo_prio.md)
+        const int dp = (int)opt[O_duo_prio];
+        kp.duo_prio = dp >= 0 ? dp : v.cfg.duo_tab > 0 ? 17 : 0;
+    }
+    kp.timeout_ticks = opt[O_timeout] * 100000000LL;   // s_memrealtime: 100 MHz
+    kp.stall_item = (int)opt[O_stall_item];
+    kp.w45_s4 = v.cfg.f3_w45 ? job.w45_s4 : -1;
+    kp.trace = reinterpret_cast<unsigned long long*>(opt[O_trace]);
+    if (v.ring) {   // the ring arena is sized (size_ring) and addressed with the one snapshot's ring_rows
+        kp.ring_rows = (int)opt[O_ring_rows];
+        kp.wrap_rows = g.wrap_rows;
+        kp.ring_cons = c->cons.p;
+    }
+    if (job.f3pwg) kp.wrap_rows = g.wrap_rows;   // each block's edge ring (kp.ring_rows stays 0)
+    if (v.cfg.hep && v.ring) kp.hrows = c->hrows.p;
+    if (edge) {   // (flow2 then runs its slab kernel, which streams the row codes)
+        kp.slab_in = edge->in;
+        kp.slab_out = edge->out;
+        kp.slab_epoch = edge->epoch;
+    }
+    return kp;
+}
+
+// Enqueue the launch for a planned job whose sequences are in `d_seq`: decide the variant, size the grid,
+// stage, launch, record the stats.  edge: the job is a column slab (plan_slab), these are its edges.
+int enqueue(Ctx* c, Job& job, const Params& prm, const Opts& opt, const unsigned char* d_seq, int* d_scores, int nscores,
+            hipStream_t s, bool time_kernel, const SlabEdge* edge = nullptr) {
+    if (job.mode == MODE_FLOW2 ? !flow2_variant_exists(job.C) : !variant_exists(job.W, job.C)) {
+        set_err("no kernel variant for W=%d C=%d", job.W, job.C);
+        return -1;
+    }
+    // one long pair on the staged flow3 linear-gap kernel: two half pairs from here on
+    plan_split(job, prm, opt, c->cus);
+    Variant v = select_variant(job, prm, opt, c->cus);
+    if (v.err) {
+        set_err("%s", v.err);
+        return -1;
+    }
+    const size_t np = job.mode == MODE_DUO ? job.duos.size() : job.pairs.size();
+    Grid g;
+    if (stage_descriptors(c, job, np, s) || size_grid(c, job, v, opt, np, g) ||
+        prepare_device(c, job, v, opt, d_seq, d_scores, nscores, np, s))
+        return -1;
+    const KParams kp = fill_kparams(c, job, v, g, prm, opt, d_seq, d_scores, np, edge);
+
     if (time_kernel) HIPCHK(hipEventRecord(c->ev0, s));
-    HIPCHK(cfg.f3 || cfg.f3a || cfg.f3ra ? launch_sw_flow3(cfg, kp, s)
-           : job.mode == MODE_FLOW2 ? launch_sw_flow2(cfg, kp, s) : launch_sw_strip(cfg, kp, s));
-    if (cut) {   // the crossing term from the halves' final edges (inside the timed span)
+    HIPCHK(v.cfg.f3 || v.cfg.f3a || v.cfg.f3ra ? launch_sw_flow3(v.cfg, kp, s)
+           : job.mode == MODE_FLOW2           ? launch_sw_flow2(v.cfg, kp, s) : launch_sw_strip(v.cfg, kp, s));
+    if (v.cut) {   // the crossing term from the halves' final edges (inside the timed span)
         const PairDesc& l = job.pairs[0];
         const PairDesc& r = job.pairs[1];
         const Granule* gl = c->bnd.p + l.bnd_off + (uint64_t)((l.strips + 3) / 4 - 1) * (uint64_t)l.m;
@@ -1233,15 +1342,11 @@ int enqueue(Ctx* c, Job& job, const Params& prm, const unsigned char* d_seq, int
     t_stats.W = job.W;
     t_stats.C = job.C;
     t_stats.dna = job.hep ? 2 : job.dna ? 1 : 0;   // 2: a seven-letter alphabet on the DNA kernels
-    t_stats.blocks = cfg.blocks;
-    t_stats.waves_per_cu = wpc;
-    t_stats.items = items;
+    t_stats.blocks = v.cfg.blocks;
+    t_stats.waves_per_cu = g.wpc;
+    t_stats.items = job.item_base[np];
     t_stats.mode = job.mode;
-    t_stats.variant = (cfg.duo_f16 ? 1 : 0) | (cfg.f2_stream ? 2 : 0) | (job.ring ? 4 : 0) | (cfg.f2_lin ? 8 : 0) |
-                      (cfg.f2_w2 ? 16 : 0) | (cfg.f2_pwg ? 32 : 0) | (cfg.f3 ? 64 : 0) | (cfg.duo_wrap > 0 ? 128 : 0) |
-                      (cfg.duo_tab > 0 ? 256 : 0) | (cfg.f3_hl ? 512 : 0) | (cfg.f3a || cfg.f3ra ? 1024 : 0) |
-                      (cfg.f3_slab ? 2048 : 0) | (cfg.f3p ? 4096 : 0) | (cfg.f3_w3 ? 8192 : 0) |
-                      (cfg.f3_w45 ? 16384 : 0) | (cfg.f3_pwg ? 32768 : 0) | (cfg.hep ? 65536 : 0) | (cut ? 1 << 17 : 0);
+    t_stats.variant = variant_word(v);
     t_stats.boundary_bytes = (long long)(job.bnd_granules * sizeof(Granule));
     c->last = s;
     return 0;
@@ -1298,13 +1403,13 @@ int check_host_pairs(const HostPair* in, int npairs, const Params& prm) {
 // Stage the non-empty pairs in[act[i]] and launch them on c's own stream (asynchronous).
 // Pair act[i]'s score goes to d_scores[full ? act[i] : i]; enqueue zeroes the nscores
 // ints of d_scores first, so empty pairs of a full-index launch read 0.
-int launch_host(Ctx* c, const HostPair* in, const std::vector<int>& act, const Params& prm, int* d_scores,
-                int nscores, bool full) {
+int launch_host(Ctx* c, const HostPair* in, const std::vector<int>& act, const Params& prm, const Opts& opt,
+                int* d_scores, int nscores, bool full) {
     hipStream_t s = c->own;
     if (c->last && c->last != s) HIPCHK(hipStreamSynchronize(c->last));
     Job job;
     const bool single = act.size() == 1;
-    bool dna = g_opt_bytes.load() == 0;
+    bool dna = opt[O_bytes] == 0;
     size_t bytes = 0;
     for (int k : act) {
         if (dna && !(all_dna(in[k].s1, in[k].n) && all_dna(in[k].s2, in[k].m))) dna = false;
@@ -1319,7 +1424,7 @@ int launch_host(Ctx* c, const HostPair* in, const std::vector<int>& act, const P
     job.pairs.resize(act.size());
     for (size_t i = 0; i < act.size(); ++i) {
         const HostPair& p = in[act[i]];
-        const bool swap = want_swap(single, p.n, p.m);
+        const bool swap = want_swap(opt, single, p.n, p.m);
         const unsigned char* colp = swap ? p.s2 : p.s1;
         const unsigned char* rowp = swap ? p.s1 : p.s2;
         const int n = swap ? p.m : p.n, m = swap ? p.n : p.m;
@@ -1334,23 +1439,24 @@ int launch_host(Ctx* c, const HostPair* in, const std::vector<int>& act, const P
         d.m = m;
         d.out_idx = full ? act[i] : (int)i;
     }
-    if (!dna && single && g_opt_bytes.load() == 0) {
+    if (!dna && single && opt[O_bytes] == 0) {
         uint32_t set[8] = {};
         byte_set(in[act[0]].s1, in[act[0]].n, set);
         byte_set(in[act[0]].s2, in[act[0]].m, set);
-        set_hep(job, set);
+        set_hep(job, opt, set);
     }
-    const int W = pick_W(job.pairs, single);
-    plan(job, W, pick_C(W), single);
-    if (finalize_alphabet(job, prm, c->cus, single)) return -1;
+    const int W = pick_W(opt, job.pairs, single);
+    plan(opt, job, W, pick_C(opt, W), single);
+    if (finalize_alphabet(job, prm, opt, c->cus, single)) return -1;
     if (c->seq.ensure(bytes, s)) return -1;
     HIPCHK(hipMemcpyAsync(c->seq.p, c->hseq.p, bytes, hipMemcpyHostToDevice, s));
-    return enqueue(c, job, prm, c->seq.p, d_scores, nscores, s, true);
+    return enqueue(c, job, prm, opt, c->seq.p, d_scores, nscores, s, true);
 }
 
 // Synchronous host-buffer path shared by every host API entry.
 int score_host(const HostPair* in, int npairs, const Params& prm, int* out) {
     const auto t0 = std::chrono::steady_clock::now();
+    const Opts opt = snapshot_opts();
     if (npairs > 0 && !out) {
         set_err("invalid arguments");
         return -1;
@@ -1366,7 +1472,7 @@ int score_host(const HostPair* in, int npairs, const Params& prm, int* out) {
     if (!c) return -1;
     hipStream_t s = c->own;
     if (c->scores.ensure(act.size(), s) || c->hscores.ensure(act.size())) return -1;
-    if (launch_host(c, in, act, prm, c->scores.p, (int)act.size(), false)) return -1;
+    if (launch_host(c, in, act, prm, opt, c->scores.p, (int)act.size(), false)) return -1;
     HIPCHK(hipMemcpyAsync(c->hscores.p, c->scores.p, act.size() * sizeof(int), hipMemcpyDeviceToHost, s));
     if (check_ctrl(c, s)) return -1;   // synchronises
     float ms = 0.f;
@@ -1379,7 +1485,7 @@ int score_host(const HostPair* in, int npairs, const Params& prm, int* out) {
 
 // One device's shard of a multi-GPU batch (sw_score_batch_multi): the scores of
 // in[0..npairs) stay in device memory, *d_out (npairs ints of this thread's context).
-int score_host_device(const HostPair* in, int npairs, const Params& prm, int** d_out, float* kernel_ms) {
+int score_host_device(const HostPair* in, int npairs, const Params& prm, const Opts& opt, int** d_out, float* kernel_ms) {
     *kernel_ms = 0.f;
     Ctx* c = get_ctx();
     if (!c) return -1;
@@ -1394,7 +1500,7 @@ int score_host_device(const HostPair* in, int npairs, const Params& prm, int** d
         HIPCHK(hipStreamSynchronize(s));
         return 0;
     }
-    if (launch_host(c, in, act, prm, c->scores.p, npairs, true)) return -1;
+    if (launch_host(c, in, act, prm, opt, c->scores.p, npairs, true)) return -1;
     if (check_ctrl(c, s)) return -1;   // synchronises
     HIPCHK(hipEventElapsedTime(kernel_ms, c->ev0, c->ev1));
     return 0;
@@ -1594,6 +1700,7 @@ int score_multi(const HostPair* in, int npairs, const Params& prm, int* out, int
     }
     if (check_host_pairs(in, npairs, prm)) return -1;
     if (npairs == 0) return 0;
+    const Opts opt = snapshot_opts();   // one for every device's worker
     MultiState& st = multi_state();
     std::lock_guard<std::mutex> g(st.mu);
     if (ngpus > 1 && !st.rccl.load()) {
@@ -1617,7 +1724,7 @@ int score_multi(const HostPair* in, int npairs, const Params& prm, int* out, int
                 errs[r] = "hipSetDevice failed";
                 return;
             }
-            rc[r] = score_host_device(in + off[r], cnt[r], prm, &dptr[r], &kms[r]);
+            rc[r] = score_host_device(in + off[r], cnt[r], prm, opt, &dptr[r], &kms[r]);
             if (rc[r]) errs[r] = t_err;
         });
     }
@@ -1806,6 +1913,7 @@ int sw_score_batch_device(const unsigned char* d_arena, const int64_t* a_off, co
         return -1;
     }
     const Params prm = current_params();
+    const Opts opt = snapshot_opts();
     if (!params_ok(prm)) return -1;
     Ctx* c = get_ctx();
     if (!c) return -1;
@@ -1832,7 +1940,7 @@ int sw_score_batch_device(const unsigned char* d_arena, const int64_t* a_off, co
     const bool single = idx.size() == 1;
     for (size_t i = 0; i < idx.size(); ++i) {
         const int k = idx[i];
-        const bool swap = want_swap(single, alen[k], blen[k]);
+        const bool swap = want_swap(opt, single, alen[k], blen[k]);
         PairDesc& d = job.pairs[i];
         d.col_off = (uint64_t)(swap ? b_off[k] : a_off[k]);
         d.row_off = (uint64_t)(swap ? a_off[k] : b_off[k]);
@@ -1845,9 +1953,9 @@ int sw_score_batch_device(const unsigned char* d_arena, const int64_t* a_off, co
         if (!stream) HIPCHK(hipStreamSynchronize(s));
         return 0;
     }
-    const int W = pick_W(job.pairs, single);
-    plan(job, W, pick_C(W), single);
-    if (flags & SW_FLAG_BYTES || g_opt_bytes.load()) {
+    const int W = pick_W(opt, job.pairs, single);
+    plan(opt, job, W, pick_C(opt, W), single);
+    if (flags & SW_FLAG_BYTES || opt[O_bytes]) {
         job.dna = false;
     } else if (flags & SW_FLAG_DNA) {
         job.dna = true;
@@ -1859,7 +1967,7 @@ int sw_score_batch_device(const unsigned char* d_arena, const int64_t* a_off, co
             c->staged_pending = false;
         }
         // (one pair: the byte set too, for the seven-letter path)
-        const int set = single && g_opt_hep.load() != 0 ? 1 : 0;
+        const int set = single && opt[O_hep] != 0 ? 1 : 0;
         // (the pinned control block, 3 x 16 B, takes the flag and the byte set back)
         if (c->hdesc.ensure(np) || c->desc.ensure(np, s) || c->flag.ensure(9, s) || c->hctrl.ensure(3)) return -1;
         std::memcpy(c->hdesc.p, job.pairs.data(), np * sizeof(PairDesc));
@@ -1879,11 +1987,11 @@ int sw_score_batch_device(const unsigned char* d_arena, const int64_t* a_off, co
         if (!job.dna && set) {
             uint32_t bits[8];
             std::memcpy(bits, hflag + 1, sizeof bits);
-            set_hep(job, bits);
+            set_hep(job, opt, bits);
         }
     }
-    if (finalize_alphabet(job, prm, c->cus, single)) return -1;
-    if (enqueue(c, job, prm, d_arena, d_scores, npairs, s, !stream)) return -1;
+    if (finalize_alphabet(job, prm, opt, c->cus, single)) return -1;
+    if (enqueue(c, job, prm, opt, d_arena, d_scores, npairs, s, !stream)) return -1;
     if (!stream) {
         if (check_ctrl(c, s)) return -1;
         float ms = 0.f;
@@ -1899,10 +2007,11 @@ int sw_slab_bounds(long long n, int m, int nslabs, int flags, long long* bounds)
         set_err("sw_slab_bounds: invalid arguments");
         return -1;
     }
+    const Opts opt = snapshot_opts();
     bool dna = true;
-    if (slab_dna(flags, &dna)) return -1;
+    if (slab_dna(opt, flags, &dna)) return -1;
     Job job;
-    const int q = plan_slab(job, (int)n, m, dna, current_params());   // the quantum does not depend on n
+    const int q = plan_slab(job, (int)n, m, dna, current_params(), opt);   // the quantum does not depend on n
     if (q < 0) return -1;
     const long long per = n / nslabs / q * q;
     if (nslabs > 1 && per == 0) {
@@ -1937,8 +2046,9 @@ int sw_score_slab_device(const unsigned char* d_arena, int64_t col_off, int n, i
         set_err("sw_score_slab_device: epoch 0 is the tag of a never-written granule");
         return -1;
     }
+    const Opts opt = snapshot_opts();
     bool dna = true;
-    if (slab_dna(flags, &dna)) return -1;
+    if (slab_dna(opt, flags, &dna)) return -1;
     const Params prm = current_params();
     if (!params_ok(prm)) return -1;
     // H of any cell is at most MATCH * (its row), whatever the slab's column range
@@ -1955,7 +2065,7 @@ int sw_score_slab_device(const unsigned char* d_arena, int64_t col_off, int n, i
     hipStream_t s = stream ? (hipStream_t)stream : c->own;
     if (c->last && c->last != s) HIPCHK(hipStreamSynchronize(c->last));
     Job job;
-    const int q = plan_slab(job, n, m, dna, prm);
+    const int q = plan_slab(job, n, m, dna, prm, opt);
     if (q < 0) return -1;
     if (d_outflow && n % q != 0) {
         set_err("a slab with an outflow edge must be a multiple of %d columns (sw_slab_bounds), got %d", q, n);
@@ -1964,7 +2074,7 @@ int sw_score_slab_device(const unsigned char* d_arena, int64_t col_off, int n, i
     job.pairs[0].col_off = (uint64_t)col_off;
     job.pairs[0].row_off = (uint64_t)row_off;
     const SlabEdge edge{static_cast<Granule*>(d_inflow), static_cast<Granule*>(d_outflow), epoch};
-    if (enqueue(c, job, prm, d_arena, d_score, 1, s, !stream, &edge)) return -1;
+    if (enqueue(c, job, prm, opt, d_arena, d_score, 1, s, !stream, &edge)) return -1;
     if (!stream) {
         if (check_ctrl(c, s)) return -1;
         float ms = 0.f;
@@ -1986,7 +2096,7 @@ int sw_slab_alloc(int m, void** d_buf, void* ipc_handle) {
     // inflow of a cross-GPU slab edge: it must be fine-grained, and the plain-memory
     // fallback is refused unless option slab_plain = 1 (one-GPU tests only); a buffer
     // of this process alone may fall back to plain device memory.
-    const int last_kind = ipc_handle && !g_opt_slab_plain.load() ? 1 : 2;
+    const int last_kind = ipc_handle && !sw_get_option("slab_plain") ? 1 : 2;
     for (int kind = 1; kind <= last_kind; ++kind) {
         void* p = nullptr;
         const hipError_t e = kind == 1 ? hipExtMallocWithFlags(&p, bytes, hipDeviceMallocFinegrained)
@@ -2064,151 +2174,23 @@ int sw_stream_status(void* stream) {
 
 int sw_set_option(const char* key, long long v) {
     if (!key) return -1;
-    const std::string k(key);
-    if (k == "W") {
-        if (v != 0 && v != 1 && v != 2 && v != 4 && v != 8) return -1;
-        g_opt_W = v;
-    } else if (k == "C") {
-        if (v != 0 && v != 16 && v != 32 && v != 64) return -1;
-        g_opt_C = v;
-    } else if (k == "bytes") {
-        g_opt_bytes = v ? 1 : 0;
-    } else if (k == "timeout") {
-        if (v < 1 || v > 3600) return -1;
-        g_opt_timeout = v;
-    } else if (k == "f3pwg") {   // 1 (default): int32 batches on flow3's three-column ring step, a pair per
-        // workgroup (sw_flow3r3p_kernel, affine: sw_flow3ra3p_kernel); 0: flow2's pair-per-workgroup kernel
-        g_opt_f3pwg = v ? 1 : 0;
-    } else if (k == "hep") {   // 1 (default): one pair over up to seven byte values on flow3's staged kernels, 0: byte path
-        if (v < 0 || v > 1) return -1;
-        g_opt_hep = v;
-    } else if (k == "duo_raw") {   // 1 (default): byte batches on the duo kernels (RAW penalty), 0: byte strip kernels
-        if (v < 0 || v > 1) return -1;
-        g_opt_duo_raw = v;
-    } else if (k == "f3split") {   // one pair on flow3's staged linear-gap kernel cut at a column and scored from both
-        // ends: -1 auto (pairs of F3_SPLIT_AUTO_N columns or more), 0 off, 1 whenever each half gets two strips
-        if (v < -1 || v > 1) return -1;
-        g_opt_f3split = v;
-    } else if (k == "stall_item") {   // tests only: flow2's compute waves skip this item (-1 = none)
-        if (v < -1) return -1;
-        g_opt_stall_item = v;
-    } else if (k == "blocks") {
-        if (v < 0) return -1;
-        g_opt_blocks = v;
-    } else if (k == "trace") {   // device buffer of 4 u64 per strip (tools only), 0 = off
-        g_opt_trace = v;
-    } else if (k == "trace_mb") {   // MiB of trace memory a traced matrix launch may hold (sw_matrix.hip)
-        if (v < 1 || v > 3072) return -1;
-        g_opt_trace_mb = v;
-    } else if (k == "orient") {
-        if (v < 0 || v > 2) return -1;
-        g_opt_orient = v;
-    } else if (k == "mode") {
-        if (v < -1 || v > 5) return -1;
-        g_opt_mode = v;
-    } else if (k == "duo16") {   // 1 = duo max3 through v_pk_maximum3_f16 when exact (default), 0 = u16 max only
-        g_opt_duo_f16 = v ? 1 : 0;
-    } else if (k == "f2stream") {   // 1 = flow2 streams row codes even when they fit in LDS (tests)
-        g_opt_f2stream = v ? 1 : 0;
-    } else if (k == "f2_wgs") {   // flow2 streamed kernel: workgroups per CU, 0 = auto, 1..F2_WGS_MAX
-        if (v < 0 || v > F2_WGS_MAX) return -1;
-        g_opt_f2_wgs = v;
-    } else if (k == "f2w") {   // flow2 columns per lane: 0 auto, 1, 2 (2: the linear-gap step only),
-        // 3 (flow3 ring mode with the linear-gap step: single long pairs and column slabs; auto there),
-        // 4 (four / five columns per lane in that ring mode, one pair, every group in one round)
-        if (v < 0 || v > 4) return -1;
-        g_opt_f2w = v;
-    } else if (k == "f2pwg") {   // int32 DNA batches on flow2, a pair per workgroup: -1 auto, 0 off, 1 forced
-        if (v < -1 || v > 1) return -1;
-        g_opt_f2pwg = v;
-    } else if (k == "linear") {   // G_INIT == G_EXT: -1 auto (the linear-gap step), 0 = the affine step
-        if (v < -1 || v > 0) return -1;
-        g_opt_linear = v;
-    } else if (k == "f3") {   // 1 (default): staged W2 linear-gap launches on flow3 (sw_flow3.hip), 0: flow2
-        if (v < 0 || v > 1) return -1;
-        g_opt_f3 = v;
-    } else if (k == "duo_lds") {   // 1 (default): duo strip hand-offs in LDS when the wrap buffer fits, 0: HBM granules
-        if (v < 0 || v > 1) return -1;
-        g_opt_duo_lds = v;
-    } else if (k == "f3hl") {   // 1: flow3 staged launches at C = 32 with half-chunk in-workgroup links (auto C: 32)
-        if (v < 0 || v > 1) return -1;
-        g_opt_f3hl = v;
-    } else if (k == "f3rhl") {   // 1: flow3 ring launches at C = 64 with half-chunk in-workgroup links
-        if (v < 0 || v > 1) return -1;
-        g_opt_f3rhl = v;
-    } else if (k == "duo_prio") {   // duo LDS kernel: -1 auto, 0 off, k in 6..20: workgroups of a CU alternate priority every 2^k clock ticks (10 ns)
-        if (v != 0 && v != -1 && (v < 6 || v > 20)) return -1;
-        g_opt_duo_prio = v;
-    } else if (k == "f3slab") {   // 1 (default): column slabs on flow3's ring kernel (sw_flow3rs_kernel), 0: flow2
-        if (v < 0 || v > 1) return -1;
-        g_opt_f3slab = v;
-    } else if (k == "f3pool") {   // 1: flow3 staged C = 32 half-chunk launches on the pool loops (default 0: slower)
-        if (v < 0 || v > 1) return -1;
-        g_opt_f3pool = v;
-    } else if (k == "f3a") {   // 1 (default): staged affine-step launches on flow3 (sw_flow3a_kernel), 0: flow2
-        if (v < 0 || v > 1) return -1;
-        g_opt_f3a = v;
-    } else if (k == "duo_roles") {   // 1 (default): duo strip roles complementary per SIMD across a CU's workgroups
-        if (v < 0 || v > 1) return -1;
-        g_opt_duo_roles = v;
-    } else if (k == "duo_tab") {   // 1 (default): duo LDS kernel row codes from an LDS table for one-pass batches,
-        // 2: whenever it fits, 0: carried by DPP
-        if (v < 0 || v > 2) return -1;
-        g_opt_duo_tab = v;
-    } else if (k == "slab_plain") {   // 1: exported slab buffers may fall back to plain device memory
-        if (v < 0 || v > 1) return -1;
-        g_opt_slab_plain = v;
-    } else if (k == "ring") {   // flow2 one-pair group edges: -1 auto (rings above 1 GB of edges), 0 off, 1 on
-        if (v < -1 || v > 1) return -1;
-        g_opt_ring = v;
-    } else if (k == "ring_rows") {   // rows per within-round ring: a power of two in [512, 2^20]
-        if (v < 512 || v > (1 << 20) || (v & (v - 1))) return -1;
-        g_opt_ring_rows = v;
-    } else {
+    const int i = find_opt(key);
+    if (i < 0) {
         set_err("unknown option '%s'", key);
         return -1;
     }
+    const OptRow& r = OPT_ROWS[i];
+    if (v < r.lo || v > r.hi || (r.ok && !r.ok(v))) return -1;
+    g_opt[i] = r.flag ? (v != 0) : v;
     return 0;
 }
 
 long long sw_get_option(const char* key) {
-    if (!key) return -1;
-    const std::string k(key);
-    if (k == "W") return g_opt_W;
-    if (k == "C") return g_opt_C;
-    if (k == "bytes") return g_opt_bytes;
-    if (k == "timeout") return g_opt_timeout;
-    if (k == "stall_item") return g_opt_stall_item;
-    if (k == "f3pwg") return g_opt_f3pwg;
-    if (k == "duo_raw") return g_opt_duo_raw;
-    if (k == "hep") return g_opt_hep;
-    if (k == "f3split") return g_opt_f3split;
-    if (k == "blocks") return g_opt_blocks;
-    if (k == "orient") return g_opt_orient;
-    if (k == "trace") return g_opt_trace;
-    if (k == "trace_mb") return g_opt_trace_mb;
-    if (k == "mode") return g_opt_mode;
-    if (k == "duo16") return g_opt_duo_f16;
-    if (k == "f2stream") return g_opt_f2stream;
-    if (k == "ring") return g_opt_ring;
-    if (k == "linear") return g_opt_linear;
-    if (k == "f2_wgs") return g_opt_f2_wgs;
-    if (k == "ring_rows") return g_opt_ring_rows;
-    if (k == "f2w") return g_opt_f2w;
-    if (k == "f2pwg") return g_opt_f2pwg;
-    if (k == "f3") return g_opt_f3;
-    if (k == "slab_plain") return g_opt_slab_plain;
-    if (k == "duo_lds") return g_opt_duo_lds;
-    if (k == "duo_tab") return g_opt_duo_tab;
-    if (k == "duo_roles") return g_opt_duo_roles;
-    if (k == "f3hl") return g_opt_f3hl;
-    if (k == "f3rhl") return g_opt_f3rhl;
-    if (k == "f3a") return g_opt_f3a;
-    if (k == "f3pool") return g_opt_f3pool;
-    if (k == "f3slab") return g_opt_f3slab;
-    if (k == "duo_prio") return g_opt_duo_prio;
-    return -1;
+    const int i = key ? find_opt(key) : -1;
+    return i < 0 ? -1 : g_opt[i].load();
 }
+
+const char* sw_option_name(int i) { return i >= 0 && i < OPT_COUNT ? OPT_ROWS[i].key : nullptr; }
 
 int sw_last_stats(sw_stats* out) {
     if (!out) return -1;

@@ -138,7 +138,7 @@ inline bool grouped_mode(int mode) { return mode == MODE_CHAIN || mode == MODE_F
 #endif
 constexpr int DUO_WAVES = SW_DUO_WAVES;   // waves per workgroup of the duo kernel (one workgroup per duo)
 
-// Host-side launch (sw_kernels.hip).
+// Host-side launch (sw_kernels.hip).  sw_engine.hip select_variant fills it; f2_wgs and blocks after the rest (size_grid).
 struct LaunchCfg {
     int W;          // columns per lane
     int C;          // rows per hand-off chunk

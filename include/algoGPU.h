@@ -397,6 +397,8 @@ void sw_last_align_ms(float* fill_ms, float* walk_ms);
  * Returns 0, or -1 for an unknown key / bad value. */
 int sw_set_option(const char* key, long long value);
 long long sw_get_option(const char* key);
+/* The keys above, in the library's own order: key i for 0 <= i < their number, else NULL. */
+const char* sw_option_name(int i);
 
 /* Details of the last launch made by this thread (for the harness / bench). */
 typedef struct {
