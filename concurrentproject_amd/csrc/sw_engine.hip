@@ -24,6 +24,7 @@
 #include <thread>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <mutex>
@@ -154,11 +155,17 @@ std::atomic<long long> g_opt[OPT_COUNT] = {SW_OPTIONS(X)};
 // hands it down, so a sw_set_option from another thread never splits a launch between two values.
 struct Opts {
     long long v[OPT_COUNT];
+    // environment SWMI_F3WEDGE, read with the snapshot (A/B runs and small-shape tests; not an option):
+    // 0 never plans a pair as two wedges (plan_wedge), 1 plans it wherever the geometry admits it, anything
+    // else or unset leaves the choice to the measured thresholds
+    int f3wedge = -1;
     long long operator[](Opt o) const { return v[o]; }
 };
 Opts snapshot_opts() {
     Opts o;
     for (int i = 0; i < OPT_COUNT; ++i) o.v[i] = g_opt[i].load();
+    const char* w = std::getenv("SWMI_F3WEDGE");
+    o.f3wedge = w && w[0] == '0' && !w[1] ? 0 : w && w[0] == '1' && !w[1] ? 1 : -1;
     return o;
 }
 int find_opt(const char* key) {
@@ -310,6 +317,10 @@ struct Job {
     int hep = 0;                 // one pair over 1..7 byte values not all in {A,C,G,T}: their count (planned as
                                  // DNA, run on flow3's staged kernels, sw_flow3.hip HEP); 0 otherwise
     unsigned char hsym[256] = {};   // with hep: each byte value's symbol 0..6
+    bool wedge = false;          // one pair as two wedges (plan_wedge): pairs = {forward, mirrored chain}
+    WedgePlan wplan{};           // ... its geometry
+    int wedge_rows = 0;          // ... rows of one group edge
+    uint64_t wedge_bnd[2] = {0, 0};   // ... granule offsets of the chains' boundary buffers
 };
 
 bool is_dna_byte(unsigned char c) { return c == 'A' || c == 'C' || c == 'G' || c == 'T'; }
@@ -631,6 +642,7 @@ struct Variant {
     LaunchCfg cfg;
     bool ring = false;
     bool cut = false;
+    bool wedge = false;
     const char* err = nullptr;
 };
 
@@ -663,6 +675,7 @@ Variant select_variant(const Job& job, const Params& prm, const Opts& opt, int c
     Variant v;
     v.ring = ring;
     v.cut = !job.pairs.empty() && (job.pairs[0].flags & PAIR_HALF) != 0;
+    v.wedge = job.wedge;
     LaunchCfg& cfg = v.cfg = LaunchCfg{job.W, job.C, job.dna, 0, job.mode, max_rows(job)};
     // flow2's ring and slab kernels always stream the row codes (sw_flow2.hip launch_v)
     const bool f2s = flow2 && (job.f2_stream || ring || slab);
@@ -729,10 +742,11 @@ Variant select_variant(const Job& job, const Params& prm, const Opts& opt, int c
 // The variant word of sw_last_stats (include/algoGPU.h documents the bits)
 int variant_word(const Variant& v) {
     const LaunchCfg& c = v.cfg;
-    const bool bits[18] = {c.duo_f16, c.f2_stream, v.ring,     c.f2_lin, c.f2_w2, c.f2_pwg, c.f3,    c.duo_wrap > 0, c.duo_tab > 0,
-                           c.f3_hl,   c.f3a || c.f3ra, c.f3_slab, c.f3p,  c.f3_w3, c.f3_w45, c.f3_pwg, c.hep,       v.cut};
+    const bool bits[19] = {c.duo_f16, c.f2_stream, v.ring,     c.f2_lin, c.f2_w2, c.f2_pwg, c.f3,    c.duo_wrap > 0, c.duo_tab > 0,
+                           c.f3_hl,   c.f3a || c.f3ra, c.f3_slab, c.f3p,  c.f3_w3, c.f3_w45, c.f3_pwg, c.hep,       v.cut,
+                           v.wedge};
     int w = 0;
-    for (int b = 0; b < 18; ++b) w |= (bits[b] ? 1 : 0) << b;
+    for (int b = 0; b < 19; ++b) w |= (bits[b] ? 1 : 0) << b;
     return w;
 }
 
@@ -789,6 +803,48 @@ bool plan_split(Job& job, const Params& prm, const Opts& opt, int cus) {
     job.bnd_granules = right.bnd_off + (uint64_t)((right.strips + 3) / 4) * (uint64_t)whole.m;
     job.pairs = {left, right};
     job.item_base = {0, (left.strips + 3) / 4, (left.strips + 3) / 4 + (right.strips + 3) / 4};
+    return true;
+}
+
+// One pair on flow3's staged two-column linear-gap kernel as two wedges cut along an anti-diagonal staircase
+// (the identity and its geometry: tests/test_wedge_identity.py, sw_internal.h
+// wedge_bounds).  The forward chain runs over all columns, strip s for e0 - 64 s rows; the mirrored chain
+// the same from the far corner; every strip leaves the last two rows of H of its lanes, and the wedge combine
+// kernel joins the two staircases.  No strip runs all m rows, so a chain ends about (m + 64 S) / 2 + S (lag - 1)
+// steps in instead of the column cut's m + S / 2 (63 + lag).  Same admission as plan_split, and every strip
+// must keep one 64-row body: m >= 64 S + 64.  The chains' groups alternate in the item order (F0, B0, F1, ...):
+// a group waits on a lower item only, whatever the grid.
+// Automatic (option f3split = -1, SWMI_F3WEDGE unset) from F3_WEDGE_AUTO_N columns, the narrowest width of the
+// measured sweep (profiles/f3wedge_ab.jsonl: the wedge beats the cut at every admissible shape measured, rows
+// from the admission edge up); below it the column cut's own rule stays.  f3split = 0 switches it off with the
+// cut, f3split = 1 keeps forcing the column cut.
+constexpr int F3_WEDGE_AUTO_N = 4096;
+bool plan_wedge(Job& job, const Params& prm, const Opts& opt, int cus) {
+    if (opt[O_f3split] != -1 || opt.f3wedge == 0 || job.pairs.size() != 1 || opt[O_trace] != 0) return false;
+    const Variant v = select_variant(job, prm, opt, cus);
+    if (v.err || !v.cfg.f3 || v.ring || v.cfg.f2_stream || v.cfg.f3p || job.slab) return false;
+    const PairDesc whole = job.pairs[0];
+    WedgePlan w;
+    if (!wedge_bounds(whole.n, whole.m, &w)) return false;
+    if (opt.f3wedge != 1 && whole.n < F3_WEDGE_AUTO_N) return false;
+    const int groups = (w.strips + 3) / 4;
+    PairDesc f = whole, b = whole;
+    f.strips = b.strips = w.strips;
+    f.flags = PAIR_WEDGE;
+    b.flags = PAIR_WEDGE | PAIR_REV;
+    b.lead = w.lead;
+    // a chain's group edges hold the rows its strips reach; behind both chains' edges the two boundary
+    // buffers of two 16-B entries per strip and lane
+    job.wedge_rows = std::max(w.e0[0], w.e0[1]) + 64;
+    f.bnd_off = 0;
+    b.bnd_off = (uint64_t)groups * (uint64_t)job.wedge_rows;
+    job.wedge_bnd[0] = 2 * b.bnd_off;
+    job.wedge_bnd[1] = job.wedge_bnd[0] + 128ull * (uint64_t)w.strips;
+    job.bnd_granules = job.wedge_bnd[1] + 128ull * (uint64_t)w.strips;
+    job.pairs = {f, b};
+    job.item_base = {0, groups, 2 * groups};
+    job.wedge = true;
+    job.wplan = w;
     return true;
 }
 
@@ -1294,6 +1350,15 @@ KParams fill_kparams(Ctx* c, const Job& job, const Variant& v, const Grid& g, co
         kp.ring_cons = c->cons.p;
     }
     if (job.f3pwg) kp.wrap_rows = g.wrap_rows;   // each block's edge ring (kp.ring_rows stays 0)
+    if (v.wedge) {
+        kp.wedge = 1;
+        kp.wedge_e0[0] = job.wplan.e0[0];
+        kp.wedge_e0[1] = job.wplan.e0[1];
+        kp.wedge_rlead = job.wplan.rlead;
+        kp.wedge_rows = job.wedge_rows;
+        kp.wedge_bnd[0] = job.wedge_bnd[0];
+        kp.wedge_bnd[1] = job.wedge_bnd[1];
+    }
     if (v.cfg.hep && v.ring) kp.hrows = c->hrows.p;
     if (edge) {   // (flow2 then runs its slab kernel, which streams the row codes)
         kp.slab_in = edge->in;
@@ -1311,8 +1376,8 @@ int enqueue(Ctx* c, Job& job, const Params& prm, const Opts& opt, const unsigned
         set_err("no kernel variant for W=%d C=%d", job.W, job.C);
         return -1;
     }
-    // one long pair on the staged flow3 linear-gap kernel: two half pairs from here on
-    plan_split(job, prm, opt, c->cus);
+    // one long pair on the staged flow3 linear-gap kernel: two wedges, or two half pairs, from here on
+    if (!plan_wedge(job, prm, opt, c->cus)) plan_split(job, prm, opt, c->cus);
     Variant v = select_variant(job, prm, opt, c->cus);
     if (v.err) {
         set_err("%s", v.err);
@@ -1335,6 +1400,9 @@ int enqueue(Ctx* c, Job& job, const Params& prm, const Opts& opt, const unsigned
         const Granule* gr = c->bnd.p + r.bnd_off + (uint64_t)((r.strips + 3) / 4 - 1) * (uint64_t)r.m;
         HIPCHK(launch_sw_flow3_combine(gl, gr, l.m, prm.gap_init, kp.epoch, c->ctrl.p, d_scores + l.out_idx, s));
     }
+    if (v.wedge)   // the crossing term from the chains' staircases (inside the timed span)
+        HIPCHK(launch_sw_flow3_wedge_combine(c->bnd.p + job.wedge_bnd[0], c->bnd.p + job.wedge_bnd[1], job.wplan,
+                                             job.pairs[0].m, kp.epoch, c->ctrl.p, d_scores + job.pairs[0].out_idx, s));
     if (time_kernel) HIPCHK(hipEventRecord(c->ev1, s));
 
     t_stats = sw_stats{};

@@ -21,10 +21,13 @@ struct PairDesc {
     // kernel only, 0 elsewhere).  PAIR_HALF: the last strip publishes its outflow as granules
     // into edge (strips + 3) / 4 - 1 for the combine kernel.  PAIR_REV: columns and rows are
     // read mirrored (column j is byte col_off + n - 1 - j, row r byte row_off + m - 1 - r).
+    // PAIR_WEDGE: one chain of a pair cut along an anti-diagonal staircase (plan_wedge; KParams::wedge_*):
+    // strip s runs wedge_e0 - 64 s steps and every strip writes its lanes' last two rows of H into the
+    // chain's boundary buffer for the wedge combine kernel.
     int flags;
     int lead;           // dead columns in front of column 0 (strip s, lane l: column 126 s + 2 l - lead)
 };
-enum : int { PAIR_HALF = 1, PAIR_REV = 2 };
+enum : int { PAIR_HALF = 1, PAIR_REV = 2, PAIR_WEDGE = 4 };
 
 // Two pairs scored in lock step by the packed-u16 "duo" kernel: lane values
 // hold pair 0 in the low and pair 1 in the high 16 bits.  Both are padded to
@@ -118,6 +121,16 @@ struct KParams {
     int stall_item;               // tests only (option stall_item): flow2's compute waves skip this item, so its
                                   // edges are never published and its consumers' bounded waits must expire; -1 = none
     // (the duo kernel with LDS hand-offs takes its wrap-buffer slots from wrap_rows)
+    // One pair as two wedges (sw_engine.hip plan_wedge; flow3's staged linear-gap kernel): pair 0 is the
+    // forward chain, pair 1 the mirrored one; item i is group i / 2 of pair i % 2.  Chain p's strip s runs
+    // wedge_e0[p] - 64 s steps (multiples of 64); the mirrored chain has wedge_rlead dead rows in front of its
+    // row 0; a chain's group edges are wedge_rows rows apart, and its boundary buffer (two 16-B entries
+    // per strip and lane) starts wedge_bnd[p] granules into the arena.
+    int wedge;                    // 0: no wedge launch
+    int wedge_e0[2];
+    int wedge_rlead;
+    int wedge_rows;
+    unsigned long long wedge_bnd[2];
 };
 
 constexpr int RING_CONS_STRIDE = 32;   // dwords between consumer progress words (one 128-B line each)
@@ -240,6 +253,32 @@ bool flow3_fits(int max_m, int C, bool aff = false);
 // from the two halves' final edges (8-B granules keyed with the launch epoch), atomicMax into *score
 hipError_t launch_sw_flow3_combine(const Granule* gl, const Granule* gr, int m, int gap, unsigned epoch, Ctrl* ctrl,
                                    int* score, hipStream_t stream);
+// One pair as two wedges (sw_engine.hip plan_wedge): strips per chain, dead columns and rows in front of the
+// mirrored chain, and the steps of each chain's strip 0.  False where a strip would keep less than 64 rows.
+struct WedgePlan {
+    int strips, lead, rlead, e0[2];
+};
+// Both chains run S = ceil((n - 2) / 126) strips over 126 S + 2 padded columns, so the mirrored chain's strip
+// S - 1 - s lies on the forward chain's strip s (lane 63 - l on lane l).  With T = m + rlead - 2 + 64 S a
+// multiple of 64 and e0[0] + e0[1] = T, the two rows a forward lane exports are the two its mirror lane
+// exports (tests/test_wedge_identity.py proves the join and that the shared nodes cover every crossing path).
+inline bool wedge_bounds(int n, int m, WedgePlan* w) {
+    if (n < 253 || m < 1) return false;
+    const long long S = ((long long)n - 2 + 125) / 126;
+    if ((long long)m < 64 * S + 64) return false;
+    const long long rlead = ((2 - (long long)m) % 64 + 64) % 64;
+    const long long T = (long long)m + rlead - 2 + 64 * S;
+    w->strips = (int)S;
+    w->lead = (int)(126 * S + 2 - n);
+    w->rlead = (int)rlead;
+    w->e0[0] = (int)(64 * (T / 128));
+    w->e0[1] = (int)(T - w->e0[0]);
+    return true;
+}
+// the crossing term of a wedge launch (sw_flow3.hip): max of H_F + H_B over the staircase's shared nodes from
+// the two chains' boundary buffers (entries keyed with the launch epoch), atomicMax into *score
+hipError_t launch_sw_flow3_wedge_combine(const Granule* bf, const Granule* bb, const WedgePlan& w, int m, unsigned epoch,
+                                         Ctrl* ctrl, int* score, hipStream_t stream);
 // workgroups per CU resident for a flow3 ring-mode launch (its LDS pad of cfg.f2_wgs), -1 on error
 int flow3_ring_resident(const LaunchCfg& cfg);
 int flow2_waves_per_cu(int C);

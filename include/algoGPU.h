@@ -366,7 +366,11 @@ void sw_last_align_ms(float* fill_ms, float* walk_ms);
  *              from both ends at once, the right half on both sequences mirrored, joined by a small
  *              combine kernel (sw_split_bounds): -1 = (default) automatic, for pairs at least the
  *              measured threshold wide; 0 = never; 1 = whenever each half gets two strips (n >= 379).
- *              Traced launches (option trace), ring mode, slabs, batches and the affine step run uncut
+ *              Traced launches (option trace), ring mode, slabs, batches and the affine step run uncut.
+ *              Under -1 a pair tall and wide enough is scored as two wedges cut along an anti-diagonal
+ *              staircase instead (variant bit 18; 0 switches that off too, 1 keeps the column cut); the
+ *              environment variable SWMI_F3WEDGE (0 = never, 1 = wherever every strip keeps 64 rows)
+ *              overrides the measured thresholds for A/B runs and tests
  *   "f3pwg"    1 = (default) DNA batches on a pair-per-workgroup plan (scores that need int32, or 1-2
  *              pairs per CU) run flow3's three-column ring step (sw_flow3r3p / ra3p_kernel), 0 = flow2's
  *   "f3slab"   1 = (default) column slabs run flow3's ring kernel with slab roles
@@ -425,7 +429,10 @@ typedef struct {
                                bit 16: a pair over up to seven byte values on flow3's staged kernels
                                        (option hep; dna = 2 then);
                                bit 17: one pair cut at a column, both halves in one launch (option f3split;
-                                       items and blocks count both halves) */
+                                       items and blocks count both halves);
+                               bit 18: one pair scored as two wedges cut along an anti-diagonal staircase,
+                                       both chains in one launch (automatic under option f3split = -1;
+                                       items and blocks count both chains) */
 } sw_stats;
 int sw_last_stats(sw_stats* out);
 

@@ -307,7 +307,23 @@ def gen_role(IN, OUT_, spec=0, halfpub=True, C=32, hl=False):
     if gran:
         granule(a, grows)
     a("s_waitcnt vmcnt(0) lgkmcnt(0)")
+    # ---- the strip's lower boundary (a wedge chain's staircase, sw_flow3.hip PAIR_WEDGE): H of both
+    # columns at the lane's last row, then one step more (row k0 - lane: the next chunk's first row
+    # codes are in v76) and H at that row.  Lane 0's inflow of that row does not exist when the strip on
+    # its left ends 64 steps later (its exit flush stops one row short), so lane 0 of a strip with
+    # inflow steps on the border value and its second row is not used: lane 63 of the strip on the left
+    # holds the same columns one row further down.
+    a("v_mov_b32 v107, v66")
+    a("v_mov_b32 v108, v68")
+    a("v_mov_b32 v64, %[ng]")
+    a("v_perm_b32 v72, %[pA], %[qA], v76")
+    a("v_perm_b32 v73, %[pB], %[qB], v76")
+    step(a, "v64", "v65", 0)
     a("v_mov_b32 %[M], v74")
+    a("v_mov_b32 %[a0], v107")
+    a("v_mov_b32 %[b0], v108")
+    a("v_mov_b32 %[a1], v66")
+    a("v_mov_b32 %[b1], v68")
     a("s_mov_b32 %[fail], s45")
     a("s_mov_b32 %[slow], s46")
     a("s_branch L_done_%=")
@@ -364,7 +380,7 @@ def slow_wait(a, label, resume, vreg, addr, sreg, reread=None, target="s40"):
     a(f"s_branch {resume}")
 
 
-CLOBBERS = ['"v%d"' % r for r in range(64, 107) if r not in (75, 104)] + \
+CLOBBERS = ['"v%d"' % r for r in range(64, 109) if r not in (75, 104)] + \
     ['"s%d"' % r for r in range(40, 53) if r != 42 and r != 47] + ['"scc"', '"vcc"', '"memory"']
 
 
@@ -384,7 +400,8 @@ def emit(spec=0, halfpub=True):
                 out.append("    asm volatile(")
                 for line in body:
                     out.append('        "%s\\n\\t"' % line)
-                out.append('        : [M] "=v"(r.M), [fail] "=s"(r.fail), [slow] "=s"(r.slow)')
+                out.append('        : [M] "=v"(r.M), [fail] "=s"(r.fail), [slow] "=s"(r.slow), [a0] "=v"(r.a0), [b0] "=v"(r.b0),')
+                out.append('          [a1] "=v"(r.a1), [b1] "=v"(r.b1)')
                 out.append('        : [pA] "v"(x.pA), [pB] "v"(x.pB), [ng] "v"(x.ng), [G] "s"(x.G), [qA] "v"(x.qA),')
                 out.append('          [qB] "v"(x.qB), [code] "v"(x.code), [lin] "v"(x.lin), [lout] "v"(x.lout), [pin] "v"(x.pin),')
                 out.append('          [pout] "v"(x.pout), [qme] "v"(x.qme), [qnx] "v"(x.qnx), [end] "s"(x.end),')
