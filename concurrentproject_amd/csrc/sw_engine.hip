@@ -159,6 +159,12 @@ struct Opts {
     // 0 never plans a pair as two wedges (plan_wedge), 1 plans it wherever the geometry admits it, anything
     // else or unset leaves the choice to the measured thresholds
     int f3wedge = -1;
+    // environment SWMI_F3WEDGE_DROPS = d0,d1,d2,d3, read with the snapshot (A/B runs and tests; not an option): the
+    // wedge plan's drop pattern (plan_wedge; sw_internal.h steep_bounds), 64,64,64,64 being the uniform plan.
+    // f3drops_set: 0 unset (the measured default), 1 set, -1 not four multiples of 64 in 64 .. WEDGE_DROP_MAX with
+    // d0 == d2 (the launch fails)
+    int f3drops_set = 0;
+    int f3drops[4] = {64, 64, 64, 64};
     long long operator[](Opt o) const { return v[o]; }
 };
 Opts snapshot_opts() {
@@ -166,6 +172,11 @@ Opts snapshot_opts() {
     for (int i = 0; i < OPT_COUNT; ++i) o.v[i] = g_opt[i].load();
     const char* w = std::getenv("SWMI_F3WEDGE");
     o.f3wedge = w && w[0] == '0' && !w[1] ? 0 : w && w[0] == '1' && !w[1] ? 1 : -1;
+    if (const char* d = std::getenv("SWMI_F3WEDGE_DROPS")) {
+        char tail = 0;
+        const int got = std::sscanf(d, "%d,%d,%d,%d%c", &o.f3drops[0], &o.f3drops[1], &o.f3drops[2], &o.f3drops[3], &tail);
+        o.f3drops_set = got == 4 && wedge_drops_ok(o.f3drops) ? 1 : -1;
+    }
     return o;
 }
 int find_opt(const char* key) {
@@ -321,6 +332,8 @@ struct Job {
     WedgePlan wplan{};           // ... its geometry
     int wedge_rows = 0;          // ... rows of one group edge
     uint64_t wedge_bnd[2] = {0, 0};   // ... granule offsets of the chains' boundary buffers
+    int wedge_segr = 0;          // ... a steep plan: 8-B entries per strip of a chain's segment buffer
+    uint64_t wedge_seg[2] = {0, 0};   // ... and the granule offsets of those buffers
 };
 
 bool is_dna_byte(unsigned char c) { return c == 'A' || c == 'C' || c == 'G' || c == 'T'; }
@@ -643,6 +656,7 @@ struct Variant {
     bool ring = false;
     bool cut = false;
     bool wedge = false;
+    bool steep = false;
     const char* err = nullptr;
 };
 
@@ -676,6 +690,7 @@ Variant select_variant(const Job& job, const Params& prm, const Opts& opt, int c
     v.ring = ring;
     v.cut = !job.pairs.empty() && (job.pairs[0].flags & PAIR_HALF) != 0;
     v.wedge = job.wedge;
+    v.steep = job.wedge && job.wplan.steep;
     LaunchCfg& cfg = v.cfg = LaunchCfg{job.W, job.C, job.dna, 0, job.mode, max_rows(job)};
     // flow2's ring and slab kernels always stream the row codes (sw_flow2.hip launch_v)
     const bool f2s = flow2 && (job.f2_stream || ring || slab);
@@ -742,11 +757,11 @@ Variant select_variant(const Job& job, const Params& prm, const Opts& opt, int c
 // The variant word of sw_last_stats (include/algoGPU.h documents the bits)
 int variant_word(const Variant& v) {
     const LaunchCfg& c = v.cfg;
-    const bool bits[19] = {c.duo_f16, c.f2_stream, v.ring,     c.f2_lin, c.f2_w2, c.f2_pwg, c.f3,    c.duo_wrap > 0, c.duo_tab > 0,
+    const bool bits[20] = {c.duo_f16, c.f2_stream, v.ring,     c.f2_lin, c.f2_w2, c.f2_pwg, c.f3,    c.duo_wrap > 0, c.duo_tab > 0,
                            c.f3_hl,   c.f3a || c.f3ra, c.f3_slab, c.f3p,  c.f3_w3, c.f3_w45, c.f3_pwg, c.hep,       v.cut,
-                           v.wedge};
+                           v.wedge,   v.steep};
     int w = 0;
-    for (int b = 0; b < 19; ++b) w |= (bits[b] ? 1 : 0) << b;
+    for (int b = 0; b < 20; ++b) w |= (bits[b] ? 1 : 0) << b;
     return w;
 }
 
@@ -819,14 +834,33 @@ bool plan_split(Job& job, const Params& prm, const Opts& opt, int cus) {
 // from the admission edge up); below it the column cut's own rule stays.  f3split = 0 switches it off with the
 // cut, f3split = 1 keeps forcing the column cut.
 constexpr int F3_WEDGE_AUTO_N = 4096;
+// The steep plan (sw_internal.h steep_bounds): a staircase that drops more than 64 rows behind some strips, so
+// that the strips of a chain end closer together than the hand-off lag lets the uniform plan's (DESIGN.md
+// section 4).  Taken with the pattern of SWMI_F3WEDGE_DROPS wherever it is admissible.  Without that variable,
+// from F3_STEEP_AUTO_N columns (profiles/f3steep_ab.jsonl: 7 to 12 % under the uniform wedge at every admissible
+// shape from 4096 columns): F3_STEEP_AUTO_DROPS, 384 rows a group, about the lag of a group's four hand-offs, so
+// the strips of a chain end together; and where the launch has more groups than the GPU has CUs (a workgroup a
+// CU: C2's 262 on 256), F3_STEEP_QUEUED_DROPS first, 448 rows a group: the queued groups wait for a resident one
+// to end, and with the drops above the lag the late groups end first (C2: 1.41 ms uniform, 1.37 at 384 rows a
+// group, 1.28 at 448, whichever links carry them).  Elsewhere the uniform plan.
+constexpr int F3_STEEP_AUTO_N = 4096;
+constexpr int F3_STEEP_AUTO_DROPS[4] = {64, 128, 64, 128};
+constexpr int F3_STEEP_QUEUED_DROPS[4] = {128, 64, 128, 128};
 bool plan_wedge(Job& job, const Params& prm, const Opts& opt, int cus) {
     if (opt[O_f3split] != -1 || opt.f3wedge == 0 || job.pairs.size() != 1 || opt[O_trace] != 0) return false;
     const Variant v = select_variant(job, prm, opt, cus);
     if (v.err || !v.cfg.f3 || v.ring || v.cfg.f2_stream || v.cfg.f3p || job.slab) return false;
     const PairDesc whole = job.pairs[0];
-    WedgePlan w;
-    if (!wedge_bounds(whole.n, whole.m, &w)) return false;
     if (opt.f3wedge != 1 && whole.n < F3_WEDGE_AUTO_N) return false;
+    WedgePlan w;
+    const auto steep = [&](const int* d) {
+        return std::max(std::max(d[0], d[1]), std::max(d[2], d[3])) > 64 && steep_bounds(whole.n, whole.m, d, &w);
+    };
+    const bool queued = 2 * ((((long long)whole.n - 2 + 125) / 126 + 3) / 4) > cus;
+    const bool st = opt.f3drops_set ? steep(opt.f3drops)
+                                    : whole.n >= F3_STEEP_AUTO_N &&
+                                          ((queued && steep(F3_STEEP_QUEUED_DROPS)) || steep(F3_STEEP_AUTO_DROPS));
+    if (!st && !wedge_bounds(whole.n, whole.m, &w)) return false;
     const int groups = (w.strips + 3) / 4;
     PairDesc f = whole, b = whole;
     f.strips = b.strips = w.strips;
@@ -841,6 +875,13 @@ bool plan_wedge(Job& job, const Params& prm, const Opts& opt, int cus) {
     job.wedge_bnd[0] = 2 * b.bnd_off;
     job.wedge_bnd[1] = job.wedge_bnd[0] + 128ull * (uint64_t)w.strips;
     job.bnd_granules = job.wedge_bnd[1] + 128ull * (uint64_t)w.strips;
+    if (w.steep) {   // per chain and strip the longest hand-off column's 8-B entries (even: whole granules)
+        job.wedge_segr = std::max(std::max(w.drop[0], w.drop[1]), std::max(w.drop[2], w.drop[3])) - 62;
+        const uint64_t seg = (uint64_t)w.strips * (uint64_t)job.wedge_segr / 2;
+        job.wedge_seg[0] = job.bnd_granules;
+        job.wedge_seg[1] = job.wedge_seg[0] + seg;
+        job.bnd_granules = job.wedge_seg[1] + seg;
+    }
     job.pairs = {f, b};
     job.item_base = {0, groups, 2 * groups};
     job.wedge = true;
@@ -1358,6 +1399,10 @@ KParams fill_kparams(Ctx* c, const Job& job, const Variant& v, const Grid& g, co
         kp.wedge_rows = job.wedge_rows;
         kp.wedge_bnd[0] = job.wedge_bnd[0];
         kp.wedge_bnd[1] = job.wedge_bnd[1];
+        for (int j = 0; j < 4; ++j) kp.wedge_drop[j] = job.wplan.drop[j];
+        kp.wedge_segr = job.wedge_segr;
+        kp.wedge_seg[0] = job.wedge_seg[0];
+        kp.wedge_seg[1] = job.wedge_seg[1];
     }
     if (v.cfg.hep && v.ring) kp.hrows = c->hrows.p;
     if (edge) {   // (flow2 then runs its slab kernel, which streams the row codes)
@@ -1374,6 +1419,10 @@ int enqueue(Ctx* c, Job& job, const Params& prm, const Opts& opt, const unsigned
             hipStream_t s, bool time_kernel, const SlabEdge* edge = nullptr) {
     if (job.mode == MODE_FLOW2 ? !flow2_variant_exists(job.C) : !variant_exists(job.W, job.C)) {
         set_err("no kernel variant for W=%d C=%d", job.W, job.C);
+        return -1;
+    }
+    if (opt.f3drops_set < 0) {
+        set_err("SWMI_F3WEDGE_DROPS: need d0,d1,d2,d3, multiples of 64 from 64 to %d with d0 == d2", WEDGE_DROP_MAX);
         return -1;
     }
     // one long pair on the staged flow3 linear-gap kernel: two wedges, or two half pairs, from here on
@@ -1400,7 +1449,12 @@ int enqueue(Ctx* c, Job& job, const Params& prm, const Opts& opt, const unsigned
         const Granule* gr = c->bnd.p + r.bnd_off + (uint64_t)((r.strips + 3) / 4 - 1) * (uint64_t)r.m;
         HIPCHK(launch_sw_flow3_combine(gl, gr, l.m, prm.gap_init, kp.epoch, c->ctrl.p, d_scores + l.out_idx, s));
     }
-    if (v.wedge)   // the crossing term from the chains' staircases (inside the timed span)
+    if (v.steep) {   // the crossing term from the chains' staircases and hand-off columns (inside the timed span)
+        const SteepJoin j = {c->bnd.p + job.wedge_bnd[0], c->bnd.p + job.wedge_bnd[1], c->bnd.p + job.pairs[0].bnd_off,
+                             c->bnd.p + job.pairs[1].bnd_off, c->bnd.p + job.wedge_seg[0], c->bnd.p + job.wedge_seg[1],
+                             job.wedge_rows, job.wedge_segr, job.pairs[0].m, prm.gap_init};
+        HIPCHK(launch_sw_flow3_steep_combine(j, job.wplan, kp.epoch, c->ctrl.p, d_scores + job.pairs[0].out_idx, s));
+    } else if (v.wedge)   // the crossing term from the chains' staircases (inside the timed span)
         HIPCHK(launch_sw_flow3_wedge_combine(c->bnd.p + job.wedge_bnd[0], c->bnd.p + job.wedge_bnd[1], job.wplan,
                                              job.pairs[0].m, kp.epoch, c->ctrl.p, d_scores + job.pairs[0].out_idx, s));
     if (time_kernel) HIPCHK(hipEventRecord(c->ev1, s));

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+
 namespace swmi {
 
 // One pair after orientation: the "column" sequence (length n) runs across the
@@ -126,11 +128,20 @@ struct KParams {
     // wedge_e0[p] - 64 s steps (multiples of 64); the mirrored chain has wedge_rlead dead rows in front of its
     // row 0; a chain's group edges are wedge_rows rows apart, and its boundary buffer (two 16-B entries
     // per strip and lane) starts wedge_bnd[p] granules into the arena.
+    // The drop behind strip j (strip j + 1 ends that many steps before strip j) is wedge_drop[j % 4], 64 each in
+    // the uniform plan.  A steep plan (steep_bounds; wedge_segr > 0) joins the chains along every strip's hand-off
+    // column too: each strip but the last stores the outflow row no publish sends (row end - 64) as an 8-B
+    // granule {H - G, key} at entry strip * wedge_segr of its chain's segment buffer, wedge_seg[p] granules into
+    // the arena, and a producer on an in-workgroup link the drop - 63 rows above it (end - drop - 1 .. end - 65)
+    // behind that.
     int wedge;                    // 0: no wedge launch
     int wedge_e0[2];
     int wedge_rlead;
     int wedge_rows;
     unsigned long long wedge_bnd[2];
+    int wedge_drop[4];
+    int wedge_segr;
+    unsigned long long wedge_seg[2];
 };
 
 constexpr int RING_CONS_STRIDE = 32;   // dwords between consumer progress words (one 128-B line each)
@@ -255,8 +266,11 @@ hipError_t launch_sw_flow3_combine(const Granule* gl, const Granule* gr, int m, 
                                    int* score, hipStream_t stream);
 // One pair as two wedges (sw_engine.hip plan_wedge): strips per chain, dead columns and rows in front of the
 // mirrored chain, and the steps of each chain's strip 0.  False where a strip would keep less than 64 rows.
+// A steep plan (steep_bounds) also has drops above 64.
 struct WedgePlan {
     int strips, lead, rlead, e0[2];
+    int drop[4] = {64, 64, 64, 64};
+    bool steep = false;
 };
 // Both chains run S = ceil((n - 2) / 126) strips over 126 S + 2 padded columns, so the mirrored chain's strip
 // S - 1 - s lies on the forward chain's strip s (lane 63 - l on lane l).  With T = m + rlead - 2 + 64 S a
@@ -275,10 +289,59 @@ inline bool wedge_bounds(int n, int m, WedgePlan* w) {
     w->e0[1] = (int)(T - w->e0[0]);
     return true;
 }
+// The steep plan: the drop behind strip j is d[j % 4], multiples of 64 from 64 to WEDGE_DROP_MAX with
+// d[0] == d[2], so that the mirrored chain, whose drops are the forward chain's read from the far end, has the
+// same pattern once S is a multiple of 4.  Both chains run S = roundup4(ceil((n - 2) / 126)) strips over
+// W = 126 S + 2 padded columns, the mirrored chain behind W - 2 - n dead columns (two fewer than the uniform
+// plan's, n <= 126 S).  A strip hands its lane 62's column B to the strip on its right (whose lane 0 repeats lane
+// 63's columns), and those two dead columns less put the hand-off column of forward strip s and that of the
+// mirrored strip S - 2 - s onto one node column, 126 s + 126.  The staircase runs down that column from the
+// node of the right strip's lane 0 to those of the left strip's lane 62, drop - 60 nodes, and the join takes H
+// of both chains along it from the rows handed off (published up to row end - 65), the one row still in the
+// I/O register (end - 64) and lane 62's own two.  With D the sum of the S - 1 drops, rlead = (3 - m) mod 64 and
+// e0[0] + e0[1] = m + rlead + 61 + D the rows line up lane to lane (tests/test_steep_identity.py).  False where
+// W has no room or the last strip would keep less than 64 rows (m < D + 65).
+constexpr int WEDGE_DROP_MAX = 256;   // a producer runs drop - 64 rows past its consumer's last: well inside the LDS ring
+inline bool wedge_drops_ok(const int d[4]) {
+    for (int j = 0; j < 4; ++j)
+        if (d[j] < 64 || d[j] > WEDGE_DROP_MAX || d[j] % 64 != 0) return false;
+    return d[0] == d[2];
+}
+inline long long steep_cum(const int d[4], long long s) {   // the drops behind strips 0 .. s - 1
+    long long c = (s >> 2) * ((long long)d[0] + d[1] + d[2] + d[3]);
+    for (int j = 0; j < (int)(s & 3); ++j) c += d[j];
+    return c;
+}
+inline bool steep_bounds(int n, int m, const int d[4], WedgePlan* w) {
+    if (n < 253 || m < 1 || !wedge_drops_ok(d)) return false;
+    const long long S = (((long long)n - 2 + 125) / 126 + 3) / 4 * 4;
+    if ((long long)n + 2 > 126 * S + 2) return false;
+    const long long D = steep_cum(d, S - 1);
+    const long long rlead = ((3 - (long long)m) % 64 + 64) % 64;
+    const long long T = (long long)m + rlead + 61 + D;
+    const long long e0f = 64 * (T / 128), e0b = T - e0f;
+    if (std::min(e0f, e0b) - D < 64 || e0f > (long long)m - 1 || e0b > (long long)m + rlead - 1) return false;
+    w->strips = (int)S;
+    w->lead = (int)(126 * S - n);
+    w->rlead = (int)rlead;
+    w->e0[0] = (int)e0f;
+    w->e0[1] = (int)e0b;
+    for (int j = 0; j < 4; ++j) w->drop[j] = d[j];
+    w->steep = true;
+    return true;
+}
 // the crossing term of a wedge launch (sw_flow3.hip): max of H_F + H_B over the staircase's shared nodes from
 // the two chains' boundary buffers (entries keyed with the launch epoch), atomicMax into *score
 hipError_t launch_sw_flow3_wedge_combine(const Granule* bf, const Granule* bb, const WedgePlan& w, int m, unsigned epoch,
                                          Ctrl* ctrl, int* score, hipStream_t stream);
+// ... of a steep plan: the diagonal part re-indexed, and the hand-off columns from the chains' group edges
+// (ef, eb: edge b at b * edge_rows granules) and segment buffers (sf, sb: strip s at s * segr 8-B entries)
+struct SteepJoin {
+    const Granule *bf, *bb, *ef, *eb, *sf, *sb;
+    int edge_rows, segr, m, gap;
+};
+hipError_t launch_sw_flow3_steep_combine(const SteepJoin& j, const WedgePlan& w, unsigned epoch, Ctrl* ctrl, int* score,
+                                         hipStream_t stream);
 // workgroups per CU resident for a flow3 ring-mode launch (its LDS pad of cfg.f2_wgs), -1 on error
 int flow3_ring_resident(const LaunchCfg& cfg);
 int flow2_waves_per_cu(int C);

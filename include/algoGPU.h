@@ -370,7 +370,10 @@ void sw_last_align_ms(float* fill_ms, float* walk_ms);
  *              Under -1 a pair tall and wide enough is scored as two wedges cut along an anti-diagonal
  *              staircase instead (variant bit 18; 0 switches that off too, 1 keeps the column cut); the
  *              environment variable SWMI_F3WEDGE (0 = never, 1 = wherever every strip keeps 64 rows)
- *              overrides the measured thresholds for A/B runs and tests
+ *              overrides the measured thresholds for A/B runs and tests, and SWMI_F3WEDGE_DROPS =
+ *              d0,d1,d2,d3 sets the staircase's drop behind strip j to d[j % 4] rows wherever the steep
+ *              plan admits it (variant bit 19; multiples of 64 from 64 to 256 with d0 == d2, anything
+ *              else fails the launch; 64,64,64,64 is the uniform staircase; unset: the measured default)
  *   "f3pwg"    1 = (default) DNA batches on a pair-per-workgroup plan (scores that need int32, or 1-2
  *              pairs per CU) run flow3's three-column ring step (sw_flow3r3p / ra3p_kernel), 0 = flow2's
  *   "f3slab"   1 = (default) column slabs run flow3's ring kernel with slab roles
@@ -432,7 +435,10 @@ typedef struct {
                                        items and blocks count both halves);
                                bit 18: one pair scored as two wedges cut along an anti-diagonal staircase,
                                        both chains in one launch (automatic under option f3split = -1;
-                                       items and blocks count both chains) */
+                                       items and blocks count both chains);
+                               bit 19: with bit 18, the steep plan: a staircase that drops more than 64
+                                       rows behind some strips, joined along the strips' hand-off
+                                       columns too (environment SWMI_F3WEDGE_DROPS forces a pattern) */
 } sw_stats;
 int sw_last_stats(sw_stats* out);
 

@@ -313,6 +313,10 @@ def gen_role(IN, OUT_, spec=0, halfpub=True, C=32, hl=False):
     # its left ends 64 steps later (its exit flush stops one row short), so lane 0 of a strip with
     # inflow steps on the border value and its second row is not used: lane 63 of the strip on the left
     # holds the same columns one row further down.
+    # And the I/O register of the last step (v65: end is a multiple of 64): its lane 63 holds the outflow
+    # row end - 64, H - G of lane 62's column B, which no publish sends (the exit flush stops at row
+    # end - 65); a steep wedge plan's join needs it (sw_flow3.hip, the hand-off column).
+    a("v_mov_b32 v100, v65")
     a("v_mov_b32 v107, v66")
     a("v_mov_b32 v108, v68")
     a("v_mov_b32 v64, %[ng]")
@@ -324,6 +328,7 @@ def gen_role(IN, OUT_, spec=0, halfpub=True, C=32, hl=False):
     a("v_mov_b32 %[b0], v108")
     a("v_mov_b32 %[a1], v66")
     a("v_mov_b32 %[b1], v68")
+    a("v_mov_b32 %[io], v100")
     a("s_mov_b32 %[fail], s45")
     a("s_mov_b32 %[slow], s46")
     a("s_branch L_done_%=")
@@ -401,7 +406,7 @@ def emit(spec=0, halfpub=True):
                 for line in body:
                     out.append('        "%s\\n\\t"' % line)
                 out.append('        : [M] "=v"(r.M), [fail] "=s"(r.fail), [slow] "=s"(r.slow), [a0] "=v"(r.a0), [b0] "=v"(r.b0),')
-                out.append('          [a1] "=v"(r.a1), [b1] "=v"(r.b1)')
+                out.append('          [a1] "=v"(r.a1), [b1] "=v"(r.b1), [io] "=v"(r.io)')
                 out.append('        : [pA] "v"(x.pA), [pB] "v"(x.pB), [ng] "v"(x.ng), [G] "s"(x.G), [qA] "v"(x.qA),')
                 out.append('          [qB] "v"(x.qB), [code] "v"(x.code), [lin] "v"(x.lin), [lout] "v"(x.lout), [pin] "v"(x.pin),')
                 out.append('          [pout] "v"(x.pout), [qme] "v"(x.qme), [qnx] "v"(x.qnx), [end] "s"(x.end),')

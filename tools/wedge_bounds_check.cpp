@@ -1,7 +1,8 @@
-// Host-only check of the wedge planner's arithmetic (sw_internal.h wedge_bounds): a sweep of n and m with the
-// invariants the kernel and the combine rely on.  Stand-alone, so it can be built with host sanitizers:
+// Host-only check of the wedge planner's arithmetic (sw_internal.h wedge_bounds, steep_bounds): a sweep of n and m
+// with the invariants the kernel and the combine kernels rely on.  Stand-alone, so it can be built with host sanitizers:
 //   hipcc -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined --offload-arch=gfx950 \
 //       -I concurrentproject_amd/csrc tools/wedge_bounds_check.cpp -o build/wedge_bounds_check
+#include <algorithm>
 #include <cstdio>
 #include <vector>
 
@@ -40,9 +41,61 @@ static void check(int n, int m) {
             for (int k = 0; k < 2; ++k) seen.at((size_t)2 * (64 * s + l) + k) = 1;
 }
 
+// The steep plan with drop pattern d: admission, the row sums, and every index the kernel's segment stores and
+// the steep combine kernel's segment pass form (sw_flow3.hip sw_flow3_steep_combine_kernel).
+static void check_steep(int n, int m, const int d[4]) {
+    WedgePlan w{};
+    const long long S = n >= 253 ? (((long long)n - 2 + 125) / 126 + 3) / 4 * 4 : 0;
+    const long long D = S ? swmi::steep_cum(d, S - 1) : 0;
+    const bool ok = swmi::steep_bounds(n, m, d, &w);
+    CHECK(ok == (n >= 253 && n <= 126 * S && m >= D + 65));
+    if (!ok) return;
+    CHECK(w.steep && w.strips == S && S % 4 == 0);
+    CHECK(w.lead >= 0 && w.lead < 4 * 126 && 126LL * S - w.lead == n);
+    CHECK(w.rlead >= 0 && w.rlead < 64 && (m + w.rlead) % 64 == 3);
+    CHECK(w.e0[0] % 64 == 0 && w.e0[1] % 64 == 0);
+    CHECK((long long)w.e0[0] + w.e0[1] == (long long)m + w.rlead + 61 + D);
+    CHECK(w.e0[1] - w.e0[0] == 0 || w.e0[1] - w.e0[0] == 64);
+    CHECK(w.e0[0] - D >= 64 && w.e0[1] - D >= 64);
+    CHECK(w.e0[0] <= m - 1 && w.e0[1] <= m + w.rlead - 1);
+    const long long edge_rows = std::max(w.e0[0], w.e0[1]) + 64;
+    const long long segr = std::max(std::max(d[0], d[1]), std::max(d[2], d[3])) - 62;
+    for (long long s = 0; s + 1 < S; s += (S > 64 && s > 8 && s + 10 < S ? S / 7 : 1)) {
+        const long long s2 = S - 2 - s, drop = d[s & 3];
+        // the mirrored chain's drops are the forward chain's read from the far end: the same pattern
+        CHECK(d[s2 & 3] == drop && ((s & 3) == 3) == ((s2 & 3) == 3));
+        const long long endf = w.e0[0] - swmi::steep_cum(d, s), endb = w.e0[1] - swmi::steep_cum(d, s2);
+        for (long long k = 0; k < drop - 60; ++k) {
+            const long long i = endf - drop + k;                               // node row on the hand-off column
+            const long long kb = (long long)m - 1 + w.rlead - i - (endb - drop - 1);
+            CHECK(kb == drop - 61 - k);
+            for (const long long t : {k, kb}) {                                 // the sources of steep_col_h
+                const long long end = t == k ? endf : endb;
+                if (t <= drop - 64) CHECK(end - drop - 1 + t >= 0 && end - drop - 1 + t <= end - 65 && end - 65 < edge_rows);
+                if (t <= drop - 64) CHECK(1 + t < segr);
+            }
+        }
+    }
+}
+
 int main() {
     for (int n = 1; n <= 3000; ++n)
         for (int m = 1; m <= 2200; m += (n % 7 == 0 ? 1 : 61)) check(n, m);
+    const int pats[][4] = {{64, 64, 64, 128}, {64, 128, 64, 128}, {128, 128, 128, 128}, {64, 64, 64, 192}, {256, 64, 256, 64}};
+    const int bad[][4] = {{64, 64, 128, 64}, {64, 96, 64, 128}, {0, 64, 0, 64}, {64, 64, 64, 320}};
+    for (const auto& d : bad) {
+        WedgePlan w{};
+        if (swmi::wedge_drops_ok(d) || swmi::steep_bounds(1000, 100000, d, &w)) ++fails;
+    }
+    for (const auto& d : pats) {
+        for (int n = 240; n <= 1600; ++n)
+            for (int m = 1; m <= 6000; m += (n % 25 == 0 ? 1 : 53)) check_steep(n, m, d);
+        const int bign[] = {4096, 16384, 65536, 1 << 20};
+        const int bigm[] = {4096, 16384, 65536, 1 << 20, (1 << 27) - 1};
+        for (int n : bign)
+            for (int m : bigm)
+                for (int e = -70; e <= 70; e += 7) check_steep(n, m + e > (1 << 27) - 1 ? m : m + e, d);
+    }
     const int big[] = {4096, 16384, 65536, 1 << 20, (1 << 27) - 1};
     for (int n : big)
         for (int m : big)
