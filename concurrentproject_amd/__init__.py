@@ -25,6 +25,7 @@ __all__ = [
     "SwError", "LIB_PATH", "SW_FLAG_DNA", "SW_FLAG_BYTES", "slab_bounds", "SlabBuffer", "slab_alloc",
     "ipc_open", "ipc_close", "score_slab_device", "Database", "Matrix", "score_matrix", "score_matrix_batch",
     "SW_MATRIX_FOLD_CASE", "Alignment", "align_matrix", "align_matrix_batch", "last_align_ms",
+    "align_matrix_long", "align_long_plan", "last_align_long_ms",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -56,6 +57,11 @@ class _Stats(ctypes.Structure):
 class _Alignment(ctypes.Structure):
     _fields_ = [("score", ctypes.c_int), ("beg1", ctypes.c_int), ("end1", ctypes.c_int), ("beg2", ctypes.c_int),
                 ("end2", ctypes.c_int), ("ncigar", ctypes.c_int), ("cigar_off", ctypes.c_longlong)]
+
+
+class _AlignPlan(ctypes.Structure):
+    _fields_ = [("strips", ctypes.c_int), ("ckpt_bytes", ctypes.c_longlong), ("strip_trace_bytes", ctypes.c_longlong),
+                ("full_trace_bytes", ctypes.c_longlong)]
 
 
 _lib = None
@@ -209,6 +215,16 @@ def lib() -> ctypes.CDLL:
         L.sw_db_align_matrix.restype = i
         L.sw_last_align_ms.argtypes = [ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
         L.sw_last_align_ms.restype = None
+    if hasattr(L, "sw_align_matrix_long"):   # checkpointed traceback of long pairs
+        L.sw_align_matrix_long.argtypes = L.sw_align_matrix_batch.argtypes
+        L.sw_align_matrix_long.restype = i
+        L.sw_db_align_matrix_long.argtypes = L.sw_db_align_matrix.argtypes
+        L.sw_db_align_matrix_long.restype = i
+        L.sw_align_long_plan.argtypes = [i, i, ctypes.POINTER(_AlignPlan)]
+        L.sw_align_long_plan.restype = i
+        fp = ctypes.POINTER(ctypes.c_float)
+        L.sw_last_align_long_ms.argtypes = [fp, fp, fp, ctypes.POINTER(i)]
+        L.sw_last_align_long_ms.restype = None
     _lib = L
     return L
 
@@ -622,11 +638,12 @@ def _align_call(call, n: int, cap: int) -> list:
     return _alignments(out[:n], cigar)
 
 
-def align_matrix_batch(pairs: Iterable[Sequence], matrix: Matrix, gap_init: int, gap_ext: int, cpu: bool = False) -> list:
-    """An :class:`Alignment` per pair under ``matrix`` (seq1 is its first index) with affine gaps, on
-    the GPU (sw_align_matrix_batch: the traced matrix kernel and a walk) or, with ``cpu=True``, from
-    the library's plain full-matrix aligner on the host (sw_align_matrix_cpu), which gives the same
-    result.  Which alignment is reported when several reach the score is fixed (include/algoGPU.h)."""
+# a long call's first guess at the cigar entries: a second call would repeat seconds of device work
+_LONG_CIGAR_CAP = 1 << 16
+
+
+def _align_pairs(f, pairs, matrix, gap_init: int, gap_ext: int, cap: int = 0) -> list:
+    """f: one of the library's sw_align_matrix_* entry points over host pairs."""
     arrs = [(_u8(a), _u8(b)) for a, b in pairs]
     n = len(arrs)
     if n == 0:
@@ -636,9 +653,35 @@ def align_matrix_batch(pairs: Iterable[Sequence], matrix: Matrix, gap_init: int,
     B = (u8p * n)(*[_ptr(y) for _, y in arrs])
     AL = (ctypes.c_int * n)(*[len(x) for x, _ in arrs])
     BL = (ctypes.c_int * n)(*[len(y) for _, y in arrs])
-    f = lib().sw_align_matrix_cpu if cpu else lib().sw_align_matrix_batch
     return _align_call(lambda out, cig, cap, used: f(matrix._handle(), A, AL, B, BL, n, int(gap_init), int(gap_ext),
-                                                     out, cig, cap, used), n, 16 * n)
+                                                     out, cig, cap, used), n, max(16 * n, cap))
+
+
+def align_matrix_batch(pairs: Iterable[Sequence], matrix: Matrix, gap_init: int, gap_ext: int, cpu: bool = False) -> list:
+    """An :class:`Alignment` per pair under ``matrix`` (seq1 is its first index) with affine gaps, on
+    the GPU (sw_align_matrix_batch: the traced matrix kernel and a walk) or, with ``cpu=True``, from
+    the library's plain full-matrix aligner on the host (sw_align_matrix_cpu), which gives the same
+    result.  Which alignment is reported when several reach the score is fixed (include/algoGPU.h)."""
+    return _align_pairs(lib().sw_align_matrix_cpu if cpu else lib().sw_align_matrix_batch, pairs, matrix, gap_init, gap_ext)
+
+
+def align_matrix_long(pairs: Iterable[Sequence], matrix: Matrix, gap_init: int, gap_ext: int) -> list:
+    """:func:`align_matrix_batch` for pairs whose whole trace does not fit option ``trace_mb``: the same
+    alignments, bit for bit, by checkpointed traceback (sw_align_matrix_long): a locate pass keeps the
+    right-edge column of every strip of 512 seq1 positions, then the strips are filled again and
+    walked one at a time, right to left.  Memory: :func:`align_long_plan`."""
+    return _align_pairs(lib().sw_align_matrix_long, pairs, matrix, gap_init, gap_ext, _LONG_CIGAR_CAP)
+
+
+def align_long_plan(n: int, m: int) -> dict:
+    """What :func:`align_matrix_long` needs for one n x m pair under the current ``trace_mb`` and
+    SWMI_ALIGN_CKPT_MB (no GPU call): ``strips``, ``ckpt_bytes``, ``strip_trace_bytes`` and
+    ``full_trace_bytes`` (what :func:`align_matrix_batch` would need).  Raises :class:`SwError` when
+    the pair would be refused."""
+    p = _AlignPlan()
+    _check(lib().sw_align_long_plan(int(n), int(m), ctypes.byref(p)))
+    return {"strips": p.strips, "ckpt_bytes": p.ckpt_bytes, "strip_trace_bytes": p.strip_trace_bytes,
+            "full_trace_bytes": p.full_trace_bytes}
 
 
 def align_matrix(seq1, seq2, matrix: Matrix, gap_init: int, gap_ext: int, cpu: bool = False) -> Alignment:
@@ -651,6 +694,14 @@ def last_align_ms() -> tuple:
     f, w = ctypes.c_float(), ctypes.c_float()
     lib().sw_last_align_ms(ctypes.byref(f), ctypes.byref(w))
     return f.value, w.value
+
+
+def last_align_long_ms() -> dict:
+    """Device time of this thread's last :func:`align_matrix_long` / ``Database.align(long=True)`` call:
+    ``locate_ms``, ``strip_ms`` (the strip fills), ``walk_ms``, and its ``rounds``."""
+    lo, st, wk, r = ctypes.c_float(), ctypes.c_float(), ctypes.c_float(), ctypes.c_int()
+    lib().sw_last_align_long_ms(ctypes.byref(lo), ctypes.byref(st), ctypes.byref(wk), ctypes.byref(r))
+    return {"locate_ms": lo.value, "strip_ms": st.value, "walk_ms": wk.value, "rounds": r.value}
 
 
 from .db import Database  # noqa: E402  (FASTA databases, query x database search)

@@ -14,7 +14,9 @@ With --alignments every hit line gains ``q_beg  q_end  d_beg  d_end  cigar``: th
 ranges of the query and of the record that the alignment covers and its operations (M an aligned
 pair, I a query residue against a gap, D a record residue against a gap; ``*`` for a score of 0).
 Only the top K of each query are aligned.  Without --matrix the alignments are made under the
-equality table of --params over the bytes present (at most 32 distinct ones)."""
+equality table of --params over the bytes present (at most 32 distinct ones).  --long makes the
+same alignments by checkpointed traceback (Database.align(long=True)): for hits so long that a
+whole pair's trace does not fit option trace_mb; the lines are the same."""
 import argparse
 import sys
 import time
@@ -34,7 +36,11 @@ def main(argv=None) -> int:
     ap.add_argument("--matrix", default=None, help="substitution matrix file (NCBI text format); needs --gaps")
     ap.add_argument("--gaps", default=None, help="G_INIT,G_EXT of a --matrix search")
     ap.add_argument("--alignments", action="store_true", help="align the top K hits: ranges and cigar per line")
+    ap.add_argument("--long", action="store_true",
+                    help="with --alignments: checkpointed traceback, for hits whose whole trace does not fit (same lines)")
     a = ap.parse_args(argv)
+    if a.long and not a.alignments:
+        ap.error("--long goes with --alignments")
     if (a.matrix is None) != (a.gaps is None):
         ap.error("--matrix and --gaps go together")
     matrix, gaps = None, (None, None)
@@ -70,7 +76,7 @@ def main(argv=None) -> int:
             sc = scores[q]
             order = np.lexsort((np.arange(len(sc)), -sc.astype(np.int64)))[:a.top]
             if a.alignments:
-                al = db.align(qs.record(q)[1], [int(i) for i in order], amatrix, agaps[0], agaps[1])
+                al = db.align(qs.record(q)[1], [int(i) for i in order], amatrix, agaps[0], agaps[1], long=a.long)
                 for r, (i, x) in enumerate(zip(order, al)):
                     out.write("%d\t%s\t%d\t%d\t%d\t%s\t%d\t%d\t%d\t%d\t%s\n"
                               % (q, qh, r + 1, int(sc[i]), int(i), db.header(int(i)), x.beg1, x.end1, x.beg2, x.end2,

@@ -3,12 +3,16 @@
 // walk's operations into run-length encoded cigar entries, and sw_align_matrix_cpu, a plain
 // full-matrix aligner with exactly the end-cell rule and the walk priorities of the traced kernel
 // (sw_matrix.hip; include/algoGPU.h states both).  It checks the GPU path and is a usable
-// fallback for a machine without a device; it needs n * m bytes a pair.
+// fallback for a machine without a device; it needs n * m bytes a pair.  Also the arithmetic of
+// the checkpointed traceback of long pairs (sw_align_matrix_long): strips, checkpoint and strip
+// trace bytes, the two budgets' refusals and the greedy packing of groups and rounds; the exported
+// sw_align_long_plan (sw_matrix.hip) only reads option "trace_mb" and calls it.
 #include "sw_matrix_host.h"
 #include "../../include/algoGPU.h"
 
 #include <algorithm>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <vector>
 
@@ -114,6 +118,69 @@ int AlignSink::finish(unsigned* cigar, long long cigar_cap, long long* cigar_use
     }
     if (!cig.empty()) std::memcpy(cigar, cig.data(), cig.size() * sizeof(unsigned));
     return 0;
+}
+
+// ---- long pairs: the plan of a checkpointed traceback (sw_matrix_host.h) ----
+
+long long align_strip_steps(long long m) { return (m + ALIGN_STRIP - 1 + 63) / 64 * 64; }
+long long align_strip_trace_bytes(long long m) { return align_strip_steps(m) * 256; }
+long long align_ckpt_stride(long long m) { return (m + 63) / 64 * 64 * 8; }
+long long align_strips(long long n) { return (n + ALIGN_STRIP - 1) / ALIGN_STRIP; }
+
+int align_long_plan(int n, int m, long long trace_budget, long long ckpt_budget, const char* what, int idx,
+                    sw_align_plan* out) {
+    sw_align_plan p{0, 0, 0, 0};
+    if (n > 0 && m > 0) {
+        p.strips = (int)align_strips(n);
+        p.ckpt_bytes = (long long)(p.strips - 1) * align_ckpt_stride(m);
+        p.strip_trace_bytes = align_strip_trace_bytes(m);
+        p.full_trace_bytes = (long long)p.strips * p.strip_trace_bytes;
+    }
+    *out = p;
+    char msg[256];
+    if (p.ckpt_bytes > ckpt_budget) {
+        std::snprintf(msg, sizeof msg,
+                      "%s %d: a %d x %d alignment needs %lld bytes of checkpoints, more than SWMI_ALIGN_CKPT_MB = %lld MiB",
+                      what, idx, n, m, p.ckpt_bytes, ckpt_budget >> 20);
+        report_error(msg);
+        return -1;
+    }
+    if (p.strip_trace_bytes > trace_budget) {
+        std::snprintf(msg, sizeof msg,
+                      "%s %d: a %d x %d alignment needs %lld bytes of trace memory for one strip, more than option "
+                      "trace_mb = %lld MiB",
+                      what, idx, n, m, p.strip_trace_bytes, trace_budget >> 20);
+        report_error(msg);
+        return -1;
+    }
+    return 0;
+}
+
+int align_ckpt_budget(long long* bytes) {
+    long long mb = 4096;
+    if (const char* e = std::getenv("SWMI_ALIGN_CKPT_MB")) {
+        char* end = nullptr;
+        mb = std::strtoll(e, &end, 10);
+        if (end == e || *end != 0 || mb < 1 || mb > (1LL << 40)) {
+            report_error("SWMI_ALIGN_CKPT_MB must be a whole number of MiB, at least 1");
+            return -1;
+        }
+    }
+    *bytes = mb << 20;
+    return 0;
+}
+
+void align_pack(const long long* need, int n, long long budget, std::vector<int>& end) {
+    end.clear();
+    int k = 0;
+    while (k < n) {
+        long long sum = 0;
+        for (; k < n; ++k) {
+            if (sum > 0 && need[k] > 0 && sum + need[k] > budget) break;
+            sum += need[k];
+        }
+        end.push_back(k);
+    }
 }
 
 namespace {

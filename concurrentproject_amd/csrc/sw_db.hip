@@ -264,14 +264,16 @@ int search_matrix(sw_db* db, const sw_matrix* mx, const unsigned char* query, in
     return 0;
 }
 
-// the query (seq1, across the lanes) aligned with the chosen records, out of the device arena
+// the query (seq1, across the lanes) aligned with the chosen records, out of the device arena;
+// long_pairs: by checkpointed traceback (sw_db_align_matrix_long)
 int align_matrix(sw_db* db, const sw_matrix* mx, const unsigned char* query, int qlen, const int* record_idx, int nidx,
-                 int gap_init, int gap_ext, AlignSink& sink) {
+                 int gap_init, int gap_ext, AlignSink& sink, bool long_pairs) {
     const int nrec = (int)db->len.size();
     for (int k = 0; k < nidx; ++k)
         if (record_idx[k] < 0 || record_idx[k] >= nrec) {
             char m[120];
-            std::snprintf(m, sizeof m, "sw_db_align_matrix: record index %d (entry %d) is outside [0, %d)", record_idx[k], k, nrec);
+            std::snprintf(m, sizeof m, "sw_db_align_matrix%s: record index %d (entry %d) is outside [0, %d)",
+                          long_pairs ? "_long" : "", record_idx[k], k, nrec);
             report_error(m);
             return -1;
         }
@@ -287,8 +289,9 @@ int align_matrix(sw_db* db, const sw_matrix* mx, const unsigned char* query, int
         b_off[(size_t)k] = db->off[(size_t)record_idx[k]];
         blen[(size_t)k] = db->len[(size_t)record_idx[k]];
     }
-    return matrix_align_device(mx, v->arena, a_off.data(), alen.data(), b_off.data(), blen.data(), record_idx, nidx,
-                               gap_init, gap_ext, "record", sink);
+    const auto align_device = long_pairs ? matrix_align_long_device : matrix_align_device;
+    return align_device(mx, v->arena, a_off.data(), alen.data(), b_off.data(), blen.data(), record_idx, nidx, gap_init,
+                        gap_ext, "record", sink);
 }
 
 }  // namespace
@@ -336,7 +339,21 @@ int sw_db_align_matrix(sw_db* db, const sw_matrix* mx, const unsigned char* quer
     }
     std::lock_guard<std::mutex> g(db->mu);
     AlignSink sink{out, {}};
-    if (align_matrix(db, mx, query, qlen, record_idx, nidx, gap_init, gap_ext, sink)) return -1;
+    if (align_matrix(db, mx, query, qlen, record_idx, nidx, gap_init, gap_ext, sink, false)) return -1;
+    return sink.finish(cigar, cigar_cap, cigar_used);
+}
+
+int sw_db_align_matrix_long(sw_db* db, const sw_matrix* mx, const unsigned char* query, int qlen, const int* record_idx,
+                            int nidx, int gap_init, int gap_ext, sw_alignment* out, unsigned* cigar, long long cigar_cap,
+                            long long* cigar_used) {
+    if (!db || !mx || qlen < 0 || (qlen > 0 && !query) || nidx < 0 || cigar_cap < 0 || !cigar_used ||
+        (cigar_cap > 0 && !cigar) || (nidx > 0 && (!record_idx || !out))) {
+        report_error("sw_db_align_matrix_long: invalid arguments");
+        return -1;
+    }
+    std::lock_guard<std::mutex> g(db->mu);
+    AlignSink sink{out, {}};
+    if (align_matrix(db, mx, query, qlen, record_idx, nidx, gap_init, gap_ext, sink, true)) return -1;
     return sink.finish(cigar, cigar_cap, cigar_used);
 }
 

@@ -34,8 +34,10 @@
 // and reports the end cell with the maximum; sw_matrix_walk_kernel then follows the recorded
 // decisions from the end cell, one lane a pair, and the host reverses and run-length encodes
 // (sw_align_host.cpp).  The end-cell rule and the walk priorities are in include/algoGPU.h.  A launch
-// holds at most option "trace_mb" MiB of trace; a pair that does not fit alone is refused:
-// linear-space alignment of very long pairs is not built.
+// holds at most option "trace_mb" MiB of trace; a pair that does not fit alone is refused there.
+// Such pairs go through sw_align_matrix_long: a locate pass that keeps every strip's right-edge
+// column (a checkpoint), then the strips filled again one at a time, traced, from the checkpoint on
+// their left, and walked right to left -- the same bits, so the same alignment (LONG PAIRS below).
 #include "sw_device.h"
 #include "sw_matrix_host.h"
 #include "../../include/algoGPU.h"
@@ -61,6 +63,7 @@ constexpr int MAT_SENT = -127;                       // s of a cell without a ro
 constexpr int MAT_C = 64;                            // rows per inflow / outflow chunk
 constexpr int MODE_MATRIX = 6;
 constexpr int MODE_MATRIX_TRACE = 7;                 // the traced launches (alignments)
+constexpr int MODE_MATRIX_LONG = 8;                  // checkpointed traceback of long pairs (sw_align_matrix_long)
 constexpr int TRACE_W = 8;                           // the traced variant's columns per lane: a step is a dword a lane
 
 struct MatPair {
@@ -113,13 +116,17 @@ static_assert(MAT_TAB_BYTES % 4 == 0, "table words");
 
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
-template <int W, bool TRACE>
+// MODE: M_SCORE the maximum only; M_TRACE the traced step: the end-cell bookkeeping and a dword of
+// decisions a lane a step; M_LOCATE the bookkeeping without the stores (long pairs, below).
+constexpr int M_SCORE = 0, M_TRACE = 1, M_LOCATE = 2;
+
+template <int W, int MODE>
 struct MStrip {
-    static_assert(!TRACE || W == TRACE_W, "a traced step stores one dword a lane");
+    static_assert(MODE == M_SCORE || W == TRACE_W, "a traced step stores one dword a lane");
     int cb[W], tb[W];                       // LDS offset of the column's table row / bias
     int hgA[W], hgB[W], eh[W], r[W], fh[W]; // DP state, as Strip (sw_kernels.hip)
     int L0, M, IOH, IOE, IOR;
-    int Mkp, kp8;                           // TRACE: step * 8 + p at which M was reached; this step * 8
+    int Mkp, kp8;                           // M_TRACE, M_LOCATE: step * 8 + p at which M was reached; this step * 8
 
     __device__ __forceinline__ void setup(const MatArgs& a, const MatPair& pd, int strip, int lane,
                                           const unsigned char* s_code) {
@@ -146,9 +153,9 @@ struct MStrip {
     }
 
     // One anti-diagonal step (Strip::step with the score from the LDS table).
-    // TRACE: the step's cells go to trc at byte toff (the lane's dword of this step), and M is
-    // updated strictly, so that a lane keeps the first step (anti-diagonal) that reached its
-    // maximum and, within a step, the largest p: the smallest row.
+    // M_TRACE: the step's cells go to trc at byte toff (the lane's dword of this step).  M_TRACE and
+    // M_LOCATE: M is updated strictly, so that a lane keeps the first step (anti-diagonal) that
+    // reached its maximum and, within a step, the largest p: the smallest row.
     __device__ __forceinline__ void step(int (&hgCur)[W], const int (&hgPrev)[W], const bool l63, const int go,
                                          const int ge, const signed char* s_tab, const __amdgpu_buffer_rsrc_t trc,
                                          unsigned& toff) {
@@ -172,12 +179,14 @@ struct MStrip {
             const int E = max3i(ehL, hgL, 0);            // clamped E
             const int F = max3i(fh[p], hgPrev[p], 0);    // clamped F
             const int H = vmax3(t, E, F);
-            if constexpr (TRACE) {
+            if constexpr (MODE != M_SCORE) {
                 const bool up = t > M;
                 M = up ? t : M;
                 Mkp = up ? kp8 + p : Mkp;
-                const unsigned src = H == 0 ? 0u : (t == H ? 1u : (E == H ? 2u : 3u));
-                bits |= (src | (ehL > hgL ? 4u : 0u) | (fh[p] > hgPrev[p] ? 8u : 0u)) << (4 * p);
+                if constexpr (MODE == M_TRACE) {
+                    const unsigned src = H == 0 ? 0u : (t == H ? 1u : (E == H ? 2u : 3u));
+                    bits |= (src | (ehL > hgL ? 4u : 0u) | (fh[p] > hgPrev[p] ? 8u : 0u)) << (4 * p);
+                }
             } else {
                 M = max(M, t);
             }
@@ -190,11 +199,11 @@ struct MStrip {
         IOH = l63 ? hgCur[W - 1] : ioh;   // lane 63 <- this step's right-edge output
         IOE = l63 ? eh[W - 1] : ioe;
         IOR = ior;
-        if constexpr (TRACE) {
+        if constexpr (MODE == M_TRACE) {
             __builtin_amdgcn_raw_buffer_store_b32(bits, trc, toff, 0, 0);
             toff += 256u;
-            kp8 += 8;
         }
+        if constexpr (MODE != M_SCORE) kp8 += 8;
     }
 
     __device__ __forceinline__ void run(const bool l63, const int go, const int ge, const signed char* s_tab,
@@ -220,9 +229,14 @@ __device__ __forceinline__ u32x2 mat_fetch_edge(const __amdgpu_buffer_rsrc_t scr
 // more than one strip).  TRACE: wp is the pair's trace buffer; the result is the maximum with its end
 // cell -- among the cells whose t equals the maximum, the smallest i + j, then the smallest row j
 // (include/algoGPU.h) -- so each strip starts its own M and the strips are merged by that rule.
-template <int W, bool TRACE>
+// M_LOCATE: the same result without a trace; strip s reads its inflow from checkpoint column s - 1
+// of the pair and stores its right edge to column s (ckpt: column 0, ckpt_stride bytes a column,
+// m * 8 of them used), every column a buffer of its own, and the scratch is not touched.
+template <int W, int MODE>
 __device__ void matrix_pair(const MatArgs& a, const MatPair& pd, const WalkPair& wp, const int lane, uint2* scr,
-                            const signed char* s_tab, const unsigned char* s_code) {
+                            const signed char* s_tab, const unsigned char* s_code, unsigned char* ckpt = nullptr,
+                            unsigned ckpt_stride = 0) {
+    constexpr bool TRACE = MODE != M_SCORE;   // the end cell is kept
     constexpr int SW = 64 * W, C = MAT_C;
     const int m = pd.m;
     const int go = a.gap_init, ge = a.gap_ext;
@@ -232,15 +246,16 @@ __device__ void matrix_pair(const MatArgs& a, const MatPair& pd, const WalkPair&
         __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(a.seq + pd.row_off), 0, m, RSRC_FLAGS);
     // a single strip never touches the scratch: a resource of no bytes drops every access
     const __amdgpu_buffer_rsrc_t scr_rsrc =
-        __builtin_amdgcn_make_buffer_rsrc(scr, 0, strips > 1 ? (int)((unsigned)m * 8u) : 0, RSRC_FLAGS);
+        __builtin_amdgcn_make_buffer_rsrc(scr, 0, MODE != M_LOCATE && strips > 1 ? (int)((unsigned)m * 8u) : 0, RSRC_FLAGS);
     const int nchunks = (m + SW - 1 + C - 1) / C;
     // every store of a step is inside the buffer by construction (strips * steps * 256 bytes); the
     // resource drops whatever is not
     const __amdgpu_buffer_rsrc_t trc =
-        TRACE ? __builtin_amdgcn_make_buffer_rsrc(a.trace + wp.trace_off, 0, (int)wp.trace_bytes, RSRC_FLAGS) : scr_rsrc;
+        MODE == M_TRACE ? __builtin_amdgcn_make_buffer_rsrc(a.trace + wp.trace_off, 0, (int)wp.trace_bytes, RSRC_FLAGS)
+                        : scr_rsrc;
     unsigned toff = (unsigned)lane * 4u;
     int bM = 0, bD = 0, bJ = 0;   // TRACE: the best of the strips so far: t, i + j, j
-    MStrip<W, TRACE> S;
+    MStrip<W, MODE> S;
     S.M = 0;
     for (int strip = 0; strip < strips; ++strip) {
         S.setup(a, pd, strip, lane, s_code);
@@ -251,15 +266,22 @@ __device__ void matrix_pair(const MatArgs& a, const MatPair& pd, const WalkPair&
         }
         const bool has_in = strip > 0;
         const bool has_out = strip < strips - 1;
+        __amdgpu_buffer_rsrc_t in_rsrc = scr_rsrc, out_rsrc = scr_rsrc;
+        if constexpr (MODE == M_LOCATE) {   // a column that is not there (strip 0's left, the last strip's right) has no bytes
+            in_rsrc = __builtin_amdgcn_make_buffer_rsrc(ckpt + (uint64_t)(has_in ? strip - 1 : 0) * ckpt_stride, 0,
+                                                        has_in ? (int)((unsigned)m * 8u) : 0, RSRC_FLAGS);
+            out_rsrc = __builtin_amdgcn_make_buffer_rsrc(ckpt + (uint64_t)(has_out ? strip : 0) * ckpt_stride, 0,
+                                                         has_out ? (int)((unsigned)m * 8u) : 0, RSRC_FLAGS);
+        }
         unsigned raw_nxt = mat_fetch_raw(row_rsrc, 0, lane, m);
-        u32x2 g_nxt = has_in ? mat_fetch_edge(scr_rsrc, 0, lane, m) : u32x2{0u, 0u};
+        u32x2 g_nxt = has_in ? mat_fetch_edge(in_rsrc, 0, lane, m) : u32x2{0u, 0u};
         for (int c = 0; c < nchunks; ++c) {
             const int k0 = c * C;
             const unsigned raw = raw_nxt;
             const u32x2 g = g_nxt;
             // the next chunk's rows in flight while this chunk computes
             raw_nxt = mat_fetch_raw(row_rsrc, k0 + C, lane, m);
-            if (has_in) g_nxt = mat_fetch_edge(scr_rsrc, k0 + C, lane, m);
+            if (has_in) g_nxt = mat_fetch_edge(in_rsrc, k0 + C, lane, m);
             const bool live = k0 + lane < m;
             S.IOR = live ? (int)s_code[raw & 0xFFu] : a.k;
             S.IOH = has_in && live ? (int)g.x : -go;
@@ -268,7 +290,7 @@ __device__ void matrix_pair(const MatArgs& a, const MatPair& pd, const WalkPair&
             if (has_out) {   // lane l holds the right edge of row k0 + l - (SW - 1)
                 const int row_out = k0 + lane - (SW - 1);
                 const bool st = row_out >= 0 && row_out < m;
-                __builtin_amdgcn_raw_buffer_store_b64(u32x2{(unsigned)S.IOH, (unsigned)S.IOE}, scr_rsrc,
+                __builtin_amdgcn_raw_buffer_store_b64(u32x2{(unsigned)S.IOH, (unsigned)S.IOE}, out_rsrc,
                                                       st ? (unsigned)row_out * 8u : OOR, 0, AUX_SC1);
             }
         }
@@ -341,7 +363,7 @@ __global__ void __launch_bounds__(256) sw_matrix_kernel(MatArgs a) {
             wp.trace_off = uniform64(wraw.trace_off);
             wp.trace_bytes = __builtin_amdgcn_readfirstlane(wraw.trace_bytes);
         }
-        matrix_pair<W, TRACE>(a, pd, wp, lane, scr, s_tab, s_code);
+        matrix_pair<W, TRACE ? M_TRACE : M_SCORE>(a, pd, wp, lane, scr, s_tab, s_code);
     }
 }
 
@@ -411,6 +433,231 @@ __global__ void __launch_bounds__(64) sw_matrix_walk_kernel(WalkArgs w) {
     r->err = err;
 }
 
+// ---- LONG PAIRS: checkpointed traceback, one strip at a time (sw_align_matrix_long) -----------
+//
+// The only state that crosses a strip boundary is the right-edge column.  The locate pass
+// (matrix_pair<TRACE_W, M_LOCATE>) keeps every strip's column instead of overwriting one scratch
+// column, and reports the end cell.  Any strip can then be filled again on its own from the column
+// on its left with the traced step: the same recurrence on the same integers, so the same 4 bits a
+// cell as the whole traced fill would have stored.  The walk needs one strip at a time, right to
+// left: a round fills, for every pair still walking, the strip its walk stands in -- rows [0, j]
+// only, j the row at which the walk enters the strip -- into a one-strip buffer (the layout above
+// with strip index 0), and sw_matrix_walk_strip_kernel walks on through it, appending operations,
+// until the walk ends or leaves the strip on the left.  The host runs the rounds (below).  As in the
+// kernels above no wave waits for another and every loop is bounded: chunks of the strip, n + m
+// operations.
+
+struct LongPair {           // locate: per item, beside its MatPair
+    uint64_t ckpt_off;      // bytes, from LongArgs::ckpt: checkpoint column 0 of the pair
+    unsigned ckpt_stride;   // bytes a column: align_ckpt_stride(m) (m * 8 of them used)
+    unsigned pad;
+};
+struct StripItem {          // strip fill and walk: one strip of one pair
+    uint64_t col_off, row_off;   // as MatPair (seq1 across the lanes)
+    uint64_t ckpt_in;       // bytes, from LongArgs::ckpt: checkpoint column strip - 1 (strip > 0)
+    uint64_t trace_off;     // bytes, from LongArgs::trace: the item's one-strip buffer
+    uint64_t ops_off;       // bytes, from WalkStripArgs::ops: the pair's n + m operation bytes
+    int n, m;               // the pair
+    int strip;              // seq1 positions [512 * strip, 512 * strip + 512)
+    int rows;               // j + 1: rows [0, j] are filled
+    unsigned trace_bytes;   // of the item's buffer: at least align_strip_trace_bytes(rows)
+    int slot;               // the pair's WalkState
+};
+struct WalkState {          // 32 B a pair, read by the host after every round
+    int i, j, state;        // where the walk stands: the cell, and 0 H, 1 E, 2 F
+    int nops, err, done;    // operations written so far, WALK_* error, 1: the walk has ended
+    int pad0, pad1;
+};
+static_assert(sizeof(WalkState) == 32, "walk state");
+struct LongArgs {
+    const LongPair* lp;         // locate
+    unsigned char* ckpt;
+    const StripItem* items;     // strip fill: MatArgs::npairs of them
+    unsigned char* trace;
+};
+
+__device__ __forceinline__ void matrix_stage(const MatArgs& a, unsigned* s_tabw, unsigned* s_codew) {
+    for (int i = threadIdx.x; i < 2 * MAT_TAB_BYTES / 4; i += 256) s_tabw[i] = a.tab[i];
+    if (threadIdx.x < 64) s_codew[threadIdx.x] = a.code[threadIdx.x];
+    __syncthreads();
+}
+
+// The locate pass: sw_matrix_kernel<8, true> without the trace, every strip's right edge kept.
+// a.res[out_idx] receives score, ei, ej (the first half of a TraceRes).
+__global__ void __launch_bounds__(256) sw_matrix_locate_kernel(MatArgs a, LongArgs x) {
+    __shared__ unsigned s_tabw[2 * MAT_TAB_BYTES / 4];
+    __shared__ unsigned s_codew[64];
+    matrix_stage(a, s_tabw, s_codew);
+    const signed char* s_tab = reinterpret_cast<const signed char*>(s_tabw);
+    const unsigned char* s_code = reinterpret_cast<const unsigned char*>(s_codew);
+    const int lane = threadIdx.x & 63;
+    for (;;) {
+        unsigned item = 0;
+        if (lane == 0) item = atomicAdd(&a.ctrl->next_item, 1u);
+        item = __builtin_amdgcn_readfirstlane(item);
+        if ((int)item >= a.npairs) return;
+        const MatPair raw = a.pairs[item];
+        const LongPair lraw = x.lp[item];
+        MatPair pd;   // every field provably wave-uniform (buffer descriptors live in SGPRs)
+        pd.col_off = uniform64(raw.col_off);
+        pd.row_off = uniform64(raw.row_off);
+        pd.n = __builtin_amdgcn_readfirstlane(raw.n);
+        pd.m = __builtin_amdgcn_readfirstlane(raw.m);
+        pd.out_idx = __builtin_amdgcn_readfirstlane(raw.out_idx);
+        pd.swapped = 0;
+        unsigned char* ckpt = x.ckpt + uniform64(lraw.ckpt_off);
+        const unsigned stride = __builtin_amdgcn_readfirstlane(lraw.ckpt_stride);
+        matrix_pair<TRACE_W, M_LOCATE>(a, pd, WalkPair{}, lane, nullptr, s_tab, s_code, ckpt, stride);
+    }
+}
+
+// One strip of one pair, traced, rows [0, it.rows): inflow from the checkpoint column on its left
+// (the border for strip 0), no outflow, no end cell.  Every store of a step is inside the item's
+// buffer by construction (align_strip_trace_bytes(rows) <= trace_bytes); the resource drops
+// whatever is not.
+__device__ void matrix_strip_fill(const MatArgs& a, const LongArgs& x, const StripItem& it, const int lane,
+                                  const signed char* s_tab, const unsigned char* s_code) {
+    constexpr int W = TRACE_W, SW = 64 * W, C = MAT_C;
+    const int m = it.rows;
+    const int go = a.gap_init, ge = a.gap_ext;
+    const bool l63 = lane == 63;
+    const bool has_in = it.strip > 0;
+    MatPair pd;
+    pd.col_off = it.col_off;
+    pd.row_off = it.row_off;
+    pd.n = it.n;
+    pd.m = m;
+    pd.out_idx = 0;
+    pd.swapped = 0;
+    const __amdgpu_buffer_rsrc_t row_rsrc =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(a.seq + it.row_off), 0, m, RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t in_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+        x.ckpt + (has_in ? it.ckpt_in : 0), 0, has_in ? (int)((unsigned)m * 8u) : 0, RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t trc =
+        __builtin_amdgcn_make_buffer_rsrc(x.trace + it.trace_off, 0, (int)it.trace_bytes, RSRC_FLAGS);
+    const int nchunks = (m + SW - 1 + C - 1) / C;
+    unsigned toff = (unsigned)lane * 4u;
+    MStrip<W, M_TRACE> S;
+    S.setup(a, pd, it.strip, lane, s_code);
+    S.M = 0;
+    S.Mkp = 0;
+    S.kp8 = 0;
+    unsigned raw_nxt = mat_fetch_raw(row_rsrc, 0, lane, m);
+    u32x2 g_nxt = has_in ? mat_fetch_edge(in_rsrc, 0, lane, m) : u32x2{0u, 0u};
+    for (int c = 0; c < nchunks; ++c) {
+        const int k0 = c * C;
+        const unsigned raw = raw_nxt;
+        const u32x2 g = g_nxt;
+        raw_nxt = mat_fetch_raw(row_rsrc, k0 + C, lane, m);
+        if (has_in) g_nxt = mat_fetch_edge(in_rsrc, k0 + C, lane, m);
+        const bool live = k0 + lane < m;
+        S.IOR = live ? (int)s_code[raw & 0xFFu] : a.k;
+        S.IOH = has_in && live ? (int)g.x : -go;
+        S.IOE = has_in && live ? (int)g.y : -ge;
+        S.run(l63, go, ge, s_tab, trc, toff);
+    }
+}
+
+__global__ void __launch_bounds__(256) sw_matrix_strip_kernel(MatArgs a, LongArgs x) {
+    __shared__ unsigned s_tabw[2 * MAT_TAB_BYTES / 4];
+    __shared__ unsigned s_codew[64];
+    matrix_stage(a, s_tabw, s_codew);
+    const signed char* s_tab = reinterpret_cast<const signed char*>(s_tabw);
+    const unsigned char* s_code = reinterpret_cast<const unsigned char*>(s_codew);
+    const int lane = threadIdx.x & 63;
+    for (;;) {
+        unsigned item = 0;
+        if (lane == 0) item = atomicAdd(&a.ctrl->next_item, 1u);
+        item = __builtin_amdgcn_readfirstlane(item);
+        if ((int)item >= a.npairs) return;
+        const StripItem raw = x.items[item];
+        StripItem it{};   // every field used provably wave-uniform
+        it.col_off = uniform64(raw.col_off);
+        it.row_off = uniform64(raw.row_off);
+        it.ckpt_in = uniform64(raw.ckpt_in);
+        it.trace_off = uniform64(raw.trace_off);
+        it.n = __builtin_amdgcn_readfirstlane(raw.n);
+        it.strip = __builtin_amdgcn_readfirstlane(raw.strip);
+        it.rows = __builtin_amdgcn_readfirstlane(raw.rows);
+        it.trace_bytes = __builtin_amdgcn_readfirstlane(raw.trace_bytes);
+        matrix_strip_fill(a, x, it, lane, s_tab, s_code);
+    }
+}
+
+// The resumable walk: sw_matrix_walk_kernel's loop from the pair's WalkState, while the cell is in
+// the item's strip; the cell at column i - 512 * strip of the one-strip buffer.  Operations are
+// appended at the running offset nops.  done: a cell with H = 0 met in state H, or i < 0, or j < 0.
+// Otherwise the walk left the strip through its left side, in state H (after an M) or E (after an
+// I): the state the last cell's extend bit decided, exactly as inside a strip.
+struct WalkStripArgs {
+    const StripItem* items;
+    const unsigned char* trace;
+    unsigned char* ops;
+    WalkState* st;
+    int nitems;
+};
+
+__global__ void __launch_bounds__(64) sw_matrix_walk_strip_kernel(WalkStripArgs w) {
+    const int item = (int)(blockIdx.x * 64 + threadIdx.x);
+    if (item >= w.nitems) return;
+    const StripItem it = w.items[item];
+    WalkState* s = w.st + it.slot;
+    int i = s->i, j = s->j, state = s->state, nops = s->nops, err = s->err, done = s->done;
+    if (done || err) return;
+    const long long limit = (long long)it.n + it.m;
+    const int lo = it.strip * (64 * TRACE_W);
+    const unsigned* tr = reinterpret_cast<const unsigned*>(w.trace + it.trace_off);
+    unsigned char* ops = w.ops + it.ops_off;
+    if (i >= it.n || j >= it.m || i < lo || i >= lo + 64 * TRACE_W || j >= it.rows || j < 0 || nops < 0 || state < 0 ||
+        state > 2)
+        err = WALK_RANGE;
+    while (err == 0) {
+        if (i < 0 || j < 0) {
+            done = 1;
+            break;
+        }
+        if (i < lo) break;   // the next round's strip
+        const int cl = i - lo;
+        const unsigned long long dw = (unsigned long long)(unsigned)(j + cl) * 64u + (unsigned)(cl >> 3);
+        if (dw * 4u >= it.trace_bytes) {
+            err = WALK_RANGE;
+            break;
+        }
+        const unsigned nib = (tr[dw] >> (4 * (cl & 7))) & 15u;
+        if (state == 0) {
+            const unsigned src = nib & 3u;
+            if (src == 0) {
+                done = 1;
+                break;
+            }
+            if (src != 1) state = (int)src - 1;   // E: 1, F: 2
+        }
+        if (nops >= limit) {
+            err = WALK_OVERRUN;
+            break;
+        }
+        if (state == 0) {
+            ops[nops++] = 0;
+            --i;
+            --j;
+        } else if (state == 1) {
+            ops[nops++] = 1;
+            state = (nib & 4u) ? 1 : 0;
+            --i;
+        } else {
+            ops[nops++] = 2;
+            state = (nib & 8u) ? 2 : 0;
+            --j;
+        }
+    }
+    s->i = i;
+    s->j = j;
+    s->state = state;
+    s->nops = nops;
+    s->err = err;
+    s->done = done;
+}
+
 // ---- host ------------------------------------------------------------------------------------
 
 #define MCHK(expr)                                                                           \
@@ -429,12 +676,16 @@ struct MatCtx {
     int cus = 256;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
-    void* buf[9] = {};      // pairs, ctrl, scratch, arena, scores; traced launches: walk pairs, trace, results, operations
-    size_t cap[9] = {};
-    int wgs[5] = {0, 0, 0, 0, 0};   // resident workgroups per CU per W variant; [4]: the traced kernel
+    void* buf[13] = {};     // pairs, ctrl, scratch, arena, scores; traced launches: walk pairs, trace, results, operations;
+                            // long pairs: locate items, checkpoints, strip items, walk states
+    size_t cap[13] = {};
+    int wgs[7] = {0, 0, 0, 0, 0, 0, 0};   // resident workgroups per CU per W variant; [4]: the traced kernel,
+                                          // [5], [6]: the locate and the strip-fill kernel
 };
-enum { B_PAIRS = 0, B_CTRL, B_SCRATCH, B_ARENA, B_SCORES, B_WALK, B_TRACE, B_RES, B_OPS };
+enum { B_PAIRS = 0, B_CTRL, B_SCRATCH, B_ARENA, B_SCORES, B_WALK, B_TRACE, B_RES, B_OPS, B_LONG, B_CKPT, B_ITEMS, B_STATE };
 thread_local float t_fill_ms = 0.f, t_walk_ms = 0.f;   // sw_last_align_ms
+thread_local float t_locate_ms = 0.f;                  // sw_last_align_long_ms: the locate launches' share of t_fill_ms
+thread_local int t_rounds = 0;                         // and the rounds, summed over the call's groups
 thread_local std::map<int, MatCtx*> t_mctx;
 
 MatCtx* get_mctx() {
@@ -805,7 +1056,260 @@ int launch_traced(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, 
     return 0;
 }
 
+// ---- long pairs: the host side of the checkpointed traceback ----
+
+// workgroups of a claim-loop launch over `items` items (option "blocks" as in launch_traced)
+int long_blocks(MatCtx* c, int which, const void* kernel, size_t items, long long* out) {
+    if (c->wgs[which] == 0) {
+        int nb = 0;
+        MCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, 256, 0));
+        c->wgs[which] = std::max(1, std::min(nb, 8));
+    }
+    long long blocks = sw_get_option("blocks");
+    if (blocks <= 0) blocks = (long long)c->cus * c->wgs[which];
+    *out = std::max<long long>(1, std::min<long long>(blocks, ((long long)items + 3) / 4));
+    return 0;
+}
+
+int walk_failed(const char* what, int idx, int err) {
+    char m[200];
+    std::snprintf(m, sizeof m, "%s %d: the traceback walk failed (%s)", what, idx,
+                  err == WALK_OVERRUN ? "more than n + m operations"
+                  : err == WALK_RANGE ? "a cell outside the trace buffer"
+                                      : "it did not leave its strip on the left");
+    report_error(m);
+    return -1;
+}
+
+// One group: pairs whose checkpoints are held together.  act: the pairs (both lengths > 0, idx = the
+// input index, for messages), in input order.  The locate launch, then rounds of strip fill + walk;
+// res[s], ws[s] and the operations (ops, at ops_off[s], ws[s].nops of them, last first) of act[s]
+// come back to the host.
+struct LongOut {
+    std::vector<TraceRes> res;
+    std::vector<WalkState> ws;
+    std::vector<unsigned char> ops;
+    std::vector<uint64_t> ops_off;
+};
+int long_group(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, const std::vector<DevSeq>& act, int gap_init,
+               int gap_ext, long long trace_budget, const char* what, const int* name_idx, sw_stats& st, LongOut& o) {
+    const size_t np = act.size();
+    std::vector<int> order(np);
+    std::iota(order.begin(), order.end(), 0);
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) {   // longest first: the waves claim in order
+        return (long long)act[x].alen * act[x].blen > (long long)act[y].alen * act[y].blen;
+    });
+    std::vector<uint64_t> ckpt_off(np);
+    o.ops_off.assign(np, 0);
+    uint64_t ops_total = 0, ckpt_total = 0;
+    long long max_strips = 0;
+    for (size_t s = 0; s < np; ++s) {
+        o.ops_off[s] = ops_total;
+        ops_total += (uint64_t)act[s].alen + (uint64_t)act[s].blen;
+        ckpt_off[s] = ckpt_total;
+        ckpt_total += (uint64_t)((align_strips(act[s].alen) - 1) * align_ckpt_stride(act[s].blen));
+        max_strips = std::max(max_strips, align_strips(act[s].alen));
+    }
+    std::vector<MatPair> pairs(np);
+    std::vector<LongPair> lp(np);
+    for (size_t k = 0; k < np; ++k) {
+        const DevSeq& p = act[(size_t)order[k]];
+        pairs[k] = MatPair{(uint64_t)p.a_off, (uint64_t)p.b_off, p.alen, p.blen, order[k], 0};
+        lp[k] = LongPair{ckpt_off[(size_t)order[k]], (unsigned)align_ckpt_stride(p.blen), 0u};
+    }
+    long long blocks = 0;
+    if (long_blocks(c, 5, (const void*)sw_matrix_locate_kernel, np, &blocks)) return -1;
+    if (ensure(c, B_PAIRS, np * sizeof(MatPair)) || ensure(c, B_CTRL, sizeof(Ctrl)) || ensure(c, B_LONG, np * sizeof(LongPair)) ||
+        ensure(c, B_CKPT, (size_t)ckpt_total) || ensure(c, B_RES, np * sizeof(TraceRes)) ||
+        ensure(c, B_OPS, (size_t)ops_total) || ensure(c, B_STATE, np * sizeof(WalkState)))
+        return -1;
+    MCHK(hipMemcpyAsync(c->buf[B_PAIRS], pairs.data(), np * sizeof(MatPair), hipMemcpyHostToDevice, c->stream));
+    MCHK(hipMemcpyAsync(c->buf[B_LONG], lp.data(), np * sizeof(LongPair), hipMemcpyHostToDevice, c->stream));
+    MCHK(hipMemsetAsync(c->buf[B_CTRL], 0, sizeof(Ctrl), c->stream));
+    MCHK(hipMemsetAsync(c->buf[B_RES], 0, np * sizeof(TraceRes), c->stream));
+
+    MatArgs a{};
+    a.seq = d_arena;
+    a.pairs = (const MatPair*)c->buf[B_PAIRS];
+    a.ctrl = (Ctrl*)c->buf[B_CTRL];
+    a.npairs = (int)np;
+    a.nscores = (int)np;
+    a.gap_init = gap_init;
+    a.gap_ext = gap_ext;
+    stage_matrix(a, mx);
+    a.res = (TraceRes*)c->buf[B_RES];
+    LongArgs x{};
+    x.lp = (const LongPair*)c->buf[B_LONG];
+    x.ckpt = (unsigned char*)c->buf[B_CKPT];
+
+    MCHK(hipEventRecord(c->ev0, c->stream));
+    hipLaunchKernelGGL(sw_matrix_locate_kernel, dim3((unsigned)blocks), dim3(256), 0, c->stream, a, x);
+    MCHK(hipGetLastError());
+    MCHK(hipEventRecord(c->ev1, c->stream));
+    o.res.resize(np);
+    MCHK(hipMemcpyAsync(o.res.data(), c->buf[B_RES], np * sizeof(TraceRes), hipMemcpyDeviceToHost, c->stream));
+    MCHK(hipStreamSynchronize(c->stream));
+    float ms = 0.f;
+    MCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    t_fill_ms += ms;
+    t_locate_ms += ms;
+    st.blocks = (int)blocks;
+    st.waves_per_cu = 4 * c->wgs[5];
+    st.boundary_bytes = std::max(st.boundary_bytes, (long long)ckpt_total);
+
+    // every walk starts at its end cell in state H; a pair without an alignment never walks
+    o.ws.assign(np, WalkState{});
+    for (size_t s = 0; s < np; ++s) {
+        const TraceRes& r = o.res[s];
+        if (r.score > 0 && (r.ei < 0 || r.ei >= act[s].alen || r.ej < 0 || r.ej >= act[s].blen))
+            return walk_failed(what, name_idx ? name_idx[act[s].idx] : act[s].idx, WALK_RANGE);
+        o.ws[s].i = r.ei;
+        o.ws[s].j = r.ej;
+        o.ws[s].done = r.score > 0 ? 0 : 1;
+    }
+    MCHK(hipMemcpyAsync(c->buf[B_STATE], o.ws.data(), np * sizeof(WalkState), hipMemcpyHostToDevice, c->stream));
+
+    // rounds: every pair still walking has its current strip filled and walked; each round moves a
+    // walk that has not ended exactly one strip to the left, so there are at most max_strips rounds
+    std::vector<int> live, ends;
+    std::vector<long long> need;
+    std::vector<StripItem> items;
+    for (long long round = 0;; ++round) {
+        live.clear();
+        need.clear();
+        for (size_t s = 0; s < np; ++s)
+            if (!o.ws[s].done) {
+                live.push_back((int)s);
+                need.push_back(align_strip_trace_bytes(act[s].blen));
+            }
+        if (live.empty()) break;
+        if (round >= max_strips) return walk_failed(what, name_idx ? name_idx[act[(size_t)live[0]].idx] : act[(size_t)live[0]].idx, 0);
+        align_pack(need.data(), (int)live.size(), trace_budget, ends);
+        t_rounds += 1;
+        int lo = 0;
+        for (const int hi : ends) {   // one launch pair: strip fill, walk
+            items.clear();
+            uint64_t trace_total = 0;
+            for (int k = lo; k < hi; ++k) {
+                const size_t s = (size_t)live[(size_t)k];
+                const DevSeq& p = act[s];
+                StripItem it{};
+                it.col_off = (uint64_t)p.a_off;
+                it.row_off = (uint64_t)p.b_off;
+                it.n = p.alen;
+                it.m = p.blen;
+                it.strip = o.ws[s].i / ALIGN_STRIP;
+                it.rows = o.ws[s].j + 1;
+                it.ckpt_in = it.strip > 0 ? ckpt_off[s] + (uint64_t)(it.strip - 1) * (uint64_t)align_ckpt_stride(p.blen) : 0;
+                it.trace_off = trace_total;
+                it.trace_bytes = (unsigned)need[(size_t)k];
+                it.ops_off = o.ops_off[s];
+                it.slot = (int)s;
+                trace_total += (uint64_t)need[(size_t)k];
+                items.push_back(it);
+            }
+            std::stable_sort(items.begin(), items.end(), [](const StripItem& p, const StripItem& q) { return p.rows > q.rows; });
+            const size_t ni = items.size();
+            if (long_blocks(c, 6, (const void*)sw_matrix_strip_kernel, ni, &blocks)) return -1;
+            if (ensure(c, B_ITEMS, ni * sizeof(StripItem)) || ensure(c, B_TRACE, (size_t)trace_total)) return -1;
+            MCHK(hipMemcpyAsync(c->buf[B_ITEMS], items.data(), ni * sizeof(StripItem), hipMemcpyHostToDevice, c->stream));
+            MCHK(hipMemsetAsync(c->buf[B_CTRL], 0, sizeof(Ctrl), c->stream));
+            a.pairs = nullptr;
+            a.npairs = (int)ni;
+            x.items = (const StripItem*)c->buf[B_ITEMS];
+            x.trace = (unsigned char*)c->buf[B_TRACE];
+            WalkStripArgs w{x.items, x.trace, (unsigned char*)c->buf[B_OPS], (WalkState*)c->buf[B_STATE], (int)ni};
+            MCHK(hipEventRecord(c->ev0, c->stream));
+            hipLaunchKernelGGL(sw_matrix_strip_kernel, dim3((unsigned)blocks), dim3(256), 0, c->stream, a, x);
+            MCHK(hipGetLastError());
+            MCHK(hipEventRecord(c->ev1, c->stream));
+            hipLaunchKernelGGL(sw_matrix_walk_strip_kernel, dim3((unsigned)((ni + 63) / 64)), dim3(64), 0, c->stream, w);
+            MCHK(hipGetLastError());
+            MCHK(hipEventRecord(c->ev2, c->stream));
+            MCHK(hipMemcpyAsync(o.ws.data(), c->buf[B_STATE], np * sizeof(WalkState), hipMemcpyDeviceToHost, c->stream));
+            MCHK(hipStreamSynchronize(c->stream));
+            float fill = 0.f, wk = 0.f;
+            MCHK(hipEventElapsedTime(&fill, c->ev0, c->ev1));
+            MCHK(hipEventElapsedTime(&wk, c->ev1, c->ev2));
+            t_fill_ms += fill;
+            t_walk_ms += wk;
+            st.variant += 1;
+            st.blocks = (int)blocks;
+            st.waves_per_cu = 4 * c->wgs[6];
+            st.boundary_bytes = std::max(st.boundary_bytes, (long long)(ckpt_total + trace_total));
+            for (const StripItem& it : items) {   // an error stops the call; a walk that goes on stands in the strip on the left
+                const WalkState& s = o.ws[(size_t)it.slot];
+                const int idx = name_idx ? name_idx[act[(size_t)it.slot].idx] : act[(size_t)it.slot].idx;
+                if (s.err != 0 || s.nops < 0 || s.nops > (long long)it.n + it.m) return walk_failed(what, idx, s.err ? s.err : WALK_OVERRUN);
+                if (!s.done && (it.strip == 0 || s.i != it.strip * ALIGN_STRIP - 1 || s.j < 0 || s.j >= it.rows || s.state < 0 ||
+                                s.state > 1))
+                    return walk_failed(what, idx, 0);
+            }
+            lo = hi;
+        }
+    }
+    o.ops.resize((size_t)ops_total);
+    if (ops_total) MCHK(hipMemcpy(o.ops.data(), c->buf[B_OPS], (size_t)ops_total, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 }  // namespace
+
+int matrix_align_long_device(const sw_matrix* mx, const unsigned char* d_arena, const int64_t* a_off, const int* alen,
+                             const int64_t* b_off, const int* blen, const int* name_idx, int npairs, int gap_init,
+                             int gap_ext, const char* what, AlignSink& sink) {
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!gaps_ok(gap_init, gap_ext)) return -1;
+    const long long trace_budget = sw_get_option("trace_mb") << 20;
+    long long ckpt_budget = 0;
+    if (align_ckpt_budget(&ckpt_budget)) return -1;
+    std::vector<long long> need((size_t)npairs, 0);
+    for (int k = 0; k < npairs; ++k) {   // refused before anything is launched
+        sw_align_plan p;
+        if (align_long_plan(alen[k], blen[k], trace_budget, ckpt_budget, what, name_idx ? name_idx[k] : k, &p)) return -1;
+        need[(size_t)k] = p.ckpt_bytes;
+    }
+    MatCtx* c = get_mctx();
+    if (!c) return -1;
+    t_fill_ms = t_walk_ms = t_locate_ms = 0.f;
+    t_rounds = 0;
+    sw_stats st{};
+    st.mode = MODE_MATRIX_LONG;
+    st.W = TRACE_W;
+    st.C = MAT_C;
+    st.items = npairs;
+    std::vector<int> ends;
+    align_pack(need.data(), npairs, ckpt_budget, ends);   // groups: the checkpoints held at once
+    std::vector<DevSeq> act;
+    LongOut o;
+    int lo = 0;
+    for (const int hi : ends) {
+        act.clear();
+        for (int k = lo; k < hi; ++k)
+            if (alen[k] > 0 && blen[k] > 0) {
+                act.push_back(DevSeq{a_off[k], b_off[k], alen[k], blen[k], k});
+                st.cells += (long long)alen[k] * blen[k];
+            }
+        if (!act.empty() && long_group(c, mx, d_arena, act, gap_init, gap_ext, trace_budget, what, name_idx, st, o)) return -1;
+        size_t s = 0;
+        for (int k = lo; k < hi; ++k) {
+            if (alen[k] == 0 || blen[k] == 0) {
+                sink.set_empty(k);
+                continue;
+            }
+            const TraceRes& r = o.res[s];
+            const WalkState& w = o.ws[s];
+            if (r.score <= 0) sink.set_empty(k);
+            else sink.set(k, r.score, w.i + 1, r.ei + 1, w.j + 1, r.ej + 1, o.ops.data() + o.ops_off[s], w.nops);
+            ++s;
+        }
+        lo = hi;
+    }
+    st.kernel_ms = t_fill_ms;
+    st.total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    report_stats(st);
+    return 0;
+}
 
 int matrix_align_device(const sw_matrix* mx, const unsigned char* d_arena, const int64_t* a_off, const int* alen,
                         const int64_t* b_off, const int* blen, const int* name_idx, int npairs, int gap_init,
@@ -817,10 +1321,10 @@ int matrix_align_device(const sw_matrix* mx, const unsigned char* d_arena, const
         if (alen[k] == 0 || blen[k] == 0) continue;
         const long long need = trace_bytes(alen[k], blen[k]);
         if (need > budget) {
-            char m[240];
+            char m[320];
             std::snprintf(m, sizeof m,
                           "%s %d: a %d x %d alignment needs %lld bytes of trace memory, more than option trace_mb = %lld MiB "
-                          "(linear-space alignment is not built)",
+                          "(sw_align_matrix_long / sw_db_align_matrix_long align such pairs a strip at a time)",
                           what, name_idx ? name_idx[k] : k, alen[k], blen[k], need, budget >> 20);
             report_error(m);
             return -1;
@@ -828,7 +1332,8 @@ int matrix_align_device(const sw_matrix* mx, const unsigned char* d_arena, const
     }
     MatCtx* c = get_mctx();
     if (!c) return -1;
-    t_fill_ms = t_walk_ms = 0.f;
+    t_fill_ms = t_walk_ms = t_locate_ms = 0.f;
+    t_rounds = 0;
     sw_stats st{};
     st.mode = MODE_MATRIX_TRACE;
     st.W = TRACE_W;
@@ -922,12 +1427,12 @@ int sw_score_matrix(const sw_matrix* mx, const unsigned char* seq1, const unsign
     return out;
 }
 
-int sw_align_matrix_batch(const sw_matrix* mx, const unsigned char* const* a, const int* alen,
-                          const unsigned char* const* b, const int* blen, int npairs, int gap_init, int gap_ext,
-                          sw_alignment* out, unsigned* cigar, long long cigar_cap, long long* cigar_used) {
-    if (align_check("sw_align_matrix_batch", mx, a, alen, b, blen, npairs, gap_init, gap_ext, out, cigar, cigar_cap,
-                    cigar_used))
-        return -1;
+// sw_align_matrix_batch and sw_align_matrix_long: the checks, the upload, then the traced launches of
+// whole pairs or (long_pairs) the checkpointed traceback
+static int align_host(const char* fn, bool long_pairs, const sw_matrix* mx, const unsigned char* const* a, const int* alen,
+                      const unsigned char* const* b, const int* blen, int npairs, int gap_init, int gap_ext,
+                      sw_alignment* out, unsigned* cigar, long long cigar_cap, long long* cigar_used) {
+    if (align_check(fn, mx, a, alen, b, blen, npairs, gap_init, gap_ext, out, cigar, cigar_cap, cigar_used)) return -1;
     AlignSink sink{out, {}};
     if (npairs == 0) return sink.finish(cigar, cigar_cap, cigar_used);
     MatCtx* c = get_mctx();
@@ -951,15 +1456,47 @@ int sw_align_matrix_batch(const sw_matrix* mx, const unsigned char* const* a, co
     if (ensure(c, B_ARENA, total)) return -1;
     // (synchronous: a refusal below returns before anything is launched or waited for)
     if (total) MCHK(hipMemcpy(c->buf[B_ARENA], arena.data(), total, hipMemcpyHostToDevice));
-    if (matrix_align_device(mx, (const unsigned char*)c->buf[B_ARENA], a_off.data(), alen, b_off.data(), blen, nullptr,
-                            npairs, gap_init, gap_ext, "pair", sink))
+    const auto align_device = long_pairs ? matrix_align_long_device : matrix_align_device;
+    if (align_device(mx, (const unsigned char*)c->buf[B_ARENA], a_off.data(), alen, b_off.data(), blen, nullptr, npairs,
+                     gap_init, gap_ext, "pair", sink))
         return -1;
     return sink.finish(cigar, cigar_cap, cigar_used);
+}
+
+int sw_align_matrix_batch(const sw_matrix* mx, const unsigned char* const* a, const int* alen,
+                          const unsigned char* const* b, const int* blen, int npairs, int gap_init, int gap_ext,
+                          sw_alignment* out, unsigned* cigar, long long cigar_cap, long long* cigar_used) {
+    return align_host("sw_align_matrix_batch", false, mx, a, alen, b, blen, npairs, gap_init, gap_ext, out, cigar, cigar_cap,
+                      cigar_used);
+}
+
+int sw_align_matrix_long(const sw_matrix* mx, const unsigned char* const* a, const int* alen,
+                         const unsigned char* const* b, const int* blen, int npairs, int gap_init, int gap_ext,
+                         sw_alignment* out, unsigned* cigar, long long cigar_cap, long long* cigar_used) {
+    return align_host("sw_align_matrix_long", true, mx, a, alen, b, blen, npairs, gap_init, gap_ext, out, cigar, cigar_cap,
+                      cigar_used);
+}
+
+int sw_align_long_plan(int n, int m, sw_align_plan* out) {
+    if (n < 0 || m < 0 || n > MAT_MAX_SEQ || m > MAT_MAX_SEQ || !out) {
+        report_error("sw_align_long_plan: invalid arguments");
+        return -1;
+    }
+    long long ckpt_budget = 0;
+    if (align_ckpt_budget(&ckpt_budget)) return -1;
+    return align_long_plan(n, m, sw_get_option("trace_mb") << 20, ckpt_budget, "pair", 0, out);
 }
 
 void sw_last_align_ms(float* fill_ms, float* walk_ms) {
     if (fill_ms) *fill_ms = t_fill_ms;
     if (walk_ms) *walk_ms = t_walk_ms;
+}
+
+void sw_last_align_long_ms(float* locate_ms, float* strip_ms, float* walk_ms, int* rounds) {
+    if (locate_ms) *locate_ms = t_locate_ms;
+    if (strip_ms) *strip_ms = t_fill_ms - t_locate_ms;
+    if (walk_ms) *walk_ms = t_walk_ms;
+    if (rounds) *rounds = t_rounds;
 }
 
 }  // extern "C"

@@ -75,4 +75,31 @@ struct AlignSink {
 int matrix_align_device(const sw_matrix* m, const unsigned char* d_arena, const int64_t* a_off, const int* alen,
                         const int64_t* b_off, const int* blen, const int* name_idx, int npairs, int gap_init,
                         int gap_ext, const char* what, AlignSink& sink);
+
+// ---- long pairs: checkpointed traceback, one strip at a time (include/algoGPU.h sw_align_matrix_long) ----
+// The arithmetic is host only (sw_align_host.cpp); the kernels and the rounds are in sw_matrix.hip.
+
+constexpr int ALIGN_STRIP = 512;   // seq1 positions a strip of the traced kernel covers (64 lanes x 8 columns)
+// steps of one strip over m rows (whole chunks of 64), the bytes of its trace (a dword a lane a step),
+// the bytes of one checkpoint column (8 B a row, whole chunks) and the strips of n seq1 positions
+long long align_strip_steps(long long m);
+long long align_strip_trace_bytes(long long m);
+long long align_ckpt_stride(long long m);
+long long align_strips(long long n);
+// One n x m pair under a trace budget and a checkpoint budget, both in bytes: fills *out (all zero
+// when either length is 0).  0, or -1 with a message that names `what idx`, the lengths, the bytes
+// and the limit when the pair's checkpoints or one strip's trace exceed their budget.
+int align_long_plan(int n, int m, long long trace_budget, long long ckpt_budget, const char* what, int idx,
+                    sw_align_plan* out);
+// the checkpoint budget in bytes: SWMI_ALIGN_CKPT_MB (whole MiB, at least 1; unset: 4096).  0 or -1.
+int align_ckpt_budget(long long* bytes);
+// Greedy packing in input order: items [end[g-1], end[g]) form part g, as many as keep the sum of
+// need[] within the budget, and never less than one item with a need (items that need nothing
+// never close a part).  Used for the groups (checkpoint bytes) and for a round's launches (strip traces).
+void align_pack(const long long* need, int n, long long budget, std::vector<int>& end);
+
+// as matrix_align_device, by checkpointed traceback: pairs of any length that the two budgets admit
+int matrix_align_long_device(const sw_matrix* m, const unsigned char* d_arena, const int64_t* a_off, const int* alen,
+                             const int64_t* b_off, const int* blen, const int* name_idx, int npairs, int gap_init,
+                             int gap_ext, const char* what, AlignSink& sink);
 }  // namespace swmi

@@ -21,7 +21,7 @@ import os
 
 import numpy as np
 
-from . import SwError, _align_call, _check, _ptr, _u8, lib
+from . import _LONG_CIGAR_CAP, SwError, _align_call, _check, _ptr, _u8, lib
 
 
 class Database:
@@ -142,17 +142,21 @@ class Database:
         _check(lib().sw_db_search_db(self._h, queries._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
         return out
 
-    def align(self, query, indices, matrix, gap_init: int, gap_ext: int) -> list:
+    def align(self, query, indices, matrix, gap_init: int, gap_ext: int, long: bool = False) -> list:
         """An :class:`Alignment` of ``query`` (seq1) with each record of ``indices``, out of the
-        database's device arena (sw_db_align_matrix): only the query is uploaded."""
+        database's device arena (sw_db_align_matrix): only the query is uploaded.  ``long=True``: the
+        same alignments by checkpointed traceback (sw_db_align_matrix_long), for records whose whole
+        trace does not fit option ``trace_mb``."""
         q = _u8(query)
         idx = [int(i) for i in indices]
         n = len(idx)
         if n == 0:
             return []
         IDX = (ctypes.c_int * n)(*idx)
-        return _align_call(lambda out, cig, cap, used: lib().sw_db_align_matrix(
-            self._h, matrix._handle(), _ptr(q), len(q), IDX, n, int(gap_init), int(gap_ext), out, cig, cap, used), n, 16 * n)
+        f = lib().sw_db_align_matrix_long if long else lib().sw_db_align_matrix
+        return _align_call(lambda out, cig, cap, used: f(
+            self._h, matrix._handle(), _ptr(q), len(q), IDX, n, int(gap_init), int(gap_ext), out, cig, cap, used), n,
+            max(16 * n, _LONG_CIGAR_CAP if long else 0))
 
     def top(self, query, k: int = 10, matrix=None, gap_init=None, gap_ext=None, alignments: bool = False) -> list:
         """The k best records: [(score, index, header)], score descending, index ascending on ties.

@@ -283,8 +283,8 @@ int  sw_db_search_db_matrix(sw_db*, const sw_db* queries, const sw_matrix*,
  *   bytes a pair plus 128 KiB per strip of 512 seq1 positions, and a launch holds at most
  *   option "trace_mb" MiB of it (default 1024): a batch that does not fit runs as several
  *   launches, packed greedily in input order; ONE PAIR THAT DOES NOT FIT ALONE IS REFUSED
- *   (-1, sw_last_error names the pair and the bytes).  Linear-space alignment of very long
- *   pairs is not built.  Arguments, gap penalties, the score range and the alphabet are
+ *   (-1, sw_last_error names the pair and the bytes); sw_align_matrix_long (below) aligns
+ *   such pairs.  Arguments, gap penalties, the score range and the alphabet are
  *   checked as sw_score_matrix_batch checks them.  cigar_cap: entries of cigar;
  *   *cigar_used receives the entries needed, and too small a cigar_cap returns -1 (out is
  *   filled, cigar is not).  Option "W" is not honoured (one traced instantiation, W = 8);
@@ -296,6 +296,36 @@ int  sw_db_search_db_matrix(sw_db*, const sw_db* queries, const sw_matrix*,
  * sw_db_align_matrix: the query (seq1) against records record_idx[0, nidx) of the
  *   database, out of its device arena: only the query is uploaded.  out[k] belongs to
  *   record_idx[k]; an index may repeat.
+ * sw_align_matrix_long, sw_db_align_matrix_long: the same arguments, outputs and cigar
+ *   protocol, and bit for bit the same alignments, for pairs whose whole trace does not
+ *   fit: CHECKPOINTED TRACEBACK, one strip at a time.  A locate pass (the traced kernel's
+ *   end-cell bookkeeping, no trace stores) finds the score and the end cell and keeps the
+ *   right-edge column of every strip of 512 seq1 positions but the last (a checkpoint:
+ *   H - gap_init and E - gap_ext, 8 bytes a seq2 position).  Then rounds: every pair still
+ *   walking has the one strip its walk stands in filled again from the checkpoint on its
+ *   left, traced, over seq2 positions [0, j] only (j: where the walk enters the strip) --
+ *   the same recurrence on the same integers, hence the same 4 bits a cell -- and the walk
+ *   runs on through that strip, appending its operations, until it ends or leaves the strip
+ *   on the left.  At most ceil(n / 512) rounds; nothing on the device waits for anything.
+ *   Memory, for an n x m pair with s = ceil(n / 512) strips:
+ *     checkpoints  (s - 1) * roundup(m, 64) * 8 bytes    (about n * m / 64)
+ *     one strip    ceil((m + 511) / 64) * 64 * 256 bytes (about 128 m + 128 KiB)
+ *   Strip traces of a round's launch share the trace_mb budget (a round that does not fit
+ *   runs as several launches, packed greedily in input order); the checkpoints of the pairs
+ *   in flight share the budget of the environment variable SWMI_ALIGN_CKPT_MB (whole MiB,
+ *   at least 1, default 4096, read on every call), and a batch that exceeds it runs as
+ *   several groups, greedy in input order.  One pair is refused before anything is launched
+ *   (-1, sw_last_error names the pair, both lengths, the bytes and the limit) when its
+ *   checkpoints alone exceed that budget or one of its strips alone exceeds trace_mb.
+ *   sw_last_stats: mode 8, W 8, C 64, items = npairs, variant = strip-fill launches,
+ *   boundary_bytes = the most device bytes of checkpoints plus strip traces held at once,
+ *   kernel_ms = locate plus strip fills; sw_last_align_ms: fill = locate plus strip fills,
+ *   walk = the walks.  One wave still runs one pair, so a long pair is slow: seconds for
+ *   32768 x 32768.
+ * sw_align_long_plan: no GPU call.  For one n x m pair under the current trace_mb and
+ *   SWMI_ALIGN_CKPT_MB: strips, checkpoint bytes, bytes of the largest strip trace, bytes
+ *   sw_align_matrix_batch would need.  0, or -1 (sw_last_error) when sw_align_matrix_long
+ *   would refuse the pair (out is filled either way when the lengths are valid).
  * Limits: one wave fills one pair and one lane walks it, so this is for the hits of a
  * search, not for every pair of it. */
 typedef struct { int score, beg1, end1, beg2, end2, ncigar; long long cigar_off; } sw_alignment;
@@ -310,9 +340,22 @@ int  sw_align_matrix_cpu(const sw_matrix*, const unsigned char* const* a, const 
 int  sw_db_align_matrix(sw_db*, const sw_matrix*, const unsigned char* query, int qlen,
                         const int* record_idx, int nidx, int gap_init, int gap_ext,
                         sw_alignment* out, unsigned* cigar, long long cigar_cap, long long* cigar_used);
-/* device time of this thread's last sw_align_matrix_batch / sw_db_align_matrix call, summed
- * over its launches (either pointer may be NULL) */
+int  sw_align_matrix_long(const sw_matrix*, const unsigned char* const* a, const int* alen,
+                          const unsigned char* const* b, const int* blen, int npairs,
+                          int gap_init, int gap_ext, sw_alignment* out,
+                          unsigned* cigar, long long cigar_cap, long long* cigar_used);
+int  sw_db_align_matrix_long(sw_db*, const sw_matrix*, const unsigned char* query, int qlen,
+                             const int* record_idx, int nidx, int gap_init, int gap_ext,
+                             sw_alignment* out, unsigned* cigar, long long cigar_cap, long long* cigar_used);
+typedef struct { int strips; long long ckpt_bytes, strip_trace_bytes, full_trace_bytes; } sw_align_plan;
+int  sw_align_long_plan(int n, int m, sw_align_plan* out);
+/* device time of this thread's last sw_align_matrix_batch / sw_db_align_matrix (or _long) call,
+ * summed over its launches (either pointer may be NULL) */
 void sw_last_align_ms(float* fill_ms, float* walk_ms);
+/* the same for this thread's last sw_align_matrix_long / sw_db_align_matrix_long call, the fill
+ * split into the locate launches and the strip fills, and the call's rounds, summed over its
+ * groups (any pointer may be NULL; zeros after a call of the other kind) */
+void sw_last_align_long_ms(float* locate_ms, float* strip_ms, float* walk_ms, int* rounds);
 
 /* Tuning knobs (process-wide).  Keys:
  *   "W"        columns per lane: 0 = auto, 1, 2, 4, 8
@@ -331,7 +374,8 @@ void sw_last_align_ms(float* fill_ms, float* walk_ms);
  *                  slabs and batches whose scores need int32)
  *              (sw_last_stats also reports mode 6 = wave per pair, substitution matrix: the
  *              sw_*_matrix entry points, which honour "blocks" and "W" only; and mode 7 = the
- *              traced launches of sw_align_matrix_batch / sw_db_align_matrix: "blocks", "trace_mb")
+ *              traced launches of sw_align_matrix_batch / sw_db_align_matrix: "blocks", "trace_mb";
+ *              and mode 8 = their _long counterparts, which honour the same two)
  *   "trace_mb" MiB of trace memory one traced launch may hold, 1..3072 (default 1024)
  *   "duo16"    1 = (default) packed duos take max3 through v_pk_maximum3_f16 when every
  *              value stays below 0x7C00 (MATCH*(min(n,m)+1) <= 31743), 0 = u16 max only

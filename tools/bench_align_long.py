@@ -1,0 +1,130 @@
+"""Long pairs by checkpointed traceback (sw_align_matrix_long): what one pair costs.
+
+One protein pair of N x N residues under a seeded random 24-symbol table, gaps (12, 1):
+
+  --kind crossing   seq2 is a mutated copy of seq1 (6 % substitutions, a few short insertions and deletions
+                    every 80 residues), so the alignment crosses every strip: the worst case, N / 512 rounds
+  --kind random     seq2 is random: a short alignment, one or two rounds
+
+One step (--n N --kind K) prints one JSON line: the locate, strip-fill and walk milliseconds, the rounds,
+boundary_bytes, the plan (sw_align_long_plan), the time of sw_score_matrix on the same pair and, with --check
+(N = 8192 in the default run), the time of sw_align_matrix_batch and whether the three aligners agree
+(align_matrix_long == align_matrix_batch == the CPU aligner).
+
+Without --n: the whole series, N = 8192, 16384, 32768, both kinds, every step a fresh child process under a
+time limit of its own; the first step that fails or runs out of time ends the series (nothing more is started
+on the GPU after it).  Lines are appended to --out (default profiles/align_long.jsonl).
+
+    python tools/bench_align_long.py [--out FILE] [--limit SECONDS]
+    python tools/bench_align_long.py --n 8192 --kind crossing [--check]
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+SYMBOLS = b"ARNDCQEGHILKMFPSTWYVBZX*"
+
+
+def make_pair(n, kind):
+    rng = np.random.default_rng(n + (1 if kind == "crossing" else 2))
+    sym = np.frombuffer(SYMBOLS, np.uint8)
+    a = sym[rng.integers(0, 23, n)]
+    if kind == "random":
+        return a, sym[rng.integers(0, 23, n)]
+    b = a.copy()
+    sub = rng.random(n) < 0.06
+    b[sub] = sym[rng.integers(0, 23, int(sub.sum()))]
+    for at in sorted((int(x) for x in rng.integers(1, n - 1, n // 80)), reverse=True):
+        k = int(rng.integers(1, 4))
+        b = np.delete(b, slice(at, at + k)) if rng.random() < 0.5 else np.insert(b, at, sym[rng.integers(0, 23, k)])
+    b = b[:n]
+    return a, np.concatenate([b, sym[rng.integers(0, 23, n - len(b))]])
+
+
+def table():
+    rng = np.random.default_rng(24)
+    t = rng.integers(-4, 4, (24, 24))
+    t = np.minimum(t, t.T)
+    t[np.arange(24), np.arange(24)] = rng.integers(4, 12, 24)
+    return t.astype(np.int8)
+
+
+def step(n, kind, check):
+    import concurrentproject_amd as sw
+    a, b = make_pair(n, kind)
+    rec = {"what": "align_long", "n": n, "m": len(b), "kind": kind, "gaps": [12, 1], "stamp": sw.source_stamp()[:12]}
+    with sw.Matrix(SYMBOLS, table()) as mx:
+        rec["plan"] = sw.align_long_plan(n, len(b))
+        sw.align_matrix_long([(a[:600], b[:600])], mx, 12, 1)          # loads the kernels, allocates the context
+        t0 = time.perf_counter()
+        x = sw.align_matrix_long([(a, b)], mx, 12, 1)[0]
+        rec["call_ms"] = round((time.perf_counter() - t0) * 1e3, 3)
+        st = sw.last_stats()
+        ms = sw.last_align_long_ms()
+        rec.update(locate_ms=round(ms["locate_ms"], 3), strip_ms=round(ms["strip_ms"], 3), walk_ms=round(ms["walk_ms"], 3),
+                   rounds=ms["rounds"], strip_launches=st["variant"], boundary_bytes=st["boundary_bytes"], mode=st["mode"],
+                   score=x.score, beg1=x.beg1, end1=x.end1, beg2=x.beg2, end2=x.end2, cigar_entries=len(x.ops),
+                   locate_gcups=round(n * len(b) / max(ms["locate_ms"], 1e-9) / 1e6, 3))
+        sw.score_matrix(a[:600], b[:600], mx, 12, 1)
+        t0 = time.perf_counter()
+        s = sw.score_matrix(a, b, mx, 12, 1)
+        rec["score_call_ms"] = round((time.perf_counter() - t0) * 1e3, 3)
+        st = sw.last_stats()
+        rec.update(score_kernel_ms=round(st["kernel_ms"], 3), score_W=st["W"], score_same=bool(s == x.score))
+        if check:
+            sw.align_matrix_batch([(a[:600], b[:600])], mx, 12, 1)
+            t0 = time.perf_counter()
+            y = sw.align_matrix_batch([(a, b)], mx, 12, 1)[0]
+            rec["batch_call_ms"] = round((time.perf_counter() - t0) * 1e3, 3)
+            fill, walk = sw.last_align_ms()
+            rec.update(batch_fill_ms=round(fill, 3), batch_walk_ms=round(walk, 3),
+                       batch_trace_bytes=sw.last_stats()["boundary_bytes"], equals_batch=bool(x == y))
+            t0 = time.perf_counter()
+            z = sw.align_matrix_batch([(a, b)], mx, 12, 1, cpu=True)[0]
+            rec["cpu_ms"] = round((time.perf_counter() - t0) * 1e3, 1)
+            rec["equals_cpu"] = bool(x == z)
+    print(json.dumps(rec), flush=True)
+    return 0 if rec["score_same"] and rec.get("equals_batch", True) and rec.get("equals_cpu", True) else 4
+
+
+def series(out, limit):
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    for n in (8192, 16384, 32768):
+        for kind in ("crossing", "random"):
+            cmd = [sys.executable, os.path.abspath(__file__), "--n", str(n), "--kind", kind] + (["--check"] if n == 8192 else [])
+            try:
+                r = subprocess.run(cmd, capture_output=True, text=True, timeout=limit)
+            except subprocess.TimeoutExpired:
+                print("bench_align_long: %d %s ran past %d s; stopping" % (n, kind, limit), file=sys.stderr)
+                return 124
+            sys.stderr.write(r.stderr[-2000:])
+            if r.returncode != 0:
+                print("bench_align_long: %d %s failed (%d); stopping" % (n, kind, r.returncode), file=sys.stderr)
+                return r.returncode
+            line = r.stdout.strip().split("\n")[-1]
+            print(line, flush=True)
+            with open(out, "a") as f:
+                f.write(line + "\n")
+    return 0
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=0)
+    ap.add_argument("--kind", default="crossing", choices=("crossing", "random"))
+    ap.add_argument("--check", action="store_true")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "align_long.jsonl"))
+    ap.add_argument("--limit", type=int, default=150, help="seconds a step of the series may take")
+    a = ap.parse_args()
+    return step(a.n, a.kind, a.check) if a.n else series(a.out, a.limit)
+
+
+if __name__ == "__main__":
+    sys.exit(main())
