@@ -165,6 +165,11 @@ struct Opts {
     // d0 == d2 (the launch fails)
     int f3drops_set = 0;
     int f3drops[4] = {64, 64, 64, 64};
+    // environment SWMI_F3JOIN, read with the snapshot (A/B runs and tests; not an option): 0 = a wedge launch
+    // stages its descriptors with copies, resets the claim counter and the score with memsets and joins its
+    // chains in a combine kernel of its own; anything else or unset = the staged kernel does all of it
+    // (sw_internal.h KParams::wedge_join)
+    int f3join = 1;
     long long operator[](Opt o) const { return v[o]; }
 };
 Opts snapshot_opts() {
@@ -172,6 +177,8 @@ Opts snapshot_opts() {
     for (int i = 0; i < OPT_COUNT; ++i) o.v[i] = g_opt[i].load();
     const char* w = std::getenv("SWMI_F3WEDGE");
     o.f3wedge = w && w[0] == '0' && !w[1] ? 0 : w && w[0] == '1' && !w[1] ? 1 : -1;
+    const char* j = std::getenv("SWMI_F3JOIN");
+    o.f3join = j && j[0] == '0' && !j[1] ? 0 : 1;
     if (const char* d = std::getenv("SWMI_F3WEDGE_DROPS")) {
         char tail = 0;
         const int got = std::sscanf(d, "%d,%d,%d,%d%c", &o.f3drops[0], &o.f3drops[1], &o.f3drops[2], &o.f3drops[3], &tail);
@@ -271,6 +278,13 @@ struct Ctx {
     PinBuf<int> hscores;
     PinBuf<Ctrl> hctrl;
     unsigned epoch = 0;
+    // a wedge launch that joins its chains in the staged kernel (KParams::wedge_join): the join words, zero
+    // between launches (zeroed when allocated and after an error), and the value the launches so far have left
+    // in the claim counter Ctrl::next_item.  Every other kind of launch memsets the counter and leaves its own
+    // claims in it (item0_known false): the next joining launch resets it once more and counts from 0
+    DevBuf<unsigned> join;
+    unsigned item0 = 0;
+    bool item0_known = false;
     std::map<int, int> waves_cache;   // variant key -> waves per CU
 };
 
@@ -1244,8 +1258,25 @@ int size_grid(Ctx* c, Job& job, Variant& v, const Opts& opt, size_t np, Grid& g)
 }
 
 // The job's descriptors into the pinned staging buffers, and device buffers for them
-int stage_descriptors(Ctx* c, const Job& job, size_t np, hipStream_t s) {
+int stage_descriptors(Ctx* c, const Job& job, size_t np, bool join, hipStream_t s) {
     const bool duo = job.mode == MODE_DUO;
+    const Ctrl* ctrl_before = c->ctrl.p;
+    if (join) {   // the descriptors travel in the kernel's arguments: the control block and the join words only
+        const size_t join_before = c->join.cap;   // (a grown buffer may come back at the old address)
+        const size_t words = (size_t)JOIN_UNITS + (size_t)job.wplan.strips;
+        if (c->ctrl.ensure(1, s) || c->join.ensure(words, s)) return -1;
+        if (c->ctrl.p != ctrl_before) {
+            HIPCHK(hipMemsetAsync(c->ctrl.p, 0, sizeof(Ctrl), s));
+            c->item0 = 0;
+            c->item0_known = true;
+        } else if (!c->item0_known) {   // the launch before was of another kind
+            HIPCHK(hipMemsetAsync(c->ctrl.p, 0, sizeof(unsigned), s));
+            c->item0 = 0;
+            c->item0_known = true;
+        }
+        if (c->join.cap != join_before) HIPCHK(hipMemsetAsync(c->join.p, 0, c->join.cap * sizeof(unsigned), s));
+        return 0;
+    }
     // staging buffers may still be read by the previous call's async copies
     if (c->staged_pending) {
         HIPCHK(hipEventSynchronize(c->staged));
@@ -1255,7 +1286,6 @@ int stage_descriptors(Ctx* c, const Job& job, size_t np, hipStream_t s) {
     if (duo) std::memcpy(c->hduo.p, job.duos.data(), np * sizeof(DuoDesc));
     else std::memcpy(c->hdesc.p, job.pairs.data(), np * sizeof(PairDesc));
     std::memcpy(c->hibase.p, job.item_base.data(), (np + 1) * sizeof(int));
-    const Ctrl* ctrl_before = c->ctrl.p;
     if (c->desc.ensure(np, s) || c->duo.ensure(np, s) || c->ibase.ensure(np + 1, s) || c->ctrl.ensure(1, s)) return -1;
     // a fresh control block holds whatever the allocator recycled: clear the sticky
     // error fields once (afterwards only check_ctrl resets them, after reporting)
@@ -1267,7 +1297,7 @@ int stage_descriptors(Ctx* c, const Job& job, size_t np, hipStream_t s) {
 // descriptor copies, the control block and the scores zeroed, and a seven-letter ring launch's rows as
 // selectors (m bytes, before the timed kernel)
 int prepare_device(Ctx* c, const Job& job, const Variant& v, const Opts& opt, const unsigned char* d_seq, int* d_scores,
-                   int nscores, size_t np, hipStream_t s) {
+                   int nscores, size_t np, bool join, hipStream_t s) {
     // ring mode: a consumer progress word per block; duo roles: one word per CU (XCC, SE, SH, CU of HW_ID)
     const size_t cons = v.ring ? (size_t)v.cfg.blocks * RING_CONS_STRIDE
                         : v.cfg.duo_wrap > 0 && opt[O_duo_roles] != 0 ? (size_t)DUO_CU_WORDS : 0;
@@ -1285,12 +1315,19 @@ int prepare_device(Ctx* c, const Job& job, const Variant& v, const Opts& opt, co
         }
         if (c->bnd.ensure(job.bnd_granules, s)) return -1;
     }
+    if (join) {
+        // nothing to copy or clear: the claim counter runs on (Ctx::item0) and the kernel's last strip writes the
+        // pair's score slot; only the slots of a call's empty pairs are zeroed
+        if (nscores > 1) HIPCHK(hipMemsetAsync(d_scores, 0, (size_t)nscores * sizeof(int), s));
+        return 0;
+    }
     if (job.mode == MODE_DUO) HIPCHK(hipMemcpyAsync(c->duo.p, c->hduo.p, np * sizeof(DuoDesc), hipMemcpyHostToDevice, s));
     else HIPCHK(hipMemcpyAsync(c->desc.p, c->hdesc.p, np * sizeof(PairDesc), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(c->ibase.p, c->hibase.p, (np + 1) * sizeof(int), hipMemcpyHostToDevice, s));
     HIPCHK(hipEventRecord(c->staged, s));
     c->staged_pending = true;
     HIPCHK(hipMemsetAsync(c->ctrl.p, 0, sizeof(unsigned), s));   // next_item only; error stays sticky
+    c->item0_known = false;   // (this launch's kernel leaves its claims in the counter)
     HIPCHK(hipMemsetAsync(d_scores, 0, (size_t)nscores * sizeof(int), s));
     if (v.cfg.hep && v.ring) {
         const PairDesc& d = job.pairs[0];
@@ -1351,7 +1388,8 @@ void fill_score_words(KParams& kp, const Params& prm, const unsigned char* hsym)
 }
 
 KParams fill_kparams(Ctx* c, const Job& job, const Variant& v, const Grid& g, const Params& prm, const Opts& opt,
-                     const unsigned char* d_seq, int* d_scores, size_t np, const SlabEdge* edge) {
+                     const unsigned char* d_seq, int* d_scores, size_t np, const SlabEdge* edge, bool join, hipStream_t s,
+                     int* err) {
     KParams kp{};
     kp.seq = d_seq;
     kp.pairs = c->desc.p;
@@ -1366,9 +1404,14 @@ KParams fill_kparams(Ctx* c, const Job& job, const Variant& v, const Grid& g, co
     // k = epoch ^ 0x5BD1E995 zero in its low 5 bits: a zeroed 8-B granule passes its check when
     // its second word equals k (staged) or k ^ (position << 5) (ring edges), which needs exactly that;
     // the affine granules' E half is keyed k ^ 0x9E3779B9, held to the same rule
+    const unsigned epoch_before = c->epoch;
     do ++c->epoch;
     while (c->epoch == 0 || ((c->epoch ^ 0x5BD1E995u) & 31u) == 0 || ((c->epoch ^ 0x5BD1E995u ^ 0x9E3779B9u) & 31u) == 0);
     kp.epoch = c->epoch;
+    // (the score word of the joining wedge launches orders its values by epoch: cleared when the epochs wrap)
+    if (c->epoch < epoch_before && c->join.p &&
+        hipMemsetAsync(c->join.p + JOIN_SCORE, 0, 2 * sizeof(unsigned), s) != hipSuccess)
+        *err = -1;
     fill_score_words(kp, prm, v.cfg.hep ? job.hsym : nullptr);
     if (v.cfg.duo_wrap > 0) {
         kp.wrap_rows = v.cfg.duo_wrap;
@@ -1403,6 +1446,12 @@ KParams fill_kparams(Ctx* c, const Job& job, const Variant& v, const Grid& g, co
         kp.wedge_segr = job.wedge_segr;
         kp.wedge_seg[0] = job.wedge_seg[0];
         kp.wedge_seg[1] = job.wedge_seg[1];
+        if (join) {
+            kp.wedge_join = c->join.p;
+            kp.item0 = c->item0;
+            kp.wedge_pair[0] = job.pairs[0];
+            kp.wedge_pair[1] = job.pairs[1];
+        }
     }
     if (v.cfg.hep && v.ring) kp.hrows = c->hrows.p;
     if (edge) {   // (flow2 then runs its slab kernel, which streams the row codes)
@@ -1434,10 +1483,17 @@ int enqueue(Ctx* c, Job& job, const Params& prm, const Opts& opt, const unsigned
     }
     const size_t np = job.mode == MODE_DUO ? job.duos.size() : job.pairs.size();
     Grid g;
-    if (stage_descriptors(c, job, np, s) || size_grid(c, job, v, opt, np, g) ||
-        prepare_device(c, job, v, opt, d_seq, d_scores, nscores, np, s))
+    // a wedge launch joins its chains inside the staged kernel (sw_flow3.hip f3_join_strip) unless SWMI_F3JOIN=0
+    const bool join = v.wedge && opt.f3join != 0;
+    if (stage_descriptors(c, job, np, join, s) || size_grid(c, job, v, opt, np, g) ||
+        prepare_device(c, job, v, opt, d_seq, d_scores, nscores, np, join, s))
         return -1;
-    const KParams kp = fill_kparams(c, job, v, g, prm, opt, d_seq, d_scores, np, edge);
+    int kerr = 0;
+    const KParams kp = fill_kparams(c, job, v, g, prm, opt, d_seq, d_scores, np, edge, join, s, &kerr);
+    if (kerr) {
+        set_err("clearing the join words failed");
+        return -1;
+    }
 
     if (time_kernel) HIPCHK(hipEventRecord(c->ev0, s));
     HIPCHK(v.cfg.f3 || v.cfg.f3a || v.cfg.f3ra ? launch_sw_flow3(v.cfg, kp, s)
@@ -1449,7 +1505,9 @@ int enqueue(Ctx* c, Job& job, const Params& prm, const Opts& opt, const unsigned
         const Granule* gr = c->bnd.p + r.bnd_off + (uint64_t)((r.strips + 3) / 4 - 1) * (uint64_t)r.m;
         HIPCHK(launch_sw_flow3_combine(gl, gr, l.m, prm.gap_init, kp.epoch, c->ctrl.p, d_scores + l.out_idx, s));
     }
-    if (v.steep) {   // the crossing term from the chains' staircases and hand-off columns (inside the timed span)
+    if (join) {   // (its workgroups claim every item once and one claim more each)
+        c->item0 += (unsigned)kp.total_items + (unsigned)v.cfg.blocks;
+    } else if (v.steep) {   // the crossing term from the chains' staircases and hand-off columns (inside the timed span)
         const SteepJoin j = {c->bnd.p + job.wedge_bnd[0], c->bnd.p + job.wedge_bnd[1], c->bnd.p + job.pairs[0].bnd_off,
                              c->bnd.p + job.pairs[1].bnd_off, c->bnd.p + job.wedge_seg[0], c->bnd.p + job.wedge_seg[1],
                              job.wedge_rows, job.wedge_segr, job.pairs[0].m, prm.gap_init};
@@ -1485,6 +1543,10 @@ int check_ctrl(Ctx* c, hipStream_t s) {
             set_err("strip hand-off timed out (error %u, strip %u): a producer strip never published",
                     c->hctrl.p->error, c->hctrl.p->err_item);
         HIPCHK(hipMemsetAsync(c->ctrl.p, 0, sizeof(Ctrl), s));
+        c->item0 = 0;
+        c->item0_known = true;
+        // (a launch that gave up may have left join counters and claims half way)
+        if (c->join.p) HIPCHK(hipMemsetAsync(c->join.p, 0, c->join.cap * sizeof(unsigned), s));
         HIPCHK(hipStreamSynchronize(s));
         return -1;
     }

@@ -44,7 +44,8 @@ struct DuoDesc {
     int out_idx[2];     // out_idx[1] == -1: no second pair
 };
 
-// Per-launch control block (zeroed by hipMemsetAsync before every launch).
+// Per-launch control block: next_item is zeroed by hipMemsetAsync before every launch, except a two-wedge launch
+// that joins its chains itself, which counts on from KParams::item0.
 struct Ctrl {
     unsigned int next_item;   // work-claim counter (items claimed strictly in order)
     unsigned int error;       // nonzero: a bounded spin gave up (see ERR_*)
@@ -142,7 +143,33 @@ struct KParams {
     int wedge_drop[4];
     int wedge_segr;
     unsigned long long wedge_seg[2];
+    // A wedge launch that joins its chains itself (sw_flow3.hip the join; environment SWMI_F3JOIN, default on): the
+    // launch is this one kernel, with no copy, memset or combine kernel beside it.  wedge_join points at the
+    // context's join words (JOIN_*; zero between launches): a counter per join unit, the 64-bit score word and
+    // the counter of finished strips.  The two descriptors travel here (wedge_pair: item & 1 selects), and the
+    // claim counter is not reset: a launch's workgroups make total_items + blocks claims, the host keeps the
+    // sum, and item = claim - item0.
+    unsigned* wedge_join;         // null: the copies, the memsets and the combine kernel of a launch without the join
+    unsigned item0;
+    PairDesc wedge_pair[2];
 };
+// the join words of a context: the score word (64 bits: epoch << 32 | score, atomicMax), the finished strips, and
+// from JOIN_UNITS on a counter per join unit (forward strip)
+enum : int { JOIN_SCORE = 0, JOIN_DONE = 2, JOIN_UNITS = 4 };
+// Join unit s is what the combine kernels compute for forward strip s: its lanes' diagonal nodes against the mirrored
+// lanes they meet and, in a steep plan, its hand-off column against the mirrored chain's.  It reads forward strip s
+// and the mirrored strips S - s - 2 .. S - s - lo inside [0, S), lo = 1 in a steep plan (whose mirrored chain sits
+// two dead columns further left) and 0 in the uniform one (tools/wedge_bounds_check.cpp checks both against the
+// combine kernels' index sets).  A strip adds one to every unit that reads it; the add that brings a unit to
+// join_unit_full runs it.
+__host__ __device__ inline int join_unit_lo(int S, int s, bool steep) { return S - s - 2 < 0 ? 0 : S - s - 2; }
+__host__ __device__ inline int join_unit_hi(int S, int s, bool steep) {
+    const int hi = S - s - (steep ? 1 : 0);
+    return hi > S - 1 ? S - 1 : hi;
+}
+__host__ __device__ inline int join_unit_full(int S, int s, bool steep) {
+    return 1 + join_unit_hi(S, s, steep) - join_unit_lo(S, s, steep) + 1;
+}
 
 constexpr int RING_CONS_STRIDE = 32;   // dwords between consumer progress words (one 128-B line each)
 

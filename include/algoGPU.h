@@ -417,7 +417,11 @@ void sw_last_align_long_ms(float* locate_ms, float* strip_ms, float* walk_ms, in
  *              overrides the measured thresholds for A/B runs and tests, and SWMI_F3WEDGE_DROPS =
  *              d0,d1,d2,d3 sets the staircase's drop behind strip j to d[j % 4] rows wherever the steep
  *              plan admits it (variant bit 19; multiples of 64 from 64 to 256 with d0 == d2, anything
- *              else fails the launch; 64,64,64,64 is the uniform staircase; unset: the measured default)
+ *              else fails the launch; 64,64,64,64 is the uniform staircase; unset: the measured default).
+ *              A two-wedge launch is one kernel: the staged kernel joins the chains itself, carries the two
+ *              descriptors in its arguments and neither copies nor clears anything first.  The environment
+ *              variable SWMI_F3JOIN = 0 (A/B runs and tests) keeps the earlier launch instead: descriptor
+ *              copies, memsets of the claim counter and the score, and a combine kernel behind the staged one
  *   "f3pwg"    1 = (default) DNA batches on a pair-per-workgroup plan (scores that need int32, or 1-2
  *              pairs per CU) run flow3's three-column ring step (sw_flow3r3p / ra3p_kernel), 0 = flow2's
  *   "f3slab"   1 = (default) column slabs run flow3's ring kernel with slab roles

@@ -78,7 +78,74 @@ static void check_steep(int n, int m, const int d[4]) {
     }
 }
 
+// The join units of a launch that joins its chains in the staged kernel (sw_internal.h join_unit_*; sw_flow3.hip
+// f3_join_strip) against the index sets of the combine kernels, whose arithmetic is repeated here: the units visit
+// every thread index of the combine kernel exactly once, every entry a unit loads belongs to forward strip s or to
+// a mirrored strip of the range it waits for, that range is tight, the strips that count into a unit are exactly
+// those it reads, and a unit's full count is their number.
+static void check_units(int n, int m, const WedgePlan& w, const int d[4]) {
+    const int S = w.strips;
+    const bool steep = w.steep;
+    const int maxcol = std::max(std::max(d[0], d[1]), std::max(d[2], d[3])) - 60;
+    const int W = 126 * S + 2, pshift = steep ? 4 : 2;
+    const long long threads = 64LL * S + (steep ? (long long)(S - 1) * maxcol : 0);
+    std::vector<int> visits((size_t)threads, 0);
+    std::vector<int> readers((size_t)S, 0);   // per unit: mirrored strips that count into it
+    for (int t = 0; t < S; ++t) {             // f3_join_strip's range of a mirrored strip
+        const int u0 = std::max(S - t - 2, 0), u1 = std::min(S - t - (steep ? 1 : 0), S - 1);
+        CHECK(u0 <= u1);
+        for (int u = u0; u <= u1; ++u) {
+            CHECK(swmi::join_unit_lo(S, u, steep) <= t && t <= swmi::join_unit_hi(S, u, steep));
+            ++readers[(size_t)u];
+        }
+    }
+    for (int s = 0; s < S; ++s) {
+        const int lo = swmi::join_unit_lo(S, s, steep), hi = swmi::join_unit_hi(S, s, steep);
+        CHECK(0 <= lo && lo <= hi && hi < S);
+        CHECK(swmi::join_unit_full(S, s, steep) == 1 + readers[(size_t)s] && readers[(size_t)s] == hi - lo + 1);
+        std::vector<char> used((size_t)S, 0);
+        for (int l = 0; l < 64; ++l) {   // the diagonal threads [64 s, 64 s + 64)
+            ++visits.at((size_t)(64 * s + l));
+            const int c = 126 * s + 2 * l;
+            for (int col = 0; col < 2; ++col) {
+                const int p = W - pshift - c - 2 * col;
+                if (p < 0) continue;
+                const int sp = p / 126, lp = (p % 126) >> 1;
+                for (int dup = 0; dup < 2; ++dup) {
+                    const int s2 = sp - dup;
+                    if (s2 < 0 || s2 >= S || (dup && lp != 0)) continue;
+                    CHECK(lo <= s2 && s2 <= hi);
+                    used[(size_t)s2] = 1;
+                }
+            }
+        }
+        if (steep && s < S - 1) {        // the hand-off column: k = lane, lane + 64, ... below maxcol
+            for (int lane = 0; lane < 64; ++lane)
+                for (int k = lane; k < maxcol; k += 64) ++visits.at((size_t)(64LL * S + (long long)s * maxcol + k));
+            const int s2 = S - 2 - s;    // its lanes, its segment entries, its group edge: all that strip's stores
+            CHECK(lo <= s2 && s2 <= hi);
+            used[(size_t)s2] = 1;
+        }
+        // tight but for dead columns: the mirrored strips in front of the frame's last live column are all read
+        for (int t = lo; t <= hi; ++t) CHECK(used[(size_t)t] || W - pshift - (126 * s + 126) - 2 < 0);
+    }
+    for (long long i = 0; i < threads; ++i) CHECK(visits[(size_t)i] == 1);
+}
+
 int main() {
+    {   // the join units of every planned shape of the sweeps below, thinned by the strip count
+        const int uni[4] = {64, 64, 64, 64};
+        const int upats[][4] = {{64, 64, 64, 128}, {64, 128, 64, 128}, {128, 64, 128, 128}, {256, 64, 256, 64}};
+        for (int n = 253; n <= 70000; n += (n < 3000 ? 1 : 977)) {
+            const int m = n + 4000;
+            WedgePlan w{};
+            if (swmi::wedge_bounds(n, m, &w)) check_units(n, m, w, uni);
+            for (const auto& d : upats) {
+                WedgePlan v{};
+                if (swmi::steep_bounds(n, 4 * n + 4000, d, &v)) check_units(n, 4 * n + 4000, v, d);
+            }
+        }
+    }
     for (int n = 1; n <= 3000; ++n)
         for (int m = 1; m <= 2200; m += (n % 7 == 0 ? 1 : 61)) check(n, m);
     const int pats[][4] = {{64, 64, 64, 128}, {64, 128, 64, 128}, {128, 128, 128, 128}, {64, 64, 64, 192}, {256, 64, 256, 64}};
