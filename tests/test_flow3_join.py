@@ -8,7 +8,8 @@ the steep admission edge, 17 above it and n + 300; the uniform pattern, (64,128,
 random pairs and stretched copies laid corner to corner (one of whose best paths the CPU model finds on a segment
 node); grids of 1, 2, 3 workgroups and the default; three pairs launched twice each, then launches alternating
 patterns and SWMI_F3JOIN = 0 / 1, then an affine launch (which resets the claim counter) between two of them; a
-seven-letter pair; and sw_last_stats unchanged from SWMI_F3JOIN = 0."""
+seven-letter pair; and sw_last_stats unchanged from SWMI_F3JOIN = 0.
+The corners of the scoring-constant domain over these launches: tests/test_wedge_corners.py."""
 import os
 import zlib
 

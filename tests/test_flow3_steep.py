@@ -9,7 +9,8 @@ admission edge D + 65, 17 and 63 rows above it, n + 300 and 2 n + 401; random pa
 corner to corner; three linear-gap constant sets; a seven-letter pair; the patterns (64,64,64,64) (the uniform
 plan), (64,64,64,128) and (64,128,64,128) and the variable unset; shapes where the steep plan refuses; grids of
 1, 2 and 3 workgroups; launches back to back; a steep shape alternated with a uniform one on the same buffers;
-and the automatic pattern from 4096 columns."""
+and the automatic pattern from 4096 columns.
+The corners of the scoring-constant domain over these launches: tests/test_wedge_corners.py."""
 import os
 import zlib
 

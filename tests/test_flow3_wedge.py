@@ -9,7 +9,8 @@ Covered: 2, 3, 5 and 6 strips a chain (an in-workgroup and a cross-workgroup hop
 mirrored chain dead rows in front), about n and about 2 n; random pairs and mutated copies laid corner to
 corner, whose best path crosses the staircase (counted with the CPU model of tests/test_wedge_identity.py);
 three linear-gap constant sets; a seven-letter pair; grids of 1, 2 and 3 workgroups; launches back to back
-on the same buffers; and the automatic plan's choice (variant bit 18 of sw_last_stats)."""
+on the same buffers; and the automatic plan's choice (variant bit 18 of sw_last_stats).
+The corners of the scoring-constant domain over these launches: tests/test_wedge_corners.py."""
 import os
 import zlib
 

@@ -3,7 +3,10 @@ section 2), over every kernel family.
 
 The documented domain is 0 <= G_INIT, G_EXT <= 2^20, -127 <= MISMATCH <= 0, MISMATCH <= MATCH <= 127, and
 every family takes a sub-domain of it through a host predicate of its own (flow2_fits, pwg3_fits, duo_fits,
-duo_f16_fits, duo_raw_ok in csrc/sw_engine.hip).  CORNERS sits on the edges of those predicates.  Each test
+duo_f16_fits, duo_raw_ok in csrc/sw_engine.hip).  CORNERS sits on the edges of those predicates, the last five
+sets on the same edges with G_INIT == G_EXT (the linear-gap step's kernels: M + G_INIT = 127 in and 128 out at
+G = 100, MISMATCH = 0 with free and with paid gaps; tests/test_wedge_corners.py runs them, and the rest of the
+table, over the wedge launches of one long pair).  Each test
 forces one family with the options the family's own test file uses, proves from last_stats() that the
 family ran, and compares every score bit for bit with oracle.score_linear (lazySmith.cpp:15-69 restated;
 pinned to the reference's own code at every corner set by tests/test_corners_cpu.py).
@@ -50,6 +53,13 @@ CORNERS = [
     (-127, -127, 0, 0),        # MATCH = MISMATCH = -127: every score is 0; duo out
     (1, -1, 1, 1),             # control: the reference's constants
     (2, -3, 5, 2),             # control: affine
+    # the same edges on the linear-gap step (G_INIT == G_EXT: the two-column kernels, and the wedge launches of
+    # tests/test_wedge_corners.py)
+    (27, -127, 100, 100),      # M+GI = 127 on the linear step: the last set inside
+    (28, -127, 100, 100),      # M+GI = 128 on the linear step: the first one outside
+    (100, -1, 27, 27),         # M+GI = 127 from the MATCH side; M-MI = 101: raw duo in
+    (127, 0, 0, 0),            # MATCH max, MISMATCH = 0, free gaps: 127 * LCS; raw duo out
+    (5, 0, 3, 3),              # MISMATCH = 0 with paid linear gaps: raw duo out
 ]
 
 ACGT = np.frombuffer(b"ACGT", np.uint8)
@@ -88,11 +98,12 @@ def linear(t):
     return t[2] == t[3]
 
 
-# How many of the 24 sets each rule admits, counted by hand from the table:
-N_FLOW = 19       # out: M+GI = 128, and the four sets with G_INIT of 65408 or more
-N_FLOW_LIN = 6    # of those, G_INIT == G_EXT: (127,-127,0,0), (1,0,0,0), (0,0,0,0), (-1,-2,1,1), (-127,-127,0,0), (1,-1,1,1)
-N_DUO = 17        # out: GI+M = 65536, GE = 65536, the three 2^20 sets, MATCH < 0 twice
-N_DUO_RAW = 6     # (64,-63,5,2), (1,-1,1,3), (3,-2,2,9), (0,-5,3,1) and the two controls
+# How many of the 29 sets each rule admits, counted by hand from the table:
+N_FLOW = 23       # out: M+GI = 128 twice (affine and linear), and the four sets with G_INIT of 65408 or more
+N_FLOW_LIN = 10   # of those, G_INIT == G_EXT: (127,-127,0,0), (1,0,0,0), (0,0,0,0), (-1,-2,1,1), (-127,-127,0,0), (1,-1,1,1),
+                  # (27,-127,100,100), (100,-1,27,27), (127,0,0,0), (5,0,3,3)
+N_DUO = 22        # out: GI+M = 65536, GE = 65536, the three 2^20 sets, MATCH < 0 twice
+N_DUO_RAW = 7     # (64,-63,5,2), (1,-1,1,3), (3,-2,2,9), (0,-5,3,1), the two controls and (100,-1,27,27)
 
 
 # ---- inputs ---------------------------------------------------------------------------------------------
