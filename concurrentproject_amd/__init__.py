@@ -225,6 +225,20 @@ def lib() -> ctypes.CDLL:
         fp = ctypes.POINTER(ctypes.c_float)
         L.sw_last_align_long_ms.argtypes = [fp, fp, fp, ctypes.POINTER(i)]
         L.sw_last_align_long_ms.restype = None
+    if hasattr(L, "sw_align_matrix_batch_mode"):   # global and semi-global alignment (SW_MODE_*)
+        L.sw_score_matrix_batch_mode.argtypes = [vp, ctypes.POINTER(u8p), ctypes.POINTER(i), ctypes.POINTER(u8p),
+                                                 ctypes.POINTER(i), i, i, i, i, ctypes.POINTER(i)]
+        L.sw_score_matrix_batch_mode.restype = i
+        for name in ("sw_align_matrix_batch_mode", "sw_align_matrix_cpu_mode"):
+            f = getattr(L, name)
+            f.argtypes = [vp, ctypes.POINTER(u8p), ctypes.POINTER(i), ctypes.POINTER(u8p), ctypes.POINTER(i), i, i, i, i,
+                          ctypes.POINTER(_Alignment), ctypes.POINTER(ctypes.c_uint), ll, ctypes.POINTER(ll)]
+            f.restype = i
+        L.sw_db_search_matrix_mode.argtypes = [vp, vp, u8p, i, i, i, i, ctypes.POINTER(i)]
+        L.sw_db_search_matrix_mode.restype = i
+        L.sw_db_align_matrix_mode.argtypes = [vp, vp, u8p, i, ctypes.POINTER(i), i, i, i, i, ctypes.POINTER(_Alignment),
+                                              ctypes.POINTER(ctypes.c_uint), ll, ctypes.POINTER(ll)]
+        L.sw_db_align_matrix_mode.restype = i
     _lib = L
     return L
 
@@ -494,7 +508,8 @@ class Matrix:
     def equality(cls, symbols, match: int, mismatch: int) -> "Matrix":
         """The table of a byte-equality scoring over the distinct bytes ``symbols`` (at most 32):
         ``match`` on the diagonal, ``mismatch`` elsewhere.  With it, alignments under the
-        reference's own scoring (``Params``) need no matrix file."""
+        reference's own scoring (``Params``) need no matrix file.  It is also the way to global and
+        semi-global alignment (``mode=``) under equality scoring: those modes take a matrix."""
         sym = bytes(sorted(set(_u8(symbols).tolist())))
         if not 1 <= len(sym) <= 32:
             raise SwError("equality matrix: %d distinct bytes (need 1 to 32)" % len(sym))
@@ -537,15 +552,40 @@ class Matrix:
             pass
 
 
-def score_matrix(seq1, seq2, matrix: Matrix, gap_init: int, gap_ext: int) -> int:
+SW_MODE_LOCAL, SW_MODE_GLOBAL, SW_MODE_SEMIGLOBAL = 0, 1, 2
+_MODES = {"local": SW_MODE_LOCAL, "global": SW_MODE_GLOBAL, "semiglobal": SW_MODE_SEMIGLOBAL}
+
+
+def _mode(mode) -> int:
+    """The SW_MODE_* value of ``mode``: "local", "global" (seq1 and seq2 end to end) or "semiglobal"
+    (seq1, the query, end to end inside seq2, the record, whose flanks are free)."""
+    try:
+        return _MODES[mode]
+    except (KeyError, TypeError):
+        raise ValueError("unknown alignment mode %r: use 'local', 'global' or 'semiglobal'" % (mode,)) from None
+
+
+def score_matrix(seq1, seq2, matrix: Matrix, gap_init: int, gap_ext: int, mode: str = "local") -> int:
     """Best local-alignment score under ``matrix``; a gap of L residues costs gap_init + (L-1)*gap_ext
-    (BLAST's "open 11, extend 1" is gap_init=12, gap_ext=1)."""
+    (BLAST's "open 11, extend 1" is gap_init=12, gap_ext=1).  ``mode="global"`` / ``"semiglobal"``:
+    the end-to-end / query-inside-record score (include/algoGPU.h SW_MODE_*), which may be negative."""
+    if _mode(mode) != SW_MODE_LOCAL:
+        return score_matrix_batch([(seq1, seq2)], matrix, gap_init, gap_ext, mode=mode)[0]
     a, b = _u8(seq1), _u8(seq2)
     return _check(lib().sw_score_matrix(matrix._handle(), _ptr(a), _ptr(b), len(a), len(b), int(gap_init), int(gap_ext)))
 
 
-def score_matrix_batch(pairs: Iterable[Sequence], matrix: Matrix, gap_init: int, gap_ext: int) -> list:
-    """Scores of many independent pairs under ``matrix`` in one launch (sw_score_matrix_batch)."""
+def score_matrix_batch(pairs: Iterable[Sequence], matrix: Matrix, gap_init: int, gap_ext: int, mode: str = "local") -> list:
+    """Scores of many independent pairs under ``matrix`` in one launch (sw_score_matrix_batch; with
+    ``mode`` "global" or "semiglobal" sw_score_matrix_batch_mode: one launch is one mode)."""
+    am = _mode(mode)
+    if am != SW_MODE_LOCAL and not isinstance(matrix, Matrix):
+        raise ValueError("mode=%r needs a substitution matrix (Matrix.equality gives equality scoring as one)" % mode)
+    return _score_matrix_batch(pairs, matrix, gap_init, gap_ext, am if am != SW_MODE_LOCAL else None)
+
+
+def _score_matrix_batch(pairs, matrix, gap_init: int, gap_ext: int, am) -> list:
+    """am None: sw_score_matrix_batch; else sw_score_matrix_batch_mode with that SW_MODE_* value."""
     arrs = [(_u8(a), _u8(b)) for a, b in pairs]
     n = len(arrs)
     if n == 0:
@@ -556,7 +596,10 @@ def score_matrix_batch(pairs: Iterable[Sequence], matrix: Matrix, gap_init: int,
     AL = (ctypes.c_int * n)(*[len(x) for x, _ in arrs])
     BL = (ctypes.c_int * n)(*[len(y) for _, y in arrs])
     out = (ctypes.c_int * n)()
-    _check(lib().sw_score_matrix_batch(matrix._handle(), A, AL, B, BL, n, int(gap_init), int(gap_ext), out))
+    if am is not None:
+        _check(lib().sw_score_matrix_batch_mode(matrix._handle(), A, AL, B, BL, n, int(gap_init), int(gap_ext), am, out))
+    else:
+        _check(lib().sw_score_matrix_batch(matrix._handle(), A, AL, B, BL, n, int(gap_init), int(gap_ext), out))
     return list(out)
 
 
@@ -564,11 +607,13 @@ def score_matrix_batch(pairs: Iterable[Sequence], matrix: Matrix, gap_init: int,
 
 @dataclass(frozen=True)
 class Alignment:
-    """One local alignment: its score, the half-open ranges [beg1, end1) of seq1 and [beg2, end2)
+    """One alignment: its score, the half-open ranges [beg1, end1) of seq1 and [beg2, end2)
     of seq2 it covers, and its operations: ``ops`` is a tuple of (length, op) with op one of "M" (a
     residue of seq1 aligned with one of seq2), "I" (a residue of seq1 against a gap), "D" (a
-    residue of seq2 against a gap); ``cigar`` the same as a string such as ``12M2D40M``.  A pair
-    with score 0 has empty ranges at 0 and no operations."""
+    residue of seq2 against a gap); ``cigar`` the same as a string such as ``12M2D40M``.  Local: a
+    pair with score 0 has empty ranges at 0 and no operations, and an alignment begins and ends
+    with an M.  Global covers [0, n) x [0, m) and semi-global [0, n) x [beg2, end2); both may begin
+    or end with a gap and have a negative score, and a score of 0 says nothing about emptiness."""
     score: int
     beg1: int
     end1: int
@@ -642,8 +687,11 @@ def _align_call(call, n: int, cap: int) -> list:
 _LONG_CIGAR_CAP = 1 << 16
 
 
-def _align_pairs(f, pairs, matrix, gap_init: int, gap_ext: int, cap: int = 0) -> list:
-    """f: one of the library's sw_align_matrix_* entry points over host pairs."""
+def _align_pairs(f, pairs, matrix, gap_init: int, gap_ext: int, cap: int = 0, mode=None) -> list:
+    """f: one of the library's sw_align_matrix_* entry points over host pairs (mode: a *_mode one)."""
+    if mode is not None and not isinstance(matrix, Matrix):
+        raise ValueError("an alignment mode needs a substitution matrix (Matrix.equality gives equality scoring as one)")
+    extra = () if mode is None else (int(mode),)
     arrs = [(_u8(a), _u8(b)) for a, b in pairs]
     n = len(arrs)
     if n == 0:
@@ -654,14 +702,27 @@ def _align_pairs(f, pairs, matrix, gap_init: int, gap_ext: int, cap: int = 0) ->
     AL = (ctypes.c_int * n)(*[len(x) for x, _ in arrs])
     BL = (ctypes.c_int * n)(*[len(y) for _, y in arrs])
     return _align_call(lambda out, cig, cap, used: f(matrix._handle(), A, AL, B, BL, n, int(gap_init), int(gap_ext),
-                                                     out, cig, cap, used), n, max(16 * n, cap))
+                                                     *extra, out, cig, cap, used), n, max(16 * n, cap))
 
 
-def align_matrix_batch(pairs: Iterable[Sequence], matrix: Matrix, gap_init: int, gap_ext: int, cpu: bool = False) -> list:
+def align_matrix_batch(pairs: Iterable[Sequence], matrix: Matrix, gap_init: int, gap_ext: int, cpu: bool = False,
+                       mode: str = "local", long: bool = False) -> list:
     """An :class:`Alignment` per pair under ``matrix`` (seq1 is its first index) with affine gaps, on
     the GPU (sw_align_matrix_batch: the traced matrix kernel and a walk) or, with ``cpu=True``, from
     the library's plain full-matrix aligner on the host (sw_align_matrix_cpu), which gives the same
-    result.  Which alignment is reported when several reach the score is fixed (include/algoGPU.h)."""
+    result.  Which alignment is reported when several reach the score is fixed (include/algoGPU.h).
+    ``mode``: "local", "global" (both sequences end to end) or "semiglobal" (seq1 end to end inside
+    seq2); ``long=True`` is :func:`align_matrix_long`, which is local only."""
+    am = _mode(mode)
+    if long:
+        if am != SW_MODE_LOCAL:
+            raise ValueError("mode=%r is not built for long=True (checkpointed traceback): it is local only" % mode)
+        if cpu:
+            raise ValueError("long=True is a GPU path: not with cpu=True")
+        return align_matrix_long(pairs, matrix, gap_init, gap_ext)
+    if am != SW_MODE_LOCAL:
+        f = lib().sw_align_matrix_cpu_mode if cpu else lib().sw_align_matrix_batch_mode
+        return _align_pairs(f, pairs, matrix, gap_init, gap_ext, mode=am)
     return _align_pairs(lib().sw_align_matrix_cpu if cpu else lib().sw_align_matrix_batch, pairs, matrix, gap_init, gap_ext)
 
 
@@ -684,9 +745,10 @@ def align_long_plan(n: int, m: int) -> dict:
             "full_trace_bytes": p.full_trace_bytes}
 
 
-def align_matrix(seq1, seq2, matrix: Matrix, gap_init: int, gap_ext: int, cpu: bool = False) -> Alignment:
+def align_matrix(seq1, seq2, matrix: Matrix, gap_init: int, gap_ext: int, cpu: bool = False, mode: str = "local",
+                 long: bool = False) -> Alignment:
     """One pair (see :func:`align_matrix_batch`)."""
-    return align_matrix_batch([(seq1, seq2)], matrix, gap_init, gap_ext, cpu=cpu)[0]
+    return align_matrix_batch([(seq1, seq2)], matrix, gap_init, gap_ext, cpu=cpu, mode=mode, long=long)[0]
 
 
 def last_align_ms() -> tuple:

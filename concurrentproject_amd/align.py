@@ -16,7 +16,12 @@ pair, I a query residue against a gap, D a record residue against a gap; ``*`` f
 Only the top K of each query are aligned.  Without --matrix the alignments are made under the
 equality table of --params over the bytes present (at most 32 distinct ones).  --long makes the
 same alignments by checkpointed traceback (Database.align(long=True)): for hits so long that a
-whole pair's trace does not fit option trace_mb; the lines are the same."""
+whole pair's trace does not fit option trace_mb; the lines are the same.
+
+--mode global|semiglobal (with --matrix; default local): the query and the record end to end, or
+the whole query inside the record with the record's flanks free.  Scores may be negative, an
+alignment may begin or end with a gap, and the queries are searched one after another
+(Database.search(mode=...)).  Not with --long."""
 import argparse
 import sys
 import time
@@ -38,9 +43,16 @@ def main(argv=None) -> int:
     ap.add_argument("--alignments", action="store_true", help="align the top K hits: ranges and cigar per line")
     ap.add_argument("--long", action="store_true",
                     help="with --alignments: checkpointed traceback, for hits whose whole trace does not fit (same lines)")
+    ap.add_argument("--mode", choices=("local", "global", "semiglobal"), default="local",
+                    help="alignment mode of a --matrix search: global = query and record end to end, semiglobal = the "
+                         "whole query inside the record")
     a = ap.parse_args(argv)
     if a.long and not a.alignments:
         ap.error("--long goes with --alignments")
+    if a.mode != "local" and a.matrix is None:
+        ap.error("--mode %s requires --matrix (and --gaps)" % a.mode)
+    if a.mode != "local" and a.long:
+        ap.error("--long is local only: not with --mode %s" % a.mode)
     if (a.matrix is None) != (a.gaps is None):
         ap.error("--matrix and --gaps go together")
     matrix, gaps = None, (None, None)
@@ -55,7 +67,12 @@ def main(argv=None) -> int:
     with Database.open(a.db) as db, Database.open(a.query) as qs:
         lens = db.lengths()
         t0 = time.perf_counter()
-        scores = db.search_db(qs, matrix=matrix, gap_init=gaps[0], gap_ext=gaps[1])
+        if a.mode != "local":   # one query after another: search_db is local only
+            scores = np.zeros((len(qs), len(db)), dtype=np.int32)
+            for q in range(len(qs)):
+                scores[q] = db.search(qs.record(q)[1], matrix=matrix, gap_init=gaps[0], gap_ext=gaps[1], mode=a.mode)
+        else:
+            scores = db.search_db(qs, matrix=matrix, gap_init=gaps[0], gap_ext=gaps[1])
         dt = time.perf_counter() - t0
         cells = int(qs.lengths().sum()) * int(lens.sum())
         out = sys.stdout
@@ -76,7 +93,7 @@ def main(argv=None) -> int:
             sc = scores[q]
             order = np.lexsort((np.arange(len(sc)), -sc.astype(np.int64)))[:a.top]
             if a.alignments:
-                al = db.align(qs.record(q)[1], [int(i) for i in order], amatrix, agaps[0], agaps[1], long=a.long)
+                al = db.align(qs.record(q)[1], [int(i) for i in order], amatrix, agaps[0], agaps[1], long=a.long, mode=a.mode)
                 for r, (i, x) in enumerate(zip(order, al)):
                     out.write("%d\t%s\t%d\t%d\t%d\t%s\t%d\t%d\t%d\t%d\t%s\n"
                               % (q, qh, r + 1, int(sc[i]), int(i), db.header(int(i)), x.beg1, x.end1, x.beg2, x.end2,

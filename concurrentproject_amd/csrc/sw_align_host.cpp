@@ -7,6 +7,8 @@
 // the checkpointed traceback of long pairs (sw_align_matrix_long): strips, checkpoint and strip
 // trace bytes, the two budgets' refusals and the greedy packing of groups and rounds; the exported
 // sw_align_long_plan (sw_matrix.hip) only reads option "trace_mb" and calls it.
+// And the host side of global and semi-global alignment (SW_MODE_*): the mode and score-range checks,
+// the answers for empty sequences, and sw_align_matrix_cpu_mode, the same plain aligner for those modes.
 #include "sw_matrix_host.h"
 #include "../../include/algoGPU.h"
 
@@ -183,7 +185,121 @@ void align_pack(const long long* need, int n, long long budget, std::vector<int>
     }
 }
 
+bool mode_ok(const char* fn, int mode) {
+    if (mode == SW_MODE_LOCAL || mode == SW_MODE_GLOBAL || mode == SW_MODE_SEMIGLOBAL) return true;
+    char m[160];
+    std::snprintf(m, sizeof m, "%s: unknown alignment mode %d (0 local, 1 global, 2 semi-global)", fn, mode);
+    report_error(m);
+    return false;
+}
+
+bool mode_range_ok(int alen, int blen, int gap_init, int gap_ext, const char* what, int idx) {
+    const long long unit = std::max<long long>(std::max(gap_init, gap_ext), 127);
+    if (((long long)alen + blen + 1024) * unit >= (1LL << 28)) {
+        char m[200];
+        std::snprintf(m, sizeof m,
+                      "%s %d: score range exceeds the int32 engine in this mode ((n + m + 1024) * max(G_INIT, G_EXT, 127) >= 2^28)",
+                      what, idx);
+        report_error(m);
+        return false;
+    }
+    return true;
+}
+
+int mode_empty_score(int alen, int blen, int gap_init, int gap_ext, int mode) {
+    const int L = mode == SW_MODE_GLOBAL ? std::max(alen, blen) : mode == SW_MODE_SEMIGLOBAL ? alen : 0;
+    return L > 0 ? -(gap_init + (L - 1) * std::min(gap_ext, gap_init)) : 0;
+}
+
+void align_mode_empty(AlignSink& sink, int k, int alen, int blen, int gap_init, int gap_ext, int mode) {
+    const int score = mode_empty_score(alen, blen, gap_init, gap_ext, mode);
+    const bool seq1 = alen > 0;   // the run: I over seq1, or (global only) D over seq2
+    const int L = mode == SW_MODE_GLOBAL ? std::max(alen, blen) : mode == SW_MODE_SEMIGLOBAL ? alen : 0;
+    if (L == 0) {
+        sink.set_empty(k);
+        return;
+    }
+    const std::vector<unsigned char> ops((size_t)L, (unsigned char)(seq1 ? 1 : 2));
+    sink.set(k, score, 0, seq1 ? L : 0, 0, seq1 ? 0 : L, ops.data(), L);
+}
+
 namespace {
+
+constexpr int CPU_NEG = -(1 << 30);   // "minus infinity": mode_range_ok keeps every cell far above it
+
+// Global and semi-global (include/algoGPU.h): one pair, both lengths > 0, three full rows of state
+// and a byte a cell as align_pair below, the unclamped recurrence with its borders, the end rule and
+// the walk with its border exits.
+void align_pair_mode(const sw_matrix* mx, const unsigned char* a, int n, const unsigned char* b, int m, int go, int ge,
+                     int mode, std::vector<unsigned char>& cell, std::vector<int>& hup, std::vector<int>& fup,
+                     std::vector<unsigned char>& ops, int k, AlignSink& sink) {
+    const int gx = std::min(go, ge);
+    cell.assign((size_t)n * (size_t)m, 0);
+    hup.resize((size_t)n);
+    fup.assign((size_t)n, CPU_NEG);
+    for (int i = 0; i < n; ++i) hup[(size_t)i] = -(go + i * gx);   // H[i][-1]
+    int best = CPU_NEG, bj = 0;
+    for (int j = 0; j < m; ++j) {
+        const int cb = mx->code[b[j]];
+        // H[-1][j] and H[-1][j-1]; E[-1][j] is minus infinity
+        int hleft = mode == SW_MODE_GLOBAL ? -(go + j * gx) : 0;
+        int hdiag = j == 0 || mode != SW_MODE_GLOBAL ? 0 : -(go + (j - 1) * gx);
+        int eleft = CPU_NEG;
+        unsigned char* row = cell.data() + (size_t)j * (size_t)n;
+        for (int i = 0; i < n; ++i) {
+            const int eo = hleft - go, ee = eleft - ge;
+            const int fo = hup[(size_t)i] - go, fe = fup[(size_t)i] - ge;
+            const int E = std::max(eo, ee);
+            const int F = std::max(fo, fe);
+            const int t = hdiag + mx->sc[mx->code[a[i]] * mx->k + cb];
+            const int H = std::max(t, std::max(E, F));
+            row[i] = (unsigned char)((t == H ? 1 : E == H ? 2 : 3) | (ee > eo ? 4 : 0) | (fe > fo ? 8 : 0));
+            hdiag = hup[(size_t)i];
+            hup[(size_t)i] = H;
+            fup[(size_t)i] = F;
+            hleft = H;
+            eleft = E;
+        }
+        // the end: H[n-1][m-1] (global); the largest H[n-1][j], the smallest such j (semi-global)
+        const int h = hup[(size_t)n - 1];
+        if (mode == SW_MODE_GLOBAL ? j == m - 1 : h > best) {
+            best = h;
+            bj = j;
+        }
+    }
+    ops.resize((size_t)n + (size_t)m);
+    long long nops = 0;
+    int i = n - 1, j = bj, state = 0;   // 0 H, 1 E, 2 F
+    while (i >= 0 && j >= 0 && nops < (long long)n + m) {
+        const int c = cell[(size_t)j * (size_t)n + (size_t)i];
+        if (state == 0) {
+            const int src = c & 3;
+            if (src == 1) {
+                ops[(size_t)nops++] = 0;
+                --i;
+                --j;
+            } else {
+                state = src == 2 ? 1 : 2;
+            }
+        } else if (state == 1) {
+            ops[(size_t)nops++] = 1;
+            state = (c & 4) ? 1 : 0;
+            --i;
+        } else {
+            ops[(size_t)nops++] = 2;
+            state = (c & 8) ? 2 : 0;
+            --j;
+        }
+    }
+    // the border exits: at j < 0 the rest of seq1 is one leading I run; at i < 0 the rest of seq2 is
+    // one leading D run (global) or free (semi-global: beg2 = j + 1)
+    if (j < 0) {
+        for (; i >= 0 && nops < (long long)n + m; --i) ops[(size_t)nops++] = 1;
+    } else if (i < 0 && mode == SW_MODE_GLOBAL) {
+        for (; j >= 0 && nops < (long long)n + m; --j) ops[(size_t)nops++] = 2;
+    }
+    sink.set(k, best, i + 1, n, j + 1, bj + 1, ops.data(), nops);
+}
 
 // One pair, both lengths > 0.  cell[j * n + i]: bits 0-1 where H came from (0 none: H = 0, 1 diagonal,
 // 2 E, 3 F), bit 2 E extended a gap (else opened one), bit 3 the same for F; E runs along seq1
@@ -280,6 +396,35 @@ int sw_align_matrix_cpu(const sw_matrix* mx, const unsigned char* const* a, cons
     for (int k = 0; k < npairs; ++k) {
         if (alen[k] == 0 || blen[k] == 0) sink.set_empty(k);
         else align_pair(mx, a[k], alen[k], b[k], blen[k], gap_init, gap_ext, cell, hup, fup, ops, k, sink);
+    }
+    return sink.finish(cigar, cigar_cap, cigar_used);
+}
+
+int sw_align_matrix_cpu_mode(const sw_matrix* mx, const unsigned char* const* a, const int* alen,
+                             const unsigned char* const* b, const int* blen, int npairs, int gap_init, int gap_ext, int mode,
+                             sw_alignment* out, unsigned* cigar, long long cigar_cap, long long* cigar_used) {
+    if (!mode_ok("sw_align_matrix_cpu_mode", mode)) return -1;
+    if (mode == SW_MODE_LOCAL)
+        return sw_align_matrix_cpu(mx, a, alen, b, blen, npairs, gap_init, gap_ext, out, cigar, cigar_cap, cigar_used);
+    if (align_check("sw_align_matrix_cpu_mode", mx, a, alen, b, blen, npairs, gap_init, gap_ext, out, cigar, cigar_cap,
+                    cigar_used))
+        return -1;
+    for (int k = 0; k < npairs; ++k) {
+        if (!mode_range_ok(alen[k], blen[k], gap_init, gap_ext, "pair", k)) return -1;
+        if ((long long)alen[k] * blen[k] > CPU_MAX_CELLS) {
+            char m[160];
+            std::snprintf(m, sizeof m, "pair %d: %lld cells are more than the CPU aligner's full matrix holds (2^32)", k,
+                          (long long)alen[k] * blen[k]);
+            report_error(m);
+            return -1;
+        }
+    }
+    AlignSink sink{out, {}};
+    std::vector<unsigned char> cell, ops;
+    std::vector<int> hup, fup;
+    for (int k = 0; k < npairs; ++k) {
+        if (alen[k] == 0 || blen[k] == 0) align_mode_empty(sink, k, alen[k], blen[k], gap_init, gap_ext, mode);
+        else align_pair_mode(mx, a[k], alen[k], b[k], blen[k], gap_init, gap_ext, mode, cell, hup, fup, ops, k, sink);
     }
     return sink.finish(cigar, cigar_cap, cigar_used);
 }

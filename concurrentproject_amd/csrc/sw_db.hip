@@ -220,7 +220,8 @@ int check_records(sw_db* db, const sw_matrix* mx) {
     return 0;
 }
 
-int check_query(const sw_db* db, const sw_matrix* mx, const unsigned char* query, int qlen, int qidx) {
+int check_query(const sw_db* db, const sw_matrix* mx, const unsigned char* query, int qlen, int qidx, int amode = SW_MODE_LOCAL,
+                int gap_init = 0, int gap_ext = 0) {
     const long long bad = matrix_first_bad(mx, query, qlen);
     if (bad >= 0) {
         char m[160];
@@ -230,6 +231,7 @@ int check_query(const sw_db* db, const sw_matrix* mx, const unsigned char* query
         return -1;
     }
     for (size_t r = 0; r < db->len.size(); ++r) {
+        if (amode != SW_MODE_LOCAL && !mode_range_ok(qlen, db->len[r], gap_init, gap_ext, "record", (int)r)) return -1;
         if ((long long)std::min(qlen, db->len[r]) * mx->max_entry >= (1LL << 28)) {
             char m[160];
             std::snprintf(m, sizeof m, "record %d: score range exceeds the int32 engine (min length * largest entry >= 2^28)", (int)r);
@@ -242,10 +244,10 @@ int check_query(const sw_db* db, const sw_matrix* mx, const unsigned char* query
 
 // the query spread across the lanes against every record, longest first; scores in record order
 int search_matrix(sw_db* db, const sw_matrix* mx, const unsigned char* query, int qlen, int gap_init, int gap_ext,
-                  int* scores_out, int qslot, int qidx) {
+                  int* scores_out, int qslot, int qidx, int amode = SW_MODE_LOCAL) {
     const int nrec = (int)db->len.size();
     if (nrec == 0) return 0;
-    if (check_records(db, mx) || check_query(db, mx, query, qlen, qidx)) return -1;
+    if (check_records(db, mx) || check_query(db, mx, query, qlen, qidx, amode, gap_init, gap_ext)) return -1;
     sw_db::Dev* v = nullptr;
     if (device_arena(db, std::max(qlen, qslot), &v)) return -1;
     std::vector<int64_t> b_off;
@@ -256,10 +258,13 @@ int search_matrix(sw_db* db, const sw_matrix* mx, const unsigned char* query, in
     std::vector<int64_t> a_off((size_t)nrec, qoff);
     std::vector<int> alen((size_t)nrec, qlen);
     if (matrix_score_device(mx, v->arena, a_off.data(), alen.data(), b_off.data(), blen.data(), nrec, gap_init, gap_ext,
-                            v->scores, true))
+                            v->scores, true, amode))
         return -1;
     std::vector<int> got((size_t)nrec);
     DBCHK(hipMemcpy(got.data(), v->scores, (size_t)nrec * sizeof(int), hipMemcpyDeviceToHost));
+    if (amode != SW_MODE_LOCAL)   // an empty query or record is answered on the host
+        for (int k = 0; k < nrec; ++k)
+            if (qlen == 0 || blen[(size_t)k] == 0) got[(size_t)k] = mode_empty_score(qlen, blen[(size_t)k], gap_init, gap_ext, amode);
     for (int k = 0; k < nrec; ++k) scores_out[db->order[k]] = got[k];
     return 0;
 }
@@ -267,7 +272,7 @@ int search_matrix(sw_db* db, const sw_matrix* mx, const unsigned char* query, in
 // the query (seq1, across the lanes) aligned with the chosen records, out of the device arena;
 // long_pairs: by checkpointed traceback (sw_db_align_matrix_long)
 int align_matrix(sw_db* db, const sw_matrix* mx, const unsigned char* query, int qlen, const int* record_idx, int nidx,
-                 int gap_init, int gap_ext, AlignSink& sink, bool long_pairs) {
+                 int gap_init, int gap_ext, AlignSink& sink, bool long_pairs, int amode = SW_MODE_LOCAL) {
     const int nrec = (int)db->len.size();
     for (int k = 0; k < nidx; ++k)
         if (record_idx[k] < 0 || record_idx[k] >= nrec) {
@@ -289,9 +294,11 @@ int align_matrix(sw_db* db, const sw_matrix* mx, const unsigned char* query, int
         b_off[(size_t)k] = db->off[(size_t)record_idx[k]];
         blen[(size_t)k] = db->len[(size_t)record_idx[k]];
     }
-    const auto align_device = long_pairs ? matrix_align_long_device : matrix_align_device;
-    return align_device(mx, v->arena, a_off.data(), alen.data(), b_off.data(), blen.data(), record_idx, nidx, gap_init,
-                        gap_ext, "record", sink);
+    if (long_pairs)
+        return matrix_align_long_device(mx, v->arena, a_off.data(), alen.data(), b_off.data(), blen.data(), record_idx, nidx,
+                                        gap_init, gap_ext, "record", sink);
+    return matrix_align_device(mx, v->arena, a_off.data(), alen.data(), b_off.data(), blen.data(), record_idx, nidx, gap_init,
+                               gap_ext, "record", sink, amode);
 }
 
 }  // namespace
@@ -309,6 +316,32 @@ int sw_db_search_matrix(sw_db* db, const sw_matrix* mx, const unsigned char* que
     }
     std::lock_guard<std::mutex> g(db->mu);
     return search_matrix(db, mx, query, qlen, gap_init, gap_ext, scores_out, qlen, 0);
+}
+
+int sw_db_search_matrix_mode(sw_db* db, const sw_matrix* mx, const unsigned char* query, int qlen, int gap_init,
+                             int gap_ext, int mode, int* scores_out) {
+    if (!db || !mx || qlen < 0 || (qlen > 0 && !query) || (!db->len.empty() && !scores_out)) {
+        report_error("sw_db_search_matrix_mode: invalid arguments");
+        return -1;
+    }
+    if (!mode_ok("sw_db_search_matrix_mode", mode)) return -1;
+    std::lock_guard<std::mutex> g(db->mu);
+    return search_matrix(db, mx, query, qlen, gap_init, gap_ext, scores_out, qlen, 0, mode);
+}
+
+int sw_db_align_matrix_mode(sw_db* db, const sw_matrix* mx, const unsigned char* query, int qlen, const int* record_idx,
+                            int nidx, int gap_init, int gap_ext, int mode, sw_alignment* out, unsigned* cigar,
+                            long long cigar_cap, long long* cigar_used) {
+    if (!db || !mx || qlen < 0 || (qlen > 0 && !query) || nidx < 0 || cigar_cap < 0 || !cigar_used ||
+        (cigar_cap > 0 && !cigar) || (nidx > 0 && (!record_idx || !out))) {
+        report_error("sw_db_align_matrix_mode: invalid arguments");
+        return -1;
+    }
+    if (!mode_ok("sw_db_align_matrix_mode", mode)) return -1;
+    std::lock_guard<std::mutex> g(db->mu);
+    AlignSink sink{out, {}};
+    if (align_matrix(db, mx, query, qlen, record_idx, nidx, gap_init, gap_ext, sink, false, mode)) return -1;
+    return sink.finish(cigar, cigar_cap, cigar_used);
 }
 
 // (one query after another: the pipelining of sw_db_search_db is not done for matrix searches)

@@ -38,6 +38,11 @@
 // Such pairs go through sw_align_matrix_long: a locate pass that keeps every strip's right-edge
 // column (a checkpoint), then the strips filled again one at a time, traced, from the checkpoint on
 // their left, and walked right to left -- the same bits, so the same alignment (LONG PAIRS below).
+//
+// ALIGNMENT MODES.  Everything above is local alignment.  Global and semi-global alignment
+// (include/algoGPU.h SW_MODE_*) are a third template parameter of the same
+// step, pair loop and kernel (AM, below): no clamp, borders made by the set-up and the inflow, the
+// end read from one column.  The local instantiations are the code they were; the long path is local only.
 #include "sw_device.h"
 #include "sw_matrix_host.h"
 #include "../../include/algoGPU.h"
@@ -120,13 +125,35 @@ typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 // decisions a lane a step; M_LOCATE the bookkeeping without the stores (long pairs, below).
 constexpr int M_SCORE = 0, M_TRACE = 1, M_LOCATE = 2;
 
-template <int W, int MODE>
+// AM: the alignment mode (include/algoGPU.h SW_MODE_*), a compile-time parameter as MODE is: the
+// local instantiations are the code they were.  Global and semi-global have
+// no clamp at 0, so nothing makes the borders for free:
+//   * the top border H[i][-1] = -(G_INIT + i * gx), gx = min(G_EXT, G_INIT), is the E chain of row
+//     -1, which the pre-border cells compute themselves: setup() puts H[i0][-1] (as H and as E) into
+//     the strip's first column, whose state before step 0 is row -1, H[i0-1][-1] into its diagonal,
+//     and MAT_NEG ("minus infinity") everywhere else.  Column c then meets row -1 at step c - 1 with
+//     t and F from rows <= -2 (MAT_NEG and below) and E = max(E - G_EXT, H - G_INIT) from column
+//     c - 1: exactly H[c][-1], one step before its first row arrives, at no cost in the step;
+//   * the left border of strip 0 is the inflow: H[-1][j] (0, or -(G_INIT + j * gx)) and E = MAT_NEG;
+//   * the end: one lane follows one column, n - 1 (`pstar` of the lane that holds it in the last
+//     strip), over the row window [0, m) (semi-global) or [m - 1, m) (global): jrow is the row of
+//     that column at this step minus the window's first row, MAT_NEG on every other lane, so
+//     pre-border, drain and dead-column cells are never candidates; the strict update keeps the
+//     smallest j.
+// Pre-border, drain and dead-column cells hold unclamped garbage: mode_range_ok (sw_align_host.cpp)
+// refuses the pairs on which any of it could wrap.
+constexpr int AM_LOCAL = SW_MODE_LOCAL, AM_GLOBAL = SW_MODE_GLOBAL, AM_SEMI = SW_MODE_SEMIGLOBAL;
+constexpr int MAT_NEG = -(1 << 30);
+
+template <int W, int MODE, int AM = AM_LOCAL>
 struct MStrip {
     static_assert(MODE == M_SCORE || W == TRACE_W, "a traced step stores one dword a lane");
+    static_assert(AM == AM_LOCAL || MODE != M_LOCATE, "the long path is local only");
     int cb[W], tb[W];                       // LDS offset of the column's table row / bias
     int hgA[W], hgB[W], eh[W], r[W], fh[W]; // DP state, as Strip (sw_kernels.hip)
     int L0, M, IOH, IOE, IOR;
     int Mkp, kp8;                           // M_TRACE, M_LOCATE: step * 8 + p at which M was reached; this step * 8
+    int pstar, jrow, wl, Mj;                // AM != AM_LOCAL: the end bookkeeping (above); M is H - G_INIT there
 
     __device__ __forceinline__ void setup(const MatArgs& a, const MatPair& pd, int strip, int lane,
                                           const unsigned char* s_code) {
@@ -150,6 +177,23 @@ struct MStrip {
             hgA[p] = -go; hgB[p] = -go; eh[p] = -ge; fh[p] = -ge; r[p] = a.k;
         }
         L0 = -go; IOH = -go; IOE = -ge; IOR = a.k;
+        if constexpr (AM != AM_LOCAL) {
+            const int gx = min(go, ge), i0 = strip * SW;
+            const int b0 = -(go + i0 * gx);   // H[i0][-1]
+#pragma unroll
+            for (int p = 0; p < W; ++p) {
+                hgA[p] = MAT_NEG; hgB[p] = MAT_NEG; eh[p] = MAT_NEG; fh[p] = MAT_NEG;
+            }
+            hgB[0] = lane == 0 ? b0 - go : MAT_NEG;   // the first step's hgPrev
+            eh[0] = lane == 0 ? b0 - ge : MAT_NEG;
+            L0 = lane == 0 ? (i0 > 0 ? b0 + gx : 0) - go : MAT_NEG;   // H[i0-1][-1]
+            IOE = MAT_NEG;
+            const int cl = pd.n - 1 - i0;   // column n - 1 in this strip (the last strip: 0 <= cl < SW)
+            const int jlo = AM == AM_GLOBAL ? pd.m - 1 : 0;
+            pstar = cl & (W - 1);
+            jrow = cl >= 0 && cl < SW && cl / W == lane ? -cl - jlo : MAT_NEG;
+            wl = pd.m - jlo;
+        }
     }
 
     // One anti-diagonal step (Strip::step with the score from the LDS table).
@@ -176,10 +220,15 @@ struct MStrip {
             const int rL = p > 0 ? r[q] : rL0;
             const int hgD = p > 0 ? hgCur[q] : L0;
             const int t = hgD + sv[p] + tb[p];           // H[i-1][j-1] + s(q_j, d_i)
-            const int E = max3i(ehL, hgL, 0);            // clamped E
-            const int F = max3i(fh[p], hgPrev[p], 0);    // clamped F
+            const int E = AM == AM_LOCAL ? max3i(ehL, hgL, 0) : max(ehL, hgL);               // clamped E (local)
+            const int F = AM == AM_LOCAL ? max3i(fh[p], hgPrev[p], 0) : max(fh[p], hgPrev[p]);   // clamped F (local)
             const int H = vmax3(t, E, F);
-            if constexpr (MODE != M_SCORE) {
+            if constexpr (AM != AM_LOCAL) {
+                if constexpr (MODE == M_TRACE) {   // source 0 is unused: there is no H = 0 stop
+                    const unsigned src = t == H ? 1u : (E == H ? 2u : 3u);
+                    bits |= (src | (ehL > hgL ? 4u : 0u) | (fh[p] > hgPrev[p] ? 8u : 0u)) << (4 * p);
+                }
+            } else if constexpr (MODE != M_SCORE) {
                 const bool up = t > M;
                 M = up ? t : M;
                 Mkp = up ? kp8 + p : Mkp;
@@ -204,6 +253,20 @@ struct MStrip {
             toff += 256u;
         }
         if constexpr (MODE != M_SCORE) kp8 += 8;
+        if constexpr (AM != AM_LOCAL) {   // the lane's cell of column n - 1, if its row is in the window
+            int cand = hgCur[0];
+#pragma unroll
+            for (int p = 1; p < W; ++p) cand = pstar == p ? hgCur[p] : cand;
+            const bool in = (unsigned)jrow < (unsigned)wl;
+            if constexpr (MODE != M_SCORE) {
+                const bool up = in && cand > M;
+                M = up ? cand : M;
+                Mj = up ? jrow : Mj;
+            } else {
+                M = in ? max(M, cand) : M;
+            }
+            jrow += 1;
+        }
     }
 
     __device__ __forceinline__ void run(const bool l63, const int go, const int ge, const signed char* s_tab,
@@ -232,7 +295,7 @@ __device__ __forceinline__ u32x2 mat_fetch_edge(const __amdgpu_buffer_rsrc_t scr
 // M_LOCATE: the same result without a trace; strip s reads its inflow from checkpoint column s - 1
 // of the pair and stores its right edge to column s (ckpt: column 0, ckpt_stride bytes a column,
 // m * 8 of them used), every column a buffer of its own, and the scratch is not touched.
-template <int W, int MODE>
+template <int W, int MODE, int AM = AM_LOCAL>
 __device__ void matrix_pair(const MatArgs& a, const MatPair& pd, const WalkPair& wp, const int lane, uint2* scr,
                             const signed char* s_tab, const unsigned char* s_code, unsigned char* ckpt = nullptr,
                             unsigned ckpt_stride = 0) {
@@ -255,11 +318,12 @@ __device__ void matrix_pair(const MatArgs& a, const MatPair& pd, const WalkPair&
                         : scr_rsrc;
     unsigned toff = (unsigned)lane * 4u;
     int bM = 0, bD = 0, bJ = 0;   // TRACE: the best of the strips so far: t, i + j, j
-    MStrip<W, MODE> S;
-    S.M = 0;
+    MStrip<W, MODE, AM> S;
+    S.M = AM == AM_LOCAL ? 0 : MAT_NEG;
+    if constexpr (AM != AM_LOCAL) S.Mj = 0;
     for (int strip = 0; strip < strips; ++strip) {
         S.setup(a, pd, strip, lane, s_code);
-        if constexpr (TRACE) {
+        if constexpr (TRACE && AM == AM_LOCAL) {
             S.M = 0;
             S.Mkp = 0;
             S.kp8 = 0;
@@ -284,8 +348,14 @@ __device__ void matrix_pair(const MatArgs& a, const MatPair& pd, const WalkPair&
             if (has_in) g_nxt = mat_fetch_edge(in_rsrc, k0 + C, lane, m);
             const bool live = k0 + lane < m;
             S.IOR = live ? (int)s_code[raw & 0xFFu] : a.k;
-            S.IOH = has_in && live ? (int)g.x : -go;
-            S.IOE = has_in && live ? (int)g.y : -ge;
+            if constexpr (AM == AM_LOCAL) {
+                S.IOH = has_in && live ? (int)g.x : -go;
+                S.IOE = has_in && live ? (int)g.y : -ge;
+            } else {   // strip 0: the left border H[-1][j], and no E to extend out of it
+                const int lb = AM == AM_GLOBAL ? -(go + (k0 + lane) * min(go, ge)) - go : -go;
+                S.IOH = has_in && live ? (int)g.x : lb;
+                S.IOE = has_in && live ? (int)g.y : MAT_NEG;
+            }
             S.run(l63, go, ge, s_tab, trc, toff);
             if (has_out) {   // lane l holds the right edge of row k0 + l - (SW - 1)
                 const int row_out = k0 + lane - (SW - 1);
@@ -296,7 +366,7 @@ __device__ void matrix_pair(const MatArgs& a, const MatPair& pd, const WalkPair&
         }
         // the next strip (or the next pair's) reads what this one stored
         if (has_out) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
-        if constexpr (TRACE) {   // the lane's cell of this strip: column lane * W + p, reached at step k
+        if constexpr (TRACE && AM == AM_LOCAL) {   // the lane's cell of this strip: column lane * W + p, reached at step k
             const int k = S.Mkp >> 3, cl = lane * W + (S.Mkp & 7);
             const int j = k - cl, d = strip * SW + k;
             const bool better = S.M > bM || (S.M == bM && (d < bD || (d == bD && j < bJ)));
@@ -304,6 +374,29 @@ __device__ void matrix_pair(const MatArgs& a, const MatPair& pd, const WalkPair&
             bD = better ? d : bD;
             bJ = better ? j : bJ;
         }
+    }
+    if constexpr (AM != AM_LOCAL) {   // one lane holds the end; M is H - G_INIT
+        int M = S.M, J = S.Mj;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const int oM = __shfl_xor(M, off), oJ = __shfl_xor(J, off);
+            J = oM > M ? oJ : J;
+            M = max(M, oM);
+        }
+        // lane 0's store without a branch on the lane (below)
+        if constexpr (TRACE) {
+            const int jlo = AM == AM_GLOBAL ? m - 1 : 0;
+            const __amdgpu_buffer_rsrc_t res_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+                a.res, 0, (int)((unsigned)a.nscores * (unsigned)sizeof(TraceRes)), RSRC_FLAGS);
+            __builtin_amdgcn_raw_buffer_store_b128(u32x4{(unsigned)(M + go), (unsigned)(pd.n - 1), (unsigned)(J + jlo), 0u},
+                                                   res_rsrc, lane == 0 ? (unsigned)pd.out_idx * (unsigned)sizeof(TraceRes) : OOR,
+                                                   0, 0);
+        } else {
+            const __amdgpu_buffer_rsrc_t sc_rsrc =
+                __builtin_amdgcn_make_buffer_rsrc(a.scores, 0, (int)((unsigned)a.nscores * 4u), RSRC_FLAGS);
+            __builtin_amdgcn_raw_buffer_store_b32(M + go, sc_rsrc, lane == 0 ? (unsigned)pd.out_idx * 4u : OOR, 0, 0);
+        }
+        return;
     }
     if constexpr (TRACE) {
 #pragma unroll
@@ -332,7 +425,7 @@ __device__ void matrix_pair(const MatArgs& a, const MatPair& pd, const WalkPair&
     __builtin_amdgcn_raw_buffer_store_b32(M, sc_rsrc, lane == 0 ? (unsigned)pd.out_idx * 4u : OOR, 0, 0);
 }
 
-template <int W, bool TRACE = false>
+template <int W, bool TRACE = false, int AM = AM_LOCAL>
 __global__ void __launch_bounds__(256) sw_matrix_kernel(MatArgs a) {
     __shared__ unsigned s_tabw[2 * MAT_TAB_BYTES / 4];
     __shared__ unsigned s_codew[64];
@@ -363,7 +456,7 @@ __global__ void __launch_bounds__(256) sw_matrix_kernel(MatArgs a) {
             wp.trace_off = uniform64(wraw.trace_off);
             wp.trace_bytes = __builtin_amdgcn_readfirstlane(wraw.trace_bytes);
         }
-        matrix_pair<W, TRACE ? M_TRACE : M_SCORE>(a, pd, wp, lane, scr, s_tab, s_code);
+        matrix_pair<W, TRACE ? M_TRACE : M_SCORE, AM>(a, pd, wp, lane, scr, s_tab, s_code);
     }
 }
 
@@ -380,7 +473,72 @@ struct WalkArgs {
     unsigned char* ops;
     TraceRes* res;
     int npairs;
+    int amode;   // SW_MODE_*
 };
+
+// Global and semi-global: no H = 0 stop (source 0 is unused, and an error if met); the walk leaves
+// the matrix at j < 0 -- the remaining i + 1 residues of seq1 are one leading I run, the top border
+// H[i][-1] -- or at i < 0: global, the remaining j + 1 residues of seq2 are one leading D run;
+// semi-global, it stops there.  A gap is never extended out of a border (E[-1][j] and F[i][-1] are
+// minus infinity, so the fill recorded an opening), hence the walk leaves in state H.  Every M uses
+// a residue of both sequences, an I one of seq1, a D one of seq2: n + m bytes are still enough.
+__device__ void matrix_walk_mode(const WalkArgs& w, const MatPair& pd, const WalkPair& wp, TraceRes* r) {
+    int i = r->ei, j = r->ej, state = 0, err = 0, nops = 0;
+    const long long limit = (long long)pd.n + pd.m;
+    const unsigned* tr = reinterpret_cast<const unsigned*>(w.trace + wp.trace_off);
+    unsigned char* ops = w.ops + wp.ops_off;
+    if (i < 0 || i >= pd.n || j < 0 || j >= pd.m) err = WALK_RANGE;
+    while (err == 0 && i >= 0 && j >= 0) {
+        const int cl = i & (64 * TRACE_W - 1);
+        const unsigned long long dw =
+            ((unsigned long long)(i / (64 * TRACE_W)) * (unsigned)wp.steps + (unsigned)(j + cl)) * 64u + (unsigned)(cl >> 3);
+        if (dw * 4u >= wp.trace_bytes) {
+            err = WALK_RANGE;
+            break;
+        }
+        const unsigned nib = (tr[dw] >> (4 * (cl & 7))) & 15u;
+        if (state == 0) {
+            const unsigned src = nib & 3u;
+            if (src == 0) {
+                err = WALK_RANGE;
+                break;
+            }
+            if (src != 1) state = (int)src - 1;   // E: 1, F: 2
+        }
+        if (nops >= limit) {
+            err = WALK_OVERRUN;
+            break;
+        }
+        if (state == 0) {
+            ops[nops++] = 0;
+            --i;
+            --j;
+        } else if (state == 1) {
+            ops[nops++] = 1;
+            state = (nib & 4u) ? 1 : 0;
+            --i;
+        } else {
+            ops[nops++] = 2;
+            state = (nib & 8u) ? 2 : 0;
+            --j;
+        }
+    }
+    if (err == 0) {   // the border exits
+        const bool lead_i = j < 0;
+        const int run = lead_i ? i + 1 : (w.amode == SW_MODE_GLOBAL ? j + 1 : 0);
+        if (nops + (long long)run > limit) {
+            err = WALK_OVERRUN;
+        } else {
+            for (int k = 0; k < run; ++k) ops[nops++] = lead_i ? 1 : 2;
+            if (lead_i) i = -1;
+            else if (run > 0) j = -1;
+        }
+    }
+    r->bi = i + 1;
+    r->bj = j + 1;
+    r->nops = nops;
+    r->err = err;
+}
 
 __global__ void __launch_bounds__(64) sw_matrix_walk_kernel(WalkArgs w) {
     const int item = (int)(blockIdx.x * 64 + threadIdx.x);
@@ -388,6 +546,10 @@ __global__ void __launch_bounds__(64) sw_matrix_walk_kernel(WalkArgs w) {
     const MatPair pd = w.pairs[item];
     const WalkPair wp = w.walk[item];
     TraceRes* r = w.res + pd.out_idx;
+    if (w.amode != SW_MODE_LOCAL) {
+        matrix_walk_mode(w, pd, wp, r);
+        return;
+    }
     int i = r->ei, j = r->ej, state = 0, err = 0, nops = 0;
     const long long limit = (long long)pd.n + pd.m;
     if (r->score > 0) {
@@ -679,8 +841,9 @@ struct MatCtx {
     void* buf[13] = {};     // pairs, ctrl, scratch, arena, scores; traced launches: walk pairs, trace, results, operations;
                             // long pairs: locate items, checkpoints, strip items, walk states
     size_t cap[13] = {};
-    int wgs[7] = {0, 0, 0, 0, 0, 0, 0};   // resident workgroups per CU per W variant; [4]: the traced kernel,
-                                          // [5], [6]: the locate and the strip-fill kernel
+    int wgs[17] = {};                     // resident workgroups per CU per W variant; [4]: the traced kernel,
+                                          // [5], [6]: the locate and the strip-fill kernel; [7 + 5 * (mode - 1) + ...]:
+                                          // the same five for SW_MODE_GLOBAL and SW_MODE_SEMIGLOBAL
 };
 enum { B_PAIRS = 0, B_CTRL, B_SCRATCH, B_ARENA, B_SCORES, B_WALK, B_TRACE, B_RES, B_OPS, B_LONG, B_CKPT, B_ITEMS, B_STATE };
 thread_local float t_fill_ms = 0.f, t_walk_ms = 0.f;   // sw_last_align_ms
@@ -727,14 +890,21 @@ int ensure(MatCtx* c, int which, size_t bytes) {
 
 constexpr int W_OF[4] = {1, 2, 4, 8};
 
-const void* kernel_of(int wi) {
+template <int AM>
+const void* kernel_of_mode(int wi) {   // wi 4: the traced kernel
     switch (wi) {
-        case 0: return (const void*)sw_matrix_kernel<1>;
-        case 1: return (const void*)sw_matrix_kernel<2>;
-        case 2: return (const void*)sw_matrix_kernel<4>;
-        default: return (const void*)sw_matrix_kernel<8>;
+        case 0: return (const void*)sw_matrix_kernel<1, false, AM>;
+        case 1: return (const void*)sw_matrix_kernel<2, false, AM>;
+        case 2: return (const void*)sw_matrix_kernel<4, false, AM>;
+        case 3: return (const void*)sw_matrix_kernel<8, false, AM>;
+        default: return (const void*)sw_matrix_kernel<TRACE_W, true, AM>;
     }
 }
+// one launch is one mode: the run-time choice among the compiled kernels
+const void* kernel_of(int wi, int amode = AM_LOCAL) {
+    return amode == AM_GLOBAL ? kernel_of_mode<AM_GLOBAL>(wi) : amode == AM_SEMI ? kernel_of_mode<AM_SEMI>(wi) : kernel_of_mode<AM_LOCAL>(wi);
+}
+int wgs_slot(int wi, int amode) { return amode == AM_LOCAL ? wi : 7 + 5 * (amode - 1) + wi; }
 
 // steps of one pair at W columns per lane with n columns, times an issue-slot estimate of a step
 // (about 9 instructions a cell and 8 a step for the DPP moves and the I/O rotation)
@@ -776,12 +946,14 @@ void stage_matrix(MatArgs& a, const sw_matrix* mx) {
 }
 
 // act: the pairs to launch (both lengths > 0); d_scores[idx] receives each score, every other
-// entry of d_scores[0, nscores) is zeroed.
+// entry of d_scores[0, nscores) is zeroed.  amode != SW_MODE_LOCAL: seq1 always across the lanes.
 int launch(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, std::vector<DevSeq>& act, int gap_init,
-           int gap_ext, int* d_scores, int nscores, bool a_on_lanes) {
+           int gap_ext, int* d_scores, int nscores, bool a_on_lanes, int amode) {
     const auto t0 = std::chrono::steady_clock::now();
+    if (amode != AM_LOCAL) a_on_lanes = true;
     sw_stats st{};
     st.mode = MODE_MATRIX;
+    st.variant = amode;   // free on score-only matrix launches: the alignment mode (SW_MODE_*)
     st.C = MAT_C;
     st.items = nscores;
     MCHK(hipMemsetAsync(d_scores, 0, (size_t)std::max(nscores, 1) * sizeof(int), c->stream));
@@ -828,13 +1000,14 @@ int launch(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, std::ve
         if (d.n > SW) scratch_rows = std::max<long long>(scratch_rows, d.m);
         cells += (long long)d.n * d.m;
     }
-    if (c->wgs[wi] == 0) {
+    const int ws = wgs_slot(wi, amode);
+    if (c->wgs[ws] == 0) {
         int nb = 0;
-        MCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel_of(wi), 256, 0));
-        c->wgs[wi] = std::max(1, std::min(nb, 8));
+        MCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel_of(wi, amode), 256, 0));
+        c->wgs[ws] = std::max(1, std::min(nb, 8));
     }
     long long blocks = sw_get_option("blocks");
-    if (blocks <= 0) blocks = (long long)c->cus * c->wgs[wi];
+    if (blocks <= 0) blocks = (long long)c->cus * c->wgs[ws];
     blocks = std::max<long long>(1, std::min<long long>(blocks, ((long long)act.size() + 3) / 4));
     // the scratch: a right-edge column per resident wave, at most 1 GiB in all
     scratch_rows = (scratch_rows + 63) / 64 * 64;
@@ -861,11 +1034,16 @@ int launch(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, std::ve
 
     MCHK(hipEventRecord(c->ev0, c->stream));
     const dim3 grid((unsigned)blocks), block(256);
-    switch (wi) {
-        case 0: hipLaunchKernelGGL(sw_matrix_kernel<1>, grid, block, 0, c->stream, a); break;
-        case 1: hipLaunchKernelGGL(sw_matrix_kernel<2>, grid, block, 0, c->stream, a); break;
-        case 2: hipLaunchKernelGGL(sw_matrix_kernel<4>, grid, block, 0, c->stream, a); break;
-        default: hipLaunchKernelGGL(sw_matrix_kernel<8>, grid, block, 0, c->stream, a); break;
+    if (amode != AM_LOCAL) {
+        void* kargs[] = {&a};
+        MCHK(hipLaunchKernel(kernel_of(wi, amode), grid, block, kargs, 0, c->stream));
+    } else {
+        switch (wi) {
+            case 0: hipLaunchKernelGGL(sw_matrix_kernel<1>, grid, block, 0, c->stream, a); break;
+            case 1: hipLaunchKernelGGL(sw_matrix_kernel<2>, grid, block, 0, c->stream, a); break;
+            case 2: hipLaunchKernelGGL(sw_matrix_kernel<4>, grid, block, 0, c->stream, a); break;
+            default: hipLaunchKernelGGL(sw_matrix_kernel<8>, grid, block, 0, c->stream, a); break;
+        }
     }
     MCHK(hipGetLastError());
     MCHK(hipEventRecord(c->ev1, c->stream));
@@ -874,7 +1052,7 @@ int launch(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, std::ve
     st.W = W;
     st.cells = cells;
     st.blocks = (int)blocks;
-    st.waves_per_cu = 4 * c->wgs[wi];
+    st.waves_per_cu = 4 * c->wgs[ws];
     st.boundary_bytes = (long long)scratch_bytes;
     st.total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     report_stats(st);
@@ -895,7 +1073,7 @@ bool range_ok(const sw_matrix* mx, int alen, int blen, const char* what, int idx
 constexpr long long MAT_MAX_SEQ = (1LL << 27) - 1;   // the engine's longest sequence (8-B rows in a 32-bit resource)
 
 int score_host(const sw_matrix* mx, const unsigned char* const* a, const int* alen, const unsigned char* const* b,
-               const int* blen, int npairs, int gap_init, int gap_ext, int* out) {
+               const int* blen, int npairs, int gap_init, int gap_ext, int* out, int amode = AM_LOCAL) {
     if (!gaps_ok(gap_init, gap_ext)) return -1;
     size_t total = 0;
     for (int k = 0; k < npairs; ++k) {
@@ -906,6 +1084,7 @@ int score_host(const sw_matrix* mx, const unsigned char* const* a, const int* al
             report_error(m);
             return -1;
         }
+        if (amode != AM_LOCAL && !mode_range_ok(alen[k], blen[k], gap_init, gap_ext, "pair", k)) return -1;
         if (alen[k] == 0 || blen[k] == 0) continue;
         if (!range_ok(mx, alen[k], blen[k], "pair", k)) return -1;
         for (int s = 0; s < 2; ++s) {
@@ -942,9 +1121,13 @@ int score_host(const sw_matrix* mx, const unsigned char* const* a, const int* al
     }
     if (ensure(c, B_ARENA, total) || ensure(c, B_SCORES, (size_t)npairs * sizeof(int))) return -1;
     if (total) MCHK(hipMemcpyAsync(c->buf[B_ARENA], arena.data(), total, hipMemcpyHostToDevice, c->stream));
-    if (launch(c, mx, (const unsigned char*)c->buf[B_ARENA], act, gap_init, gap_ext, (int*)c->buf[B_SCORES], npairs, false))
+    if (launch(c, mx, (const unsigned char*)c->buf[B_ARENA], act, gap_init, gap_ext, (int*)c->buf[B_SCORES], npairs, false,
+               amode))
         return -1;
     MCHK(hipMemcpy(out, c->buf[B_SCORES], (size_t)npairs * sizeof(int), hipMemcpyDeviceToHost));
+    if (amode != AM_LOCAL)   // empty sequences are answered on the host
+        for (int k = 0; k < npairs; ++k)
+            if (alen[k] == 0 || blen[k] == 0) out[k] = mode_empty_score(alen[k], blen[k], gap_init, gap_ext, amode);
     return 0;
 }
 
@@ -962,7 +1145,8 @@ struct TracedOut {
     int blocks = 0;
 };
 int launch_traced(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, const std::vector<DevSeq>& act,
-                  int gap_init, int gap_ext, TracedOut& o) {
+                  int gap_init, int gap_ext, TracedOut& o, int amode) {
+    const int ws = wgs_slot(4, amode);
     constexpr int SW = 64 * TRACE_W;
     const size_t np = act.size();
     // longest first: the waves claim in order
@@ -997,13 +1181,13 @@ int launch_traced(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, 
         w.steps = (int)trace_steps(p.blen);
         trace_total += trace_bytes(p.alen, p.blen);
     }
-    if (c->wgs[4] == 0) {
+    if (c->wgs[ws] == 0) {
         int nb = 0;
-        MCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)sw_matrix_kernel<TRACE_W, true>, 256, 0));
-        c->wgs[4] = std::max(1, std::min(nb, 8));
+        MCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel_of(4, amode), 256, 0));
+        c->wgs[ws] = std::max(1, std::min(nb, 8));
     }
     long long blocks = sw_get_option("blocks");
-    if (blocks <= 0) blocks = (long long)c->cus * c->wgs[4];
+    if (blocks <= 0) blocks = (long long)c->cus * c->wgs[ws];
     blocks = std::max<long long>(1, std::min<long long>(blocks, ((long long)np + 3) / 4));
     scratch_rows = (scratch_rows + 63) / 64 * 64;
     if (scratch_rows > 0) blocks = std::max<long long>(1, std::min<long long>(blocks, (1LL << 30) / (scratch_rows * 8 * 4)));
@@ -1032,10 +1216,15 @@ int launch_traced(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, 
     a.walk = (const WalkPair*)c->buf[B_WALK];
     a.trace = (unsigned char*)c->buf[B_TRACE];
     a.res = (TraceRes*)c->buf[B_RES];
-    WalkArgs w{a.pairs, a.walk, a.trace, (unsigned char*)c->buf[B_OPS], a.res, (int)np};
+    WalkArgs w{a.pairs, a.walk, a.trace, (unsigned char*)c->buf[B_OPS], a.res, (int)np, amode};
 
     MCHK(hipEventRecord(c->ev0, c->stream));
-    hipLaunchKernelGGL((sw_matrix_kernel<TRACE_W, true>), dim3((unsigned)blocks), dim3(256), 0, c->stream, a);
+    if (amode != AM_LOCAL) {
+        void* kargs[] = {&a};
+        MCHK(hipLaunchKernel(kernel_of(4, amode), dim3((unsigned)blocks), dim3(256), kargs, 0, c->stream));
+    } else {
+        hipLaunchKernelGGL((sw_matrix_kernel<TRACE_W, true>), dim3((unsigned)blocks), dim3(256), 0, c->stream, a);
+    }
     MCHK(hipGetLastError());
     MCHK(hipEventRecord(c->ev1, c->stream));
     hipLaunchKernelGGL(sw_matrix_walk_kernel, dim3((unsigned)((np + 63) / 64)), dim3(64), 0, c->stream, w);
@@ -1313,19 +1502,28 @@ int matrix_align_long_device(const sw_matrix* mx, const unsigned char* d_arena, 
 
 int matrix_align_device(const sw_matrix* mx, const unsigned char* d_arena, const int64_t* a_off, const int* alen,
                         const int64_t* b_off, const int* blen, const int* name_idx, int npairs, int gap_init,
-                        int gap_ext, const char* what, AlignSink& sink) {
+                        int gap_ext, const char* what, AlignSink& sink, int amode) {
     const auto t0 = std::chrono::steady_clock::now();
     if (!gaps_ok(gap_init, gap_ext)) return -1;
     const long long budget = sw_get_option("trace_mb") << 20;
     for (int k = 0; k < npairs; ++k) {   // refused before anything is launched
+        if (amode != AM_LOCAL && !mode_range_ok(alen[k], blen[k], gap_init, gap_ext, what, name_idx ? name_idx[k] : k))
+            return -1;
         if (alen[k] == 0 || blen[k] == 0) continue;
         const long long need = trace_bytes(alen[k], blen[k]);
         if (need > budget) {
             char m[320];
-            std::snprintf(m, sizeof m,
-                          "%s %d: a %d x %d alignment needs %lld bytes of trace memory, more than option trace_mb = %lld MiB "
-                          "(sw_align_matrix_long / sw_db_align_matrix_long align such pairs a strip at a time)",
-                          what, name_idx ? name_idx[k] : k, alen[k], blen[k], need, budget >> 20);
+            if (amode != AM_LOCAL)
+                std::snprintf(m, sizeof m,
+                              "%s %d: a %d x %d alignment needs %lld bytes of trace memory, more than option trace_mb = %lld "
+                              "MiB, and the checkpointed traceback of long pairs is local only: no global or semi-global "
+                              "alignment of this pair",
+                              what, name_idx ? name_idx[k] : k, alen[k], blen[k], need, budget >> 20);
+            else
+                std::snprintf(m, sizeof m,
+                              "%s %d: a %d x %d alignment needs %lld bytes of trace memory, more than option trace_mb = %lld MiB "
+                              "(sw_align_matrix_long / sw_db_align_matrix_long align such pairs a strip at a time)",
+                              what, name_idx ? name_idx[k] : k, alen[k], blen[k], need, budget >> 20);
             report_error(m);
             return -1;
         }
@@ -1355,16 +1553,17 @@ int matrix_align_device(const sw_matrix* mx, const unsigned char* d_arena, const
             st.cells += (long long)alen[hi] * blen[hi];
         }
         if (!act.empty()) {
-            if (launch_traced(c, mx, d_arena, act, gap_init, gap_ext, o)) return -1;
+            if (launch_traced(c, mx, d_arena, act, gap_init, gap_ext, o, amode)) return -1;
             st.variant += 1;
             st.blocks = o.blocks;
-            st.waves_per_cu = 4 * c->wgs[4];
+            st.waves_per_cu = 4 * c->wgs[wgs_slot(4, amode)];
             st.boundary_bytes = std::max(st.boundary_bytes, o.trace_total);
         }
         size_t s = 0;
         for (int k = lo; k < hi; ++k) {
             if (alen[k] == 0 || blen[k] == 0) {
-                sink.set_empty(k);
+                if (amode != AM_LOCAL) align_mode_empty(sink, k, alen[k], blen[k], gap_init, gap_ext, amode);
+                else sink.set_empty(k);
                 continue;
             }
             const TraceRes& r = o.res[s];
@@ -1375,12 +1574,13 @@ int matrix_align_device(const sw_matrix* mx, const unsigned char* d_arena, const
                 report_error(m);
                 return -1;
             }
-            if (r.score <= 0) sink.set_empty(k);
+            if (amode == AM_LOCAL && r.score <= 0) sink.set_empty(k);
             else sink.set(k, r.score, r.bi, r.ei + 1, r.bj, r.ej + 1, o.ops.data() + o.ops_off[s], r.nops);
             ++s;
         }
         lo = hi;
     }
+    st.variant |= amode << 28;   // bits 28-29: the alignment mode (SW_MODE_*); the launches below them
     st.kernel_ms = t_fill_ms;
     st.total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     report_stats(st);
@@ -1389,14 +1589,14 @@ int matrix_align_device(const sw_matrix* mx, const unsigned char* d_arena, const
 
 int matrix_score_device(const sw_matrix* mx, const unsigned char* d_arena, const int64_t* a_off, const int* alen,
                         const int64_t* b_off, const int* blen, int npairs, int gap_init, int gap_ext, int* d_scores,
-                        bool a_on_lanes) {
+                        bool a_on_lanes, int amode) {
     if (!gaps_ok(gap_init, gap_ext)) return -1;
     MatCtx* c = get_mctx();
     if (!c) return -1;
     std::vector<DevSeq> act;
     for (int k = 0; k < npairs; ++k)
         if (alen[k] > 0 && blen[k] > 0) act.push_back(DevSeq{a_off[k], b_off[k], alen[k], blen[k], k});
-    return launch(c, mx, d_arena, act, gap_init, gap_ext, d_scores, npairs, a_on_lanes);
+    return launch(c, mx, d_arena, act, gap_init, gap_ext, d_scores, npairs, a_on_lanes, amode);
 }
 
 }  // namespace swmi
@@ -1431,7 +1631,7 @@ int sw_score_matrix(const sw_matrix* mx, const unsigned char* seq1, const unsign
 // whole pairs or (long_pairs) the checkpointed traceback
 static int align_host(const char* fn, bool long_pairs, const sw_matrix* mx, const unsigned char* const* a, const int* alen,
                       const unsigned char* const* b, const int* blen, int npairs, int gap_init, int gap_ext,
-                      sw_alignment* out, unsigned* cigar, long long cigar_cap, long long* cigar_used) {
+                      sw_alignment* out, unsigned* cigar, long long cigar_cap, long long* cigar_used, int amode = SW_MODE_LOCAL) {
     if (align_check(fn, mx, a, alen, b, blen, npairs, gap_init, gap_ext, out, cigar, cigar_cap, cigar_used)) return -1;
     AlignSink sink{out, {}};
     if (npairs == 0) return sink.finish(cigar, cigar_cap, cigar_used);
@@ -1456,11 +1656,32 @@ static int align_host(const char* fn, bool long_pairs, const sw_matrix* mx, cons
     if (ensure(c, B_ARENA, total)) return -1;
     // (synchronous: a refusal below returns before anything is launched or waited for)
     if (total) MCHK(hipMemcpy(c->buf[B_ARENA], arena.data(), total, hipMemcpyHostToDevice));
-    const auto align_device = long_pairs ? matrix_align_long_device : matrix_align_device;
-    if (align_device(mx, (const unsigned char*)c->buf[B_ARENA], a_off.data(), alen, b_off.data(), blen, nullptr, npairs,
-                     gap_init, gap_ext, "pair", sink))
+    if (long_pairs ? matrix_align_long_device(mx, (const unsigned char*)c->buf[B_ARENA], a_off.data(), alen, b_off.data(), blen,
+                                              nullptr, npairs, gap_init, gap_ext, "pair", sink)
+                   : matrix_align_device(mx, (const unsigned char*)c->buf[B_ARENA], a_off.data(), alen, b_off.data(), blen,
+                                         nullptr, npairs, gap_init, gap_ext, "pair", sink, amode))
         return -1;
     return sink.finish(cigar, cigar_cap, cigar_used);
+}
+
+int sw_score_matrix_batch_mode(const sw_matrix* mx, const unsigned char* const* a, const int* alen,
+                               const unsigned char* const* b, const int* blen, int npairs, int gap_init, int gap_ext,
+                               int mode, int* scores_out) {
+    if (!mx || npairs < 0 || (npairs > 0 && (!a || !alen || !b || !blen || !scores_out))) {
+        report_error("sw_score_matrix_batch_mode: invalid arguments");
+        return -1;
+    }
+    if (!mode_ok("sw_score_matrix_batch_mode", mode)) return -1;
+    if (npairs == 0) return 0;
+    return score_host(mx, a, alen, b, blen, npairs, gap_init, gap_ext, scores_out, mode);
+}
+
+int sw_align_matrix_batch_mode(const sw_matrix* mx, const unsigned char* const* a, const int* alen,
+                               const unsigned char* const* b, const int* blen, int npairs, int gap_init, int gap_ext,
+                               int mode, sw_alignment* out, unsigned* cigar, long long cigar_cap, long long* cigar_used) {
+    if (!mode_ok("sw_align_matrix_batch_mode", mode)) return -1;
+    return align_host("sw_align_matrix_batch_mode", false, mx, a, alen, b, blen, npairs, gap_init, gap_ext, out, cigar,
+                      cigar_cap, cigar_used, mode);
 }
 
 int sw_align_matrix_batch(const sw_matrix* mx, const unsigned char* const* a, const int* alen,

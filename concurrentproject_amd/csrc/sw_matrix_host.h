@@ -37,10 +37,12 @@ long long matrix_first_bad(const sw_matrix* m, const unsigned char* p, long long
 // d_arena[a_off[k], +alen[k]) (seq1: the table's first index) against d_arena[b_off[k], +blen[k]);
 // d_scores[k] (device) receives its score.  Synchronous.  a_on_lanes: every pair spreads seq1 across
 // the lanes (database search: the query); else the orientation is chosen per pair.  The bytes must
-// have been checked against the alphabet.  0 or -1.
+// have been checked against the alphabet.  amode: SW_MODE_*; global and semi-global always lay seq1
+// across the lanes, the caller has checked mode_range_ok, and the score of a pair with an empty
+// sequence is the caller's to fill in (mode_empty_score): the device writes 0 there.  0 or -1.
 int matrix_score_device(const sw_matrix* m, const unsigned char* d_arena, const int64_t* a_off, const int* alen,
                         const int64_t* b_off, const int* blen, int npairs, int gap_init, int gap_ext,
-                        int* d_scores, bool a_on_lanes);
+                        int* d_scores, bool a_on_lanes, int amode);
 
 // ---- alignments (sw_align_host.cpp: host only; the traced launch is in sw_matrix.hip) ----
 
@@ -67,14 +69,29 @@ struct AlignSink {
     int finish(unsigned* cigar, long long cigar_cap, long long* cigar_used);
 };
 
+// ---- global and semi-global alignment (include/algoGPU.h SW_MODE_*) ----
+// 0 <= mode <= 2, or the message names fn and the mode
+bool mode_ok(const char* fn, int mode);
+// The int32 range of the unclamped recurrence: (n + m + 1024) * max(G_INIT, G_EXT, 127) < 2^28.  Every
+// cell of the matrix then lies within +-2^28, and the cells outside it (pre-border, drain, dead
+// columns), which start at "minus infinity" = -2^30 and lose at most max(G_INIT, 127) a step over
+// fewer than m + 1024 steps of a strip, stay below every cell of the matrix and above -2^31.
+// The message names `what idx`.
+bool mode_range_ok(int alen, int blen, int gap_init, int gap_ext, const char* what, int idx);
+// a pair with an empty sequence, answered on the host: global, the other sequence of length L as one
+// gap run, -(G_INIT + (L - 1) * gx); semi-global, 0 when seq1 is empty, else seq1 as one I run
+int mode_empty_score(int alen, int blen, int gap_init, int gap_ext, int mode);
+void align_mode_empty(AlignSink& sink, int k, int alen, int blen, int gap_init, int gap_ext, int mode);
+
 // The traced launches of sw_matrix.hip over pairs resident in device memory (as matrix_score_device:
 // seq1 always across the lanes, bytes checked by the caller): sink.out[k] for every pair k, in order.
 // Pairs are packed greedily in input order into launches of at most option "trace_mb" MiB of trace
 // memory; a pair that does not fit alone is refused (-1; the message names it `what` name_idx[k], or
 // `what` k when name_idx is null).
+// amode: SW_MODE_*; global and semi-global pairs are checked with mode_range_ok here.
 int matrix_align_device(const sw_matrix* m, const unsigned char* d_arena, const int64_t* a_off, const int* alen,
                         const int64_t* b_off, const int* blen, const int* name_idx, int npairs, int gap_init,
-                        int gap_ext, const char* what, AlignSink& sink);
+                        int gap_ext, const char* what, AlignSink& sink, int amode);
 
 // ---- long pairs: checkpointed traceback, one strip at a time (include/algoGPU.h sw_align_matrix_long) ----
 // The arithmetic is host only (sw_align_host.cpp); the kernels and the rounds are in sw_matrix.hip.

@@ -21,7 +21,7 @@ import os
 
 import numpy as np
 
-from . import _LONG_CIGAR_CAP, SwError, _align_call, _check, _ptr, _u8, lib
+from . import _LONG_CIGAR_CAP, SwError, _align_call, _check, _mode, _ptr, _u8, lib
 
 
 class Database:
@@ -116,13 +116,31 @@ class Database:
             raise SwError("a matrix search needs gap_init and gap_ext")
         return int(gap_init), int(gap_ext)
 
-    def search(self, query, matrix=None, gap_init=None, gap_ext=None) -> np.ndarray:
+    @staticmethod
+    def _amode(mode, matrix, what=None):
+        """SW_MODE_* of ``mode``; a non-local mode needs a matrix and is not built for ``what``."""
+        am = _mode(mode)
+        if am != 0 and what:
+            raise ValueError("mode=%r is not built for %s: it is local only" % (mode, what))
+        if am != 0 and matrix is None:
+            raise ValueError("mode=%r needs matrix= (Matrix.equality gives the table of an equality scoring)" % (mode,))
+        return am
+
+    def search(self, query, matrix=None, gap_init=None, gap_ext=None, mode: str = "local") -> np.ndarray:
         """int32 score of ``query`` against every record, in record order.  With ``matrix`` (a
         :class:`Matrix`; the query is its first index) the scores are substitution-matrix scores
-        with the gap penalties given here; without, byte-equality scores as set_params has them."""
+        with the gap penalties given here; without, byte-equality scores as set_params has them.
+        ``mode`` (matrix searches): "local"; "semiglobal", the whole query inside the record, the
+        record's flanks free; "global", query and record end to end.  Scores of the last two may
+        be negative."""
         q = _u8(query)
         out = np.zeros(len(self), dtype=np.int32)
+        am = self._amode(mode, matrix)
         gaps = self._gaps(matrix, gap_init, gap_ext)
+        if gaps is not None and am != 0:
+            _check(lib().sw_db_search_matrix_mode(self._h, matrix._handle(), _ptr(q), len(q), gaps[0], gaps[1], am,
+                                                  out.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+            return out
         if gaps is not None:
             _check(lib().sw_db_search_matrix(self._h, matrix._handle(), _ptr(q), len(q), gaps[0], gaps[1],
                                              out.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
@@ -130,9 +148,11 @@ class Database:
         _check(lib().sw_db_search(self._h, _ptr(q), len(q), out.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
         return out
 
-    def search_db(self, queries: "Database", matrix=None, gap_init=None, gap_ext=None) -> np.ndarray:
+    def search_db(self, queries: "Database", matrix=None, gap_init=None, gap_ext=None, mode: str = "local") -> np.ndarray:
         """[len(queries), len(self)] int32 scores of every query record against every record
-        (``matrix``, ``gap_init``, ``gap_ext`` as in :meth:`search`; matrix queries run one by one)."""
+        (``matrix``, ``gap_init``, ``gap_ext`` as in :meth:`search`; matrix queries run one by one).
+        Local only: any other ``mode`` raises ValueError."""
+        self._amode(mode, matrix, "search_db")
         out = np.zeros((len(queries), len(self)), dtype=np.int32)
         gaps = self._gaps(matrix, gap_init, gap_ext)
         if gaps is not None:
@@ -142,31 +162,38 @@ class Database:
         _check(lib().sw_db_search_db(self._h, queries._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
         return out
 
-    def align(self, query, indices, matrix, gap_init: int, gap_ext: int, long: bool = False) -> list:
+    def align(self, query, indices, matrix, gap_init: int, gap_ext: int, long: bool = False, mode: str = "local") -> list:
         """An :class:`Alignment` of ``query`` (seq1) with each record of ``indices``, out of the
         database's device arena (sw_db_align_matrix): only the query is uploaded.  ``long=True``: the
         same alignments by checkpointed traceback (sw_db_align_matrix_long), for records whose whole
-        trace does not fit option ``trace_mb``."""
+        trace does not fit option ``trace_mb`` (local only).  ``mode`` as in :meth:`search`."""
+        am = self._amode(mode, matrix, "long=True (checkpointed traceback)" if long else None)
         q = _u8(query)
         idx = [int(i) for i in indices]
         n = len(idx)
         if n == 0:
             return []
         IDX = (ctypes.c_int * n)(*idx)
+        if am != 0:
+            return _align_call(lambda out, cig, cap, used: lib().sw_db_align_matrix_mode(
+                self._h, matrix._handle(), _ptr(q), len(q), IDX, n, int(gap_init), int(gap_ext), am, out, cig, cap, used), n,
+                16 * n)
         f = lib().sw_db_align_matrix_long if long else lib().sw_db_align_matrix
         return _align_call(lambda out, cig, cap, used: f(
             self._h, matrix._handle(), _ptr(q), len(q), IDX, n, int(gap_init), int(gap_ext), out, cig, cap, used), n,
             max(16 * n, _LONG_CIGAR_CAP if long else 0))
 
-    def top(self, query, k: int = 10, matrix=None, gap_init=None, gap_ext=None, alignments: bool = False) -> list:
+    def top(self, query, k: int = 10, matrix=None, gap_init=None, gap_ext=None, alignments: bool = False,
+            mode: str = "local") -> list:
         """The k best records: [(score, index, header)], score descending, index ascending on ties.
-        With ``alignments=True`` (a matrix search) each tuple ends with the hit's :class:`Alignment`."""
-        sc = self.search(query, matrix=matrix, gap_init=gap_init, gap_ext=gap_ext)
+        With ``alignments=True`` (a matrix search) each tuple ends with the hit's :class:`Alignment`.
+        ``mode`` as in :meth:`search`; the ranking is by score as ever, and scores may be negative."""
+        sc = self.search(query, matrix=matrix, gap_init=gap_init, gap_ext=gap_ext, mode=mode)
         idx = np.lexsort((np.arange(len(sc)), -sc.astype(np.int64)))[:k]
         hits = [(int(sc[i]), int(i), self.header(int(i))) for i in idx]
         if not alignments:
             return hits
         if matrix is None:
             raise SwError("alignments=True needs matrix= (Matrix.equality gives the table of an equality scoring)")
-        al = self.align(query, [h[1] for h in hits], matrix, gap_init, gap_ext)
+        al = self.align(query, [h[1] for h in hits], matrix, gap_init, gap_ext, mode=mode)
         return [h + (x,) for h, x in zip(hits, al)]

@@ -357,6 +357,79 @@ void sw_last_align_ms(float* fill_ms, float* walk_ms);
  * groups (any pointer may be NULL; zeros after a call of the other kind) */
 void sw_last_align_long_ms(float* locate_ms, float* strip_ms, float* walk_ms, int* rounds);
 
+/* ---- global and semi-global alignment under a substitution matrix ----
+ * Everything above is LOCAL alignment.  The *_mode entry points take an alignment mode:
+ *   SW_MODE_LOCAL       what every call above does, bit for bit (through either entry point)
+ *   SW_MODE_GLOBAL      seq1 and seq2 both end to end (Needleman-Wunsch with Gotoh's affine gaps)
+ *   SW_MODE_SEMIGLOBAL  seq1 (the query) end to end; seq2 (the record) free at both ends
+ *
+ * THE RECURRENCE.  i in seq1 (across the lanes, n residues), j in seq2 (the rows that stream, m
+ * residues); s = matrix[seq1[i]][seq2[j]]; E runs along seq1 (operation I), F along seq2
+ * (operation D).  A run of L gap operations costs G_INIT + (L-1) * min(G_EXT, G_INIT), which is
+ * what the local recurrence charges in the interior; the borders charge the same, so that one
+ * re-scoring rule (above) covers all modes.  gx = min(G_EXT, G_INIT).
+ *     E[i][j] = max(E[i-1][j] - G_EXT, H[i-1][j] - G_INIT)
+ *     F[i][j] = max(F[i][j-1] - G_EXT, H[i][j-1] - G_INIT)
+ *     H[i][j] = max(H[i-1][j-1] + s, E[i][j], F[i][j])           no clamp at 0
+ *   Borders:
+ *     H[-1][-1] = 0
+ *     H[i][-1]  = -(G_INIT + i * gx)      both modes: i + 1 residues of seq1 against gaps
+ *     H[-1][j]  = -(G_INIT + j * gx)      global
+ *     H[-1][j]  = 0                       semi-global
+ *     E[-1][j], F[i][-1] = minus infinity: a gap cannot be extended out of a border
+ *   SCORE AND END CELL.  Global: H[n-1][m-1].  Semi-global: the maximum over j in [0, m) of
+ *     H[n-1][j]; the end cell is the smallest such j.  (H, not the diagonal arrival t of the
+ *     local rule: an end-to-end alignment may end in a gap.)  end1 = n, end2 = j + 1.
+ *   WALK.  From the end cell in state H, backwards, with the local priorities: in H the diagonal
+ *     (H == t) first, then E, then F; in E and F opening before extending.  There is no H = 0 stop.
+ *     The walk leaves the matrix at j < 0 -- the remaining i + 1 residues of seq1 become one
+ *     leading I run -- or at i < 0: global, the remaining j + 1 residues of seq2 become one
+ *     leading D run; semi-global, the walk stops and beg2 = j + 1.
+ *   Ranges: global [0, n) x [0, m); semi-global [0, n) x [beg2, end2).  Unlike local, an
+ *   alignment may begin or end with a gap, and scores may be negative: every function here
+ *   returns 0 or -1, never a score.
+ *   EMPTY SEQUENCES are answered on the host.  Global with one side empty, the other of length
+ *   L: score -(G_INIT + (L-1) * gx), one gap run (I over seq1 or D over seq2); both empty: 0.
+ *   Semi-global: n = 0 scores 0 (no operations, all coordinates 0); m = 0 is the all-I run.
+ *   SCORE RANGE.  A pair with (n + m + 1024) * max(G_INIT, G_EXT, 127) >= 2^28 is refused before
+ *   any launch (-1, sw_last_error names the pair): below that bound every cell of the matrix lies
+ *   within +-2^28 and no cell outside it -- those now hold unclamped values that start at
+ *   "minus infinity" = -2^30 -- can wrap int32 or reach a cell of the matrix.  The local bound
+ *   (min length * largest entry < 2^28) is checked as well.
+ *
+ * sw_score_matrix_batch_mode: as sw_score_matrix_batch.  One launch is one mode; in the new modes
+ *   seq1 always lies across the lanes (the modes are not symmetric in the sequences).  Options
+ *   "W" and "blocks" are honoured.  sw_last_stats: mode 6 as before, and variant = the alignment
+ *   mode (variant is otherwise unused on score-only matrix launches; 0 = local as ever).
+ * sw_align_matrix_batch_mode: as sw_align_matrix_batch (trace memory, packing, cigar protocol).
+ *   sw_last_stats: mode 7; variant = launches as before in bits 0-27, the alignment mode in
+ *   bits 28-29.  A pair whose trace does not fit option "trace_mb" alone is refused with a
+ *   message that says so: the checkpointed traceback (sw_align_matrix_long) is local only.
+ * sw_align_matrix_cpu_mode: the plain full-matrix host aligner with the same end rule and walk.
+ * sw_db_search_matrix_mode, sw_db_align_matrix_mode: as sw_db_search_matrix / sw_db_align_matrix;
+ *   the query is seq1, so semi-global finds the whole query inside a record.
+ * An unknown mode returns -1 with a message.  Not built in the new modes: the long path and
+ * sw_db_search_db_matrix. */
+#define SW_MODE_LOCAL      0
+#define SW_MODE_GLOBAL     1
+#define SW_MODE_SEMIGLOBAL 2
+int  sw_score_matrix_batch_mode(const sw_matrix*, const unsigned char* const* a, const int* alen,
+                                const unsigned char* const* b, const int* blen, int npairs,
+                                int gap_init, int gap_ext, int mode, int* scores_out);
+int  sw_align_matrix_batch_mode(const sw_matrix*, const unsigned char* const* a, const int* alen,
+                                const unsigned char* const* b, const int* blen, int npairs,
+                                int gap_init, int gap_ext, int mode, sw_alignment* out,
+                                unsigned* cigar, long long cigar_cap, long long* cigar_used);
+int  sw_align_matrix_cpu_mode(const sw_matrix*, const unsigned char* const* a, const int* alen,
+                              const unsigned char* const* b, const int* blen, int npairs,
+                              int gap_init, int gap_ext, int mode, sw_alignment* out,
+                              unsigned* cigar, long long cigar_cap, long long* cigar_used);
+int  sw_db_search_matrix_mode(sw_db*, const sw_matrix*, const unsigned char* query, int qlen,
+                              int gap_init, int gap_ext, int mode, int* scores_out);
+int  sw_db_align_matrix_mode(sw_db*, const sw_matrix*, const unsigned char* query, int qlen,
+                             const int* record_idx, int nidx, int gap_init, int gap_ext, int mode,
+                             sw_alignment* out, unsigned* cigar, long long cigar_cap, long long* cigar_used);
+
 /* Tuning knobs (process-wide).  Keys:
  *   "W"        columns per lane: 0 = auto, 1, 2, 4, 8
  *   "C"        rows per strip hand-off chunk: 0 = auto, 16, 32, 64
@@ -463,7 +536,9 @@ typedef struct {
     int W, C, dna, blocks, waves_per_cu, items;
     long long boundary_bytes;
     int mode;
-    int variant;            /* bit 0: duo max3 via v_pk_maximum3_f16; bit 1: flow2 streams row codes;
+    int variant;            /* (mode 6: the alignment mode SW_MODE_*; mode 7: launches in bits 0-27, the alignment
+                               mode in bits 28-29; mode 8: strip-fill launches; the bits below are the engine's)
+                               bit 0: duo max3 via v_pk_maximum3_f16; bit 1: flow2 streams row codes;
                                bit 2: flow2 ring edges; bit 3: the linear-gap step;
                                bit 4: flow2 two columns per lane; bit 5: flow2 pair per workgroup;
                                bit 6: the flow3 kernel (sw_flow3.hip);

@@ -14,8 +14,12 @@ sw_db_align_matrix, the traced kernel and the walk) next to the search alone, th
 score-only kernel at the same W on those K pairs, the walk's time and the trace bytes.  --plant P replaces P records
 by mutated copies of the query, so that the top hits have real alignments (with neither, nothing changes).
 
+--mode global|semiglobal (with --matrix): the same search, alignments and timings in that alignment mode
+(Database.search(mode=...)); the lines then carry "align_mode".
+
     python tools/bench_db.py [--records R] [--qlen Q] [--lo L] [--hi H] [--steps K] [--alphabet dna|protein]
                              [--opt k=v ...] [--matrix random|FILE --gaps G_INIT,G_EXT] [--alignments K] [--plant P]
+                             [--mode local|global|semiglobal]
 """
 import argparse
 import json
@@ -44,7 +48,11 @@ def main():
     ap.add_argument("--gaps", default=None, help="G_INIT,G_EXT of a --matrix search")
     ap.add_argument("--alignments", type=int, default=0, help="also time the search plus aligning its top K (--matrix)")
     ap.add_argument("--plant", type=int, default=0, help="records replaced by mutated copies of the query")
+    ap.add_argument("--mode", default="local", choices=("local", "global", "semiglobal"),
+                    help="alignment mode of a --matrix search")
     a = ap.parse_args()
+    if a.mode != "local" and a.matrix is None:
+        ap.error("--mode needs --matrix")
     if (a.matrix is None) != (a.gaps is None):
         ap.error("--matrix and --gaps go together")
     if a.alignments and a.matrix is None:
@@ -88,6 +96,9 @@ def main():
         gi, ge = (int(x) for x in a.gaps.split(","))
         kw = {"matrix": mx, "gap_init": gi, "gap_ext": ge}
         extra = {"matrix": a.matrix, "gaps": [gi, ge]}
+        if a.mode != "local":   # (a local run prints the lines it always printed)
+            kw["mode"] = a.mode
+            extra["align_mode"] = a.mode
     db.search(q, **kw)  # upload + warm
     t0 = time.perf_counter()
     for _ in range(a.steps):
@@ -114,7 +125,7 @@ def main():
         idx = [t[1] for t in top]
         fills, walks = [], []
         for _ in range(a.steps):
-            al = db.align(q, idx, mx, gi, ge)
+            al = db.align(q, idx, mx, gi, ge, mode=a.mode)
             sta = sw.last_stats()
             f, w = sw.last_align_ms()
             fills.append(f)
@@ -123,14 +134,14 @@ def main():
         sw.set_option("W", sta["W"])                     # the score-only kernel at the traced kernel's W, same pairs
         plain = []
         for _ in range(a.steps + 1):
-            assert sw.score_matrix_batch(pairs, mx, gi, ge) == [x.score for x in al]
+            assert sw.score_matrix_batch(pairs, mx, gi, ge, mode=a.mode) == [x.score for x in al]
             plain.append(sw.last_stats()["kernel_ms"])
         sw.set_option("W", 0)
         kcells = sum(len(y) for _, y in pairs) * a.qlen
         fill, walk, score_ms = float(np.median(fills)), float(np.median(walks)), float(np.median(plain[1:]))
         print(json.dumps({**extra, "metric": "db search + alignments of the top K (host API)", "alphabet": a.alphabet, "K": K,
                           "planted": a.plant, "ms_search_top": round(dts * 1e3, 3), "ms_search_top_aligned": round(dta * 1e3, 3),
-                          "W": sta["W"], "launches": sta["variant"], "trace_bytes": sta["boundary_bytes"], "cells": kcells,
+                          "W": sta["W"], "launches": sta["variant"] & 0xFFFFFFF, "trace_bytes": sta["boundary_bytes"], "cells": kcells,
                           "fill_kernel_ms": round(fill, 4), "fill_GCUPS": round(kcells / fill / 1e6, 2),
                           "score_kernel_ms_same_W": round(score_ms, 4), "score_GCUPS_same_W": round(kcells / score_ms / 1e6, 2),
                           "walk_kernel_ms": round(walk, 4), "cigar_ops_mean": round(float(np.mean([len(x.ops) for x in al])), 1),
