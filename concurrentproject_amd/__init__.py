@@ -64,6 +64,11 @@ class _AlignPlan(ctypes.Structure):
                 ("full_trace_bytes", ctypes.c_longlong)]
 
 
+class _BandPlan(ctypes.Structure):
+    _fields_ = [("dlo", ctypes.c_longlong), ("dhi", ctypes.c_longlong), ("cells", ctypes.c_longlong),
+                ("trace_bytes", ctypes.c_longlong), ("full_trace_bytes", ctypes.c_longlong)]
+
+
 _lib = None
 
 
@@ -239,6 +244,17 @@ def lib() -> ctypes.CDLL:
         L.sw_db_align_matrix_mode.argtypes = [vp, vp, u8p, i, ctypes.POINTER(i), i, i, i, i, ctypes.POINTER(_Alignment),
                                               ctypes.POINTER(ctypes.c_uint), ll, ctypes.POINTER(ll)]
         L.sw_db_align_matrix_mode.restype = i
+    if hasattr(L, "sw_align_matrix_batch_band"):   # banded alignment (include/algoGPU.h sw_*_band)
+        L.sw_score_matrix_batch_band.argtypes = [vp, ctypes.POINTER(u8p), ctypes.POINTER(i), ctypes.POINTER(u8p),
+                                                 ctypes.POINTER(i), i, i, i, i, i, ctypes.POINTER(i)]
+        L.sw_score_matrix_batch_band.restype = i
+        for name in ("sw_align_matrix_batch_band", "sw_align_matrix_cpu_band"):
+            f = getattr(L, name)
+            f.argtypes = [vp, ctypes.POINTER(u8p), ctypes.POINTER(i), ctypes.POINTER(u8p), ctypes.POINTER(i), i, i, i, i, i,
+                          ctypes.POINTER(_Alignment), ctypes.POINTER(ctypes.c_uint), ll, ctypes.POINTER(ll)]
+            f.restype = i
+        L.sw_band_plan.argtypes = [i, i, i, ctypes.POINTER(_BandPlan)]
+        L.sw_band_plan.restype = i
     _lib = L
     return L
 
@@ -565,27 +581,44 @@ def _mode(mode) -> int:
         raise ValueError("unknown alignment mode %r: use 'local', 'global' or 'semiglobal'" % (mode,)) from None
 
 
-def score_matrix(seq1, seq2, matrix: Matrix, gap_init: int, gap_ext: int, mode: str = "local") -> int:
+def _band(band) -> int:
+    """``band`` as the library takes it: a C int (the library refuses a negative one by name)."""
+    if isinstance(band, bool) or not isinstance(band, (int, np.integer)):
+        raise ValueError("band=%r: a band is a whole number >= 0, or None" % (band,))
+    return max(-1, min(int(band), 2 ** 31 - 1))
+
+
+def score_matrix(seq1, seq2, matrix: Matrix, gap_init: int, gap_ext: int, mode: str = "local",
+                 band: int | None = None) -> int:
     """Best local-alignment score under ``matrix``; a gap of L residues costs gap_init + (L-1)*gap_ext
     (BLAST's "open 11, extend 1" is gap_init=12, gap_ext=1).  ``mode="global"`` / ``"semiglobal"``:
-    the end-to-end / query-inside-record score (include/algoGPU.h SW_MODE_*), which may be negative."""
-    if _mode(mode) != SW_MODE_LOCAL:
-        return score_matrix_batch([(seq1, seq2)], matrix, gap_init, gap_ext, mode=mode)[0]
+    the end-to-end / query-inside-record score (include/algoGPU.h SW_MODE_*), which may be negative.
+    ``band``: see :func:`score_matrix_batch`."""
+    if _mode(mode) != SW_MODE_LOCAL or band is not None:
+        return score_matrix_batch([(seq1, seq2)], matrix, gap_init, gap_ext, mode=mode, band=band)[0]
     a, b = _u8(seq1), _u8(seq2)
     return _check(lib().sw_score_matrix(matrix._handle(), _ptr(a), _ptr(b), len(a), len(b), int(gap_init), int(gap_ext)))
 
 
-def score_matrix_batch(pairs: Iterable[Sequence], matrix: Matrix, gap_init: int, gap_ext: int, mode: str = "local") -> list:
+def score_matrix_batch(pairs: Iterable[Sequence], matrix: Matrix, gap_init: int, gap_ext: int, mode: str = "local",
+                       band: int | None = None) -> list:
     """Scores of many independent pairs under ``matrix`` in one launch (sw_score_matrix_batch; with
-    ``mode`` "global" or "semiglobal" sw_score_matrix_batch_mode: one launch is one mode)."""
+    ``mode`` "global" or "semiglobal" sw_score_matrix_batch_mode: one launch is one mode).
+    ``band=B`` (sw_score_matrix_batch_band, any mode): only the cells (i, j) of a pair with
+    min(0, m - n) - B <= j - i <= max(0, m - n) + B exist (include/algoGPU.h; :func:`band_plan`)."""
     am = _mode(mode)
+    if band is not None:
+        if not isinstance(matrix, Matrix):
+            raise ValueError("band= needs a substitution matrix (Matrix.equality gives equality scoring as one)")
+        return _score_matrix_batch(pairs, matrix, gap_init, gap_ext, am, _band(band))
     if am != SW_MODE_LOCAL and not isinstance(matrix, Matrix):
         raise ValueError("mode=%r needs a substitution matrix (Matrix.equality gives equality scoring as one)" % mode)
     return _score_matrix_batch(pairs, matrix, gap_init, gap_ext, am if am != SW_MODE_LOCAL else None)
 
 
-def _score_matrix_batch(pairs, matrix, gap_init: int, gap_ext: int, am) -> list:
-    """am None: sw_score_matrix_batch; else sw_score_matrix_batch_mode with that SW_MODE_* value."""
+def _score_matrix_batch(pairs, matrix, gap_init: int, gap_ext: int, am, band=None) -> list:
+    """am None: sw_score_matrix_batch; else sw_score_matrix_batch_mode with that SW_MODE_* value, or with
+    a band sw_score_matrix_batch_band."""
     arrs = [(_u8(a), _u8(b)) for a, b in pairs]
     n = len(arrs)
     if n == 0:
@@ -596,7 +629,9 @@ def _score_matrix_batch(pairs, matrix, gap_init: int, gap_ext: int, am) -> list:
     AL = (ctypes.c_int * n)(*[len(x) for x, _ in arrs])
     BL = (ctypes.c_int * n)(*[len(y) for _, y in arrs])
     out = (ctypes.c_int * n)()
-    if am is not None:
+    if band is not None:
+        _check(lib().sw_score_matrix_batch_band(matrix._handle(), A, AL, B, BL, n, int(gap_init), int(gap_ext), am, band, out))
+    elif am is not None:
         _check(lib().sw_score_matrix_batch_mode(matrix._handle(), A, AL, B, BL, n, int(gap_init), int(gap_ext), am, out))
     else:
         _check(lib().sw_score_matrix_batch(matrix._handle(), A, AL, B, BL, n, int(gap_init), int(gap_ext), out))
@@ -687,11 +722,12 @@ def _align_call(call, n: int, cap: int) -> list:
 _LONG_CIGAR_CAP = 1 << 16
 
 
-def _align_pairs(f, pairs, matrix, gap_init: int, gap_ext: int, cap: int = 0, mode=None) -> list:
-    """f: one of the library's sw_align_matrix_* entry points over host pairs (mode: a *_mode one)."""
+def _align_pairs(f, pairs, matrix, gap_init: int, gap_ext: int, cap: int = 0, mode=None, band=None) -> list:
+    """f: one of the library's sw_align_matrix_* entry points over host pairs (mode: a *_mode one; mode
+    and band: a *_band one)."""
     if mode is not None and not isinstance(matrix, Matrix):
         raise ValueError("an alignment mode needs a substitution matrix (Matrix.equality gives equality scoring as one)")
-    extra = () if mode is None else (int(mode),)
+    extra = () if mode is None else (int(mode),) if band is None else (int(mode), int(band))
     arrs = [(_u8(a), _u8(b)) for a, b in pairs]
     n = len(arrs)
     if n == 0:
@@ -706,14 +742,22 @@ def _align_pairs(f, pairs, matrix, gap_init: int, gap_ext: int, cap: int = 0, mo
 
 
 def align_matrix_batch(pairs: Iterable[Sequence], matrix: Matrix, gap_init: int, gap_ext: int, cpu: bool = False,
-                       mode: str = "local", long: bool = False) -> list:
+                       mode: str = "local", long: bool = False, band: int | None = None) -> list:
     """An :class:`Alignment` per pair under ``matrix`` (seq1 is its first index) with affine gaps, on
     the GPU (sw_align_matrix_batch: the traced matrix kernel and a walk) or, with ``cpu=True``, from
     the library's plain full-matrix aligner on the host (sw_align_matrix_cpu), which gives the same
     result.  Which alignment is reported when several reach the score is fixed (include/algoGPU.h).
     ``mode``: "local", "global" (both sequences end to end) or "semiglobal" (seq1 end to end inside
-    seq2); ``long=True`` is :func:`align_matrix_long`, which is local only."""
+    seq2); ``long=True`` is :func:`align_matrix_long`, which is local only.
+    ``band=B`` (any mode, not with ``long=True``): the alignment within the band of
+    :func:`score_matrix_batch`, from the band kernels (sw_align_matrix_batch_band), which hold only the
+    band's trace (:func:`band_plan`), or with ``cpu=True`` from the host aligner restricted to it."""
     am = _mode(mode)
+    if band is not None:
+        if long:
+            raise ValueError("band= is not built for long=True (checkpointed traceback)")
+        f = lib().sw_align_matrix_cpu_band if cpu else lib().sw_align_matrix_batch_band
+        return _align_pairs(f, pairs, matrix, gap_init, gap_ext, mode=am, band=_band(band))
     if long:
         if am != SW_MODE_LOCAL:
             raise ValueError("mode=%r is not built for long=True (checkpointed traceback): it is local only" % mode)
@@ -746,9 +790,19 @@ def align_long_plan(n: int, m: int) -> dict:
 
 
 def align_matrix(seq1, seq2, matrix: Matrix, gap_init: int, gap_ext: int, cpu: bool = False, mode: str = "local",
-                 long: bool = False) -> Alignment:
+                 long: bool = False, band: int | None = None) -> Alignment:
     """One pair (see :func:`align_matrix_batch`)."""
-    return align_matrix_batch([(seq1, seq2)], matrix, gap_init, gap_ext, cpu=cpu, mode=mode, long=long)[0]
+    return align_matrix_batch([(seq1, seq2)], matrix, gap_init, gap_ext, cpu=cpu, mode=mode, long=long, band=band)[0]
+
+
+def band_plan(n: int, m: int, band: int) -> dict:
+    """The band of an n x m pair (sw_band_plan, no GPU call): ``dlo`` and ``dhi`` (a cell (i, j) is in the
+    band iff dlo <= j - i <= dhi), ``cells`` in the band, ``trace_bytes`` the traced band launch holds for
+    the pair and ``full_trace_bytes`` the unbanded launch would."""
+    p = _BandPlan()
+    _check(lib().sw_band_plan(int(n), int(m), _band(band), ctypes.byref(p)))
+    return {"dlo": p.dlo, "dhi": p.dhi, "cells": p.cells, "trace_bytes": p.trace_bytes,
+            "full_trace_bytes": p.full_trace_bytes}
 
 
 def last_align_ms() -> tuple:

@@ -9,6 +9,8 @@
 // sw_align_long_plan (sw_matrix.hip) only reads option "trace_mb" and calls it.
 // And the host side of global and semi-global alignment (SW_MODE_*): the mode and score-range checks,
 // the answers for empty sequences, and sw_align_matrix_cpu_mode, the same plain aligner for those modes.
+// And banded alignment (sw_*_band): the band's arithmetic (range, cells, the strips' chunks, trace bytes),
+// sw_band_plan, and sw_align_matrix_cpu_band, the plain aligner restricted to a band, every mode.
 #include "sw_matrix_host.h"
 #include "../../include/algoGPU.h"
 
@@ -223,9 +225,155 @@ void align_mode_empty(AlignSink& sink, int k, int alen, int blen, int gap_init, 
     sink.set(k, score, 0, seq1 ? L : 0, 0, seq1 ? 0 : L, ops.data(), L);
 }
 
+// ---- banded alignment: the arithmetic of a band (sw_matrix_host.h) ----
+
+bool band_ok(const char* fn, int band) {
+    if (band >= 0) return true;
+    char m[160];
+    std::snprintf(m, sizeof m, "%s: band %d is negative (a band is the distance from the corner-to-corner diagonal, >= 0)", fn,
+                  band);
+    report_error(m);
+    return false;
+}
+
+void band_range(int n, int m, int band, int* dlo, int* dhi) {
+    const int B = std::min(band, std::max(n, m));
+    *dlo = std::min(0, m - n) - B;
+    *dhi = std::max(0, m - n) + B;
+}
+
+long long band_cells(long long n, long long m, long long dlo, long long dhi) {
+    long long cells = 0;
+    for (long long i = 0; i < n; ++i) cells += std::max(0LL, std::min(m - 1, i + dhi) - std::max(0LL, i + dlo) + 1);
+    return cells;
+}
+
+long long band_first(long long i0, long long dlo) { return std::max(0LL, i0 + dlo - 1) / 64 * 64; }
+long long band_chunks(long long i0, long long SW, long long m, long long dlo, long long dhi) {
+    return (std::min(m - 1, i0 + SW - 1 + dhi) + SW - 1 - band_first(i0, dlo)) / 64 + 1;
+}
+
+long long band_steps(long long n, long long m, long long dlo, long long dhi, int W, long long* most) {
+    const long long SW = 64LL * W;
+    long long sum = 0, mx = 0;
+    for (long long i0 = 0; i0 < n; i0 += SW) {
+        const long long st = 64 * band_chunks(i0, SW, m, dlo, dhi);
+        sum += st;
+        mx = std::max(mx, st);
+    }
+    *most = mx;
+    return sum;
+}
+
+long long band_trace_steps(long long m, long long dlo, long long dhi) { return std::min(dhi - dlo, m - 1) + 15; }
+long long band_trace_bytes(long long n, long long m, long long dlo, long long dhi) {
+    return align_strips(n) * 64 * band_trace_steps(m, dlo, dhi) * 4;
+}
+
 namespace {
 
 constexpr int CPU_NEG = -(1 << 30);   // "minus infinity": mode_range_ok keeps every cell far above it
+
+// One pair in a band, both lengths > 0, any mode: align_pair / align_pair_mode over the cells with
+// dlo <= j - i <= dhi.  A neighbour outside the band is absent: in local mode the border state
+// H = E = F = 0; else it offers minus infinity to E and to F, open and extend alike (what the kernel's
+// forced cell offers, so that every recorded bit is the kernel's).  The borders are not masked.  The
+// diagonal neighbour lies on the cell's own diagonal: in the band, or a border.
+void align_pair_band(const sw_matrix* mx, const unsigned char* a, int n, const unsigned char* b, int m, int go, int ge,
+                     int mode, int dlo, int dhi, std::vector<unsigned char>& cell, std::vector<int>& hup, std::vector<int>& fup,
+                     std::vector<unsigned char>& ops, int k, AlignSink& sink) {
+    const bool local = mode == SW_MODE_LOCAL;
+    const int gx = std::min(go, ge);
+    cell.assign((size_t)n * (size_t)m, 0);
+    hup.resize((size_t)n);
+    fup.assign((size_t)n, local ? 0 : CPU_NEG);
+    for (int i = 0; i < n; ++i) hup[(size_t)i] = local ? 0 : -(go + i * gx);   // H[i][-1]
+    int best = local ? 0 : CPU_NEG, bi = local ? 0 : n - 1, bj = 0;
+    for (int j = 0; j < m; ++j) {
+        const int cb = mx->code[b[j]];
+        const int ilo = (int)std::max<long long>(0, (long long)j - dhi), ihi = (int)std::min<long long>(n - 1, (long long)j - dlo);
+        if (ilo > ihi) continue;   // (never: the band holds a cell of every row)
+        // the cell left of ilo: the border H[-1][j] (E[-1][j] is minus infinity), or absent
+        const bool left_absent = ilo > 0;
+        int hleft = local || mode == SW_MODE_SEMIGLOBAL ? 0 : -(go + j * gx);
+        int eleft = local ? 0 : CPU_NEG;
+        int hdiag = ilo > 0 ? hup[(size_t)ilo - 1] : (local || mode == SW_MODE_SEMIGLOBAL || j == 0 ? 0 : -(go + (j - 1) * gx));
+        unsigned char* row = cell.data() + (size_t)j * (size_t)n;
+        for (int i = ilo; i <= ihi; ++i) {
+            const bool la = left_absent && i == ilo;
+            const bool ua = j > 0 && (long long)j - 1 - i < dlo;   // the cell above: absent (row -1 is a border)
+            int eo = hleft - go, ee = eleft - ge;
+            int fo = hup[(size_t)i] - go, fe = fup[(size_t)i] - ge;
+            if (la) {
+                eo = local ? -go : CPU_NEG;
+                ee = local ? -ge : CPU_NEG;
+            }
+            if (ua) {
+                fo = local ? -go : CPU_NEG;
+                fe = local ? -ge : CPU_NEG;
+            }
+            int E = std::max(eo, ee), F = std::max(fo, fe);
+            if (local) E = std::max(E, 0), F = std::max(F, 0);
+            const int t = hdiag + mx->sc[mx->code[a[i]] * mx->k + cb];
+            const int H = std::max(t, std::max(E, F));
+            row[i] = (unsigned char)((local && H == 0 ? 0 : t == H ? 1 : E == H ? 2 : 3) | (ee > eo ? 4 : 0) | (fe > fo ? 8 : 0));
+            if (local && (t > best || (t == best && t > 0 && (i + j < bi + bj || (i + j == bi + bj && j < bj))))) {
+                best = t;
+                bi = i;
+                bj = j;
+            }
+            hdiag = hup[(size_t)i];
+            hup[(size_t)i] = H;
+            fup[(size_t)i] = F;
+            hleft = H;
+            eleft = E;
+        }
+        if (!local && ihi == n - 1) {   // the end: (n-1, m-1) (global); the largest H[n-1][j] in the band, the smallest such j
+            const int h = hup[(size_t)n - 1];
+            if (mode == SW_MODE_GLOBAL ? j == m - 1 : h > best) {
+                best = h;
+                bj = j;
+            }
+        }
+    }
+    if (local && best <= 0) {
+        sink.set_empty(k);
+        return;
+    }
+    ops.resize((size_t)n + (size_t)m);
+    long long nops = 0;
+    int i = bi, j = bj, state = 0;   // 0 H, 1 E, 2 F
+    while (i >= 0 && j >= 0 && nops < (long long)n + m) {
+        const int c = cell[(size_t)j * (size_t)n + (size_t)i];
+        if (state == 0) {
+            const int src = c & 3;
+            if (src == 0) break;   // local: H = 0 (also a cell outside the band, which the walk never enters)
+            if (src == 1) {
+                ops[(size_t)nops++] = 0;
+                --i;
+                --j;
+            } else {
+                state = src == 2 ? 1 : 2;
+            }
+        } else if (state == 1) {
+            ops[(size_t)nops++] = 1;
+            state = (c & 4) ? 1 : 0;
+            --i;
+        } else {
+            ops[(size_t)nops++] = 2;
+            state = (c & 8) ? 2 : 0;
+            --j;
+        }
+    }
+    if (!local) {   // the border exits of align_pair_mode
+        if (j < 0) {
+            for (; i >= 0 && nops < (long long)n + m; --i) ops[(size_t)nops++] = 1;
+        } else if (i < 0 && mode == SW_MODE_GLOBAL) {
+            for (; j >= 0 && nops < (long long)n + m; --j) ops[(size_t)nops++] = 2;
+        }
+    }
+    sink.set(k, best, i + 1, bi + 1, j + 1, bj + 1, ops.data(), nops);
+}
 
 // Global and semi-global (include/algoGPU.h): one pair, both lengths > 0, three full rows of state
 // and a byte a cell as align_pair below, the unclamped recurrence with its borders, the end rule and
@@ -427,6 +575,59 @@ int sw_align_matrix_cpu_mode(const sw_matrix* mx, const unsigned char* const* a,
         else align_pair_mode(mx, a[k], alen[k], b[k], blen[k], gap_init, gap_ext, mode, cell, hup, fup, ops, k, sink);
     }
     return sink.finish(cigar, cigar_cap, cigar_used);
+}
+
+int sw_align_matrix_cpu_band(const sw_matrix* mx, const unsigned char* const* a, const int* alen,
+                             const unsigned char* const* b, const int* blen, int npairs, int gap_init, int gap_ext, int mode,
+                             int band, sw_alignment* out, unsigned* cigar, long long cigar_cap, long long* cigar_used) {
+    if (!mode_ok("sw_align_matrix_cpu_band", mode) || !band_ok("sw_align_matrix_cpu_band", band)) return -1;
+    if (align_check("sw_align_matrix_cpu_band", mx, a, alen, b, blen, npairs, gap_init, gap_ext, out, cigar, cigar_cap,
+                    cigar_used))
+        return -1;
+    for (int k = 0; k < npairs; ++k) {
+        if (mode != SW_MODE_LOCAL && !mode_range_ok(alen[k], blen[k], gap_init, gap_ext, "pair", k)) return -1;
+        if ((long long)alen[k] * blen[k] > CPU_MAX_CELLS) {
+            char m[160];
+            std::snprintf(m, sizeof m, "pair %d: %lld cells are more than the CPU aligner's full matrix holds (2^32)", k,
+                          (long long)alen[k] * blen[k]);
+            report_error(m);
+            return -1;
+        }
+    }
+    AlignSink sink{out, {}};
+    std::vector<unsigned char> cell, ops;
+    std::vector<int> hup, fup;
+    for (int k = 0; k < npairs; ++k) {
+        if (alen[k] == 0 || blen[k] == 0) {
+            if (mode != SW_MODE_LOCAL) align_mode_empty(sink, k, alen[k], blen[k], gap_init, gap_ext, mode);
+            else sink.set_empty(k);
+            continue;
+        }
+        int dlo, dhi;
+        band_range(alen[k], blen[k], band, &dlo, &dhi);
+        align_pair_band(mx, a[k], alen[k], b[k], blen[k], gap_init, gap_ext, mode, dlo, dhi, cell, hup, fup, ops, k, sink);
+    }
+    return sink.finish(cigar, cigar_cap, cigar_used);
+}
+
+int sw_band_plan(int n, int m, int band, sw_band_plan_t* out) {
+    if (n < 0 || m < 0 || n > ALIGN_MAX_SEQ || m > ALIGN_MAX_SEQ || !out) {
+        report_error("sw_band_plan: invalid arguments");
+        return -1;
+    }
+    if (!band_ok("sw_band_plan", band)) return -1;
+    sw_band_plan_t p{0, 0, 0, 0, 0};
+    p.dlo = std::min<long long>(0, (long long)m - n) - band;
+    p.dhi = std::max<long long>(0, (long long)m - n) + band;
+    if (n > 0 && m > 0) {
+        int dlo, dhi;
+        band_range(n, m, band, &dlo, &dhi);
+        p.cells = band_cells(n, m, dlo, dhi);
+        p.trace_bytes = band_trace_bytes(n, m, dlo, dhi);
+        p.full_trace_bytes = align_strips(n) * align_strip_trace_bytes(m);
+    }
+    *out = p;
+    return 0;
 }
 
 }  // extern "C"

@@ -43,6 +43,12 @@
 // (include/algoGPU.h SW_MODE_*) are a third template parameter of the same
 // step, pair loop and kernel (AM, below): no clamp, borders made by the set-up and the inflow, the
 // end read from one column.  The local instantiations are the code they were; the long path is local only.
+//
+// BANDED ALIGNMENT (include/algoGPU.h sw_*_band) is a fourth template parameter
+// (BAND, below) of the step and the pair loop, launched through sw_matrix_band_kernel: a strip runs
+// only the chunks that hold cells of the band, a cell outside it is forced to the absent state, the
+// inflow is absent outside the rows the strip on the left stored, and the trace holds the band only.
+// Every instantiation above is the code it was.
 #include "sw_device.h"
 #include "sw_matrix_host.h"
 #include "../../include/algoGPU.h"
@@ -69,6 +75,8 @@ constexpr int MAT_C = 64;                            // rows per inflow / outflo
 constexpr int MODE_MATRIX = 6;
 constexpr int MODE_MATRIX_TRACE = 7;                 // the traced launches (alignments)
 constexpr int MODE_MATRIX_LONG = 8;                  // checkpointed traceback of long pairs (sw_align_matrix_long)
+constexpr int MODE_MATRIX_BAND = 9;                  // the band launches, score-only (sw_score_matrix_batch_band)
+constexpr int MODE_MATRIX_BAND_TRACE = 10;           // and traced (sw_align_matrix_batch_band)
 constexpr int TRACE_W = 8;                           // the traced variant's columns per lane: a step is a dword a lane
 
 struct MatPair {
@@ -97,6 +105,16 @@ struct TraceRes {
 };
 constexpr int WALK_OVERRUN = 1;   // more than n + m operations
 constexpr int WALK_RANGE = 2;     // a cell outside the pair or its trace buffer
+
+// Band launches (BANDED ALIGNMENT below): the pair's diagonal range, dlo <= j - i <= dhi.  A band
+// launch never swaps the sequences, and its MatPair::swapped carries the pair's band B instead
+// (clamped to max(n, m): band_range, sw_align_host.cpp); the kernels derive the range from it.
+struct BandPair {
+    int dlo, dhi;
+};
+__host__ __device__ inline BandPair band_of(int n, int m, int B) {
+    return BandPair{(m < n ? m - n : 0) - B, (m > n ? m - n : 0) + B};
+}
 
 struct MatArgs {
     const unsigned char* seq;
@@ -145,15 +163,32 @@ constexpr int M_SCORE = 0, M_TRACE = 1, M_LOCATE = 2;
 constexpr int AM_LOCAL = SW_MODE_LOCAL, AM_GLOBAL = SW_MODE_GLOBAL, AM_SEMI = SW_MODE_SEMIGLOBAL;
 constexpr int MAT_NEG = -(1 << 30);
 
-template <int W, int MODE, int AM = AM_LOCAL>
+// BAND: the banded step (BANDED ALIGNMENT below), one more compile-time parameter: a cell outside
+// the band is forced to the "absent" state every step -- the border state H = E = F = 0 (local),
+// MAT_NEG for all three (global, semi-global) -- and never updates M.
+//   * the mask: bu is the lane's diagonal counter, (j - i) - dlo of its column p = 0 at this step,
+//     advanced once a step; column p is 2p diagonals behind, so the cell is in the band iff
+//     (unsigned)(bu - 2p) <= dhi - dlo;
+//   * row -1 (global, semi-global): H[i][-1] is a border, not a cell, and must reach every column
+//     whose cell (i, 0) is in the band: i <= -dlo.  The raw test keeps the E chain of row -1 up to
+//     i = -dlo - 1 only.  The one missing cell (-dlo, -1) is met by one lane at one step: bz counts
+//     up to 0 there (and never reaches 0 anywhere else), and at that step that lane tests
+//     (unsigned)(bu + 1 - 2p) <= dhi - dlo + 1 instead: the lower bound one diagonal lower, the upper
+//     bound where it was.  The lane's other cells of that step are either in rows >= 0 on diagonals
+//     >= dlo + 1 (columns before it: unaffected) or in rows <= -2 (columns after it: never read by a
+//     cell of the matrix).
+template <int W, int MODE, int AM = AM_LOCAL, bool BAND = false>
 struct MStrip {
     static_assert(MODE == M_SCORE || W == TRACE_W, "a traced step stores one dword a lane");
     static_assert(AM == AM_LOCAL || MODE != M_LOCATE, "the long path is local only");
+    static_assert(!BAND || MODE != M_LOCATE, "the long path has no band");
     int cb[W], tb[W];                       // LDS offset of the column's table row / bias
     int hgA[W], hgB[W], eh[W], r[W], fh[W]; // DP state, as Strip (sw_kernels.hip)
     int L0, M, IOH, IOE, IOR;
     int Mkp, kp8;                           // M_TRACE, M_LOCATE: step * 8 + p at which M was reached; this step * 8
     int pstar, jrow, wl, Mj;                // AM != AM_LOCAL: the end bookkeeping (above); M is H - G_INIT there
+    int bu, bz;                             // BAND: the diagonal counter and the row -1 exception (above)
+    int bt, bts;                            // BAND, M_TRACE: the lane's trace step (band_trace_origin) and their number
 
     __device__ __forceinline__ void setup(const MatArgs& a, const MatPair& pd, int strip, int lane,
                                           const unsigned char* s_code) {
@@ -196,13 +231,31 @@ struct MStrip {
         }
     }
 
+    // BAND, after setup(): the strip starts at step kf (a multiple of 64), not at 0.
+    __device__ __forceinline__ void band_setup(int strip, int lane, int kf, int dlo) {
+        constexpr int SW = 64 * W;
+        const int i0 = strip * SW;
+        bu = kf - i0 - 2 * lane * W - dlo;
+        bz = 1;
+        if constexpr (AM != AM_LOCAL) {
+            const int cs = -dlo - i0;   // column -dlo in this strip: its row -1 cell is the exception (kf is 0 then)
+            bz = cs >= 1 && cs < SW && cs / W == lane ? 1 - cs : 1;
+            if (i0 + dlo > 0) {   // no column of the strip has its row 0 in the band: no border to build
+                hgB[0] = MAT_NEG;
+                eh[0] = MAT_NEG;
+                L0 = MAT_NEG;
+            }
+            jrow = jrow == MAT_NEG ? MAT_NEG : jrow + kf;
+        }
+    }
+
     // One anti-diagonal step (Strip::step with the score from the LDS table).
     // M_TRACE: the step's cells go to trc at byte toff (the lane's dword of this step).  M_TRACE and
     // M_LOCATE: M is updated strictly, so that a lane keeps the first step (anti-diagonal) that
     // reached its maximum and, within a step, the largest p: the smallest row.
     __device__ __forceinline__ void step(int (&hgCur)[W], const int (&hgPrev)[W], const bool l63, const int go,
                                          const int ge, const signed char* s_tab, const __amdgpu_buffer_rsrc_t trc,
-                                         unsigned& toff) {
+                                         unsigned& toff, const int bw = 0) {
         const int ioh = dpp_rol1(IOH), ioe = dpp_rol1(IOE), ior = dpp_rol1(IOR);
         const int hgL0 = dpp_shr1(IOH, hgPrev[W - 1]);
         const int ehL0 = dpp_shr1(IOE, eh[W - 1]);
@@ -212,6 +265,18 @@ struct MStrip {
 #pragma unroll
         for (int p = 0; p < W; ++p) sv[p] = (int)s_tab[cb[p] + (p > 0 ? r[p - 1] : rL0)];   // ds_read_i8
         unsigned bits = 0;
+        int bue = 0, bwe = 0;   // BAND: this step's test (the exception moves both by one)
+        if constexpr (BAND) {
+            bue = bu;
+            bwe = bw;
+            if constexpr (AM != AM_LOCAL) {
+                const int e = bz == 0 ? 1 : 0;
+                bue += e;
+                bwe += e;
+                bz += 1;
+            }
+            bu += 1;
+        }
 #pragma unroll
         for (int p = W - 1; p >= 0; --p) {
             const int q = p > 0 ? p - 1 : 0;
@@ -223,13 +288,15 @@ struct MStrip {
             const int E = AM == AM_LOCAL ? max3i(ehL, hgL, 0) : max(ehL, hgL);               // clamped E (local)
             const int F = AM == AM_LOCAL ? max3i(fh[p], hgPrev[p], 0) : max(fh[p], hgPrev[p]);   // clamped F (local)
             const int H = vmax3(t, E, F);
+            bool inb = true;
+            if constexpr (BAND) inb = (unsigned)(bue - 2 * p) <= (unsigned)bwe;
             if constexpr (AM != AM_LOCAL) {
                 if constexpr (MODE == M_TRACE) {   // source 0 is unused: there is no H = 0 stop
                     const unsigned src = t == H ? 1u : (E == H ? 2u : 3u);
                     bits |= (src | (ehL > hgL ? 4u : 0u) | (fh[p] > hgPrev[p] ? 8u : 0u)) << (4 * p);
                 }
             } else if constexpr (MODE != M_SCORE) {
-                const bool up = t > M;
+                const bool up = BAND ? inb && t > M : t > M;
                 M = up ? t : M;
                 Mkp = up ? kp8 + p : Mkp;
                 if constexpr (MODE == M_TRACE) {
@@ -237,18 +304,29 @@ struct MStrip {
                     bits |= (src | (ehL > hgL ? 4u : 0u) | (fh[p] > hgPrev[p] ? 8u : 0u)) << (4 * p);
                 }
             } else {
-                M = max(M, t);
+                if constexpr (BAND) M = inb ? max(M, t) : M;
+                else M = max(M, t);
             }
-            hgCur[p] = H - go;
-            eh[p] = E - ge;
-            fh[p] = F - ge;
+            if constexpr (BAND) {   // absent: the border state (local: H - go, E - ge of 0), minus infinity (else)
+                hgCur[p] = inb ? H - go : (AM == AM_LOCAL ? -go : MAT_NEG);
+                eh[p] = inb ? E - ge : (AM == AM_LOCAL ? -ge : MAT_NEG);
+                fh[p] = inb ? F - ge : (AM == AM_LOCAL ? -ge : MAT_NEG);
+            } else {
+                hgCur[p] = H - go;
+                eh[p] = E - ge;
+                fh[p] = F - ge;
+            }
             r[p] = rL;
         }
         L0 = hgL0;
         IOH = l63 ? hgCur[W - 1] : ioh;   // lane 63 <- this step's right-edge output
         IOE = l63 ? eh[W - 1] : ioe;
         IOR = ior;
-        if constexpr (MODE == M_TRACE) {
+        if constexpr (MODE == M_TRACE && BAND) {   // the lane's own run of dwords; a step outside it is dropped
+            __builtin_amdgcn_raw_buffer_store_b32(bits, trc, (unsigned)bt < (unsigned)bts ? toff : OOR, 0, 0);
+            toff += 4u;
+            bt += 1;
+        } else if constexpr (MODE == M_TRACE) {
             __builtin_amdgcn_raw_buffer_store_b32(bits, trc, toff, 0, 0);
             toff += 256u;
         }
@@ -270,11 +348,11 @@ struct MStrip {
     }
 
     __device__ __forceinline__ void run(const bool l63, const int go, const int ge, const signed char* s_tab,
-                                        const __amdgpu_buffer_rsrc_t trc, unsigned& toff) {
+                                        const __amdgpu_buffer_rsrc_t trc, unsigned& toff, const int bw = 0) {
 #pragma unroll 2
         for (int s = 0; s < MAT_C; s += 2) {
-            step(hgA, hgB, l63, go, ge, s_tab, trc, toff);
-            step(hgB, hgA, l63, go, ge, s_tab, trc, toff);
+            step(hgA, hgB, l63, go, ge, s_tab, trc, toff, bw);
+            step(hgB, hgA, l63, go, ge, s_tab, trc, toff, bw);
         }
     }
 };
@@ -287,6 +365,33 @@ __device__ __forceinline__ u32x2 mat_fetch_edge(const __amdgpu_buffer_rsrc_t scr
     const int row = k0 + lane;
     return __builtin_amdgcn_raw_buffer_load_b64(scr_rsrc, row < m ? (unsigned)row * 8u : OOR, 0, AUX_SC1);
 }
+// BAND: only the rows [olo, ohi] that the strip on the left stored (band_rows below)
+__device__ __forceinline__ u32x2 mat_fetch_edge_band(const __amdgpu_buffer_rsrc_t scr_rsrc, int k0, int lane, int olo, int ohi) {
+    const int row = k0 + lane;
+    return __builtin_amdgcn_raw_buffer_load_b64(scr_rsrc, row >= olo && row <= ohi ? (unsigned)row * 8u : OOR, 0, AUX_SC1);
+}
+
+// BANDED ALIGNMENT (include/algoGPU.h sw_*_band).  Only the cells with
+// dlo <= j - i <= dhi exist.  A strip of columns [i0, i0 + SW) meets cells of the band at the steps
+// k = j + c in [max(0, i0 + dlo), min(m - 1, i0 + SW - 1 + dhi) + SW - 1] and runs the chunks of 64
+// that hold them, from one step earlier: the first cell of column i0, (i0, i0 + dlo), takes its diagonal
+// input H[i0 - 1][i0 + dlo - 1] from the inflow of the step before.  kf is the first step, nch the chunks.  (The corner (n - 1, m - 1) is in the band and
+// i0 <= n - 1, so i0 + dlo <= m - 1: every strip has rows.)  Rows below kf never enter the strip: every
+// cell that would need them lies below diagonal dlo.  The same two functions on the host: band_first,
+// band_chunks (sw_align_host.cpp).
+__device__ __forceinline__ int band_kf(int i0, int dlo) { return max(0, i0 + dlo - 1) & ~63; }
+// THE BAND'S TRACE.  A dense [step][lane] strip would hold width + 2 * 512 steps: the skew of the
+// wavefront, not the band.  Instead every lane keeps its own run of dwords: lane l's eight columns
+// i0 + 8l + p meet cells of the band at the steps from max(0, i0 + 8l + dlo) + 8l (column p = 0 enters
+// the band; the others enter later) to min(m - 1, i0 + 8l + 7 + dhi) + 8l + 7: at most
+// min(dhi - dlo, m - 1) + 15 steps, the pair's wp.steps.  The trace is [strip][lane][step - origin]
+// dwords, n / 8 * steps * 4 bytes: n * width / 2, and a lane fills a cache line in 16 steps of its own.
+__device__ __forceinline__ int band_trace_origin(int i0, int lane, int dlo) {
+    return max(0, i0 + TRACE_W * lane + dlo) + TRACE_W * lane;
+}
+__device__ __forceinline__ int band_nch(int i0, int SW, int m, int dlo, int dhi) {
+    return (min(m - 1, i0 + SW - 1 + dhi) + SW - 1 - band_kf(i0, dlo)) / 64 + 1;
+}
 
 // All strips of one pair on this wave; scr: the wave's scratch (at least m entries when the pair has
 // more than one strip).  TRACE: wp is the pair's trace buffer; the result is the maximum with its end
@@ -295,10 +400,17 @@ __device__ __forceinline__ u32x2 mat_fetch_edge(const __amdgpu_buffer_rsrc_t scr
 // M_LOCATE: the same result without a trace; strip s reads its inflow from checkpoint column s - 1
 // of the pair and stores its right edge to column s (ckpt: column 0, ckpt_stride bytes a column,
 // m * 8 of them used), every column a buffer of its own, and the scratch is not touched.
-template <int W, int MODE, int AM = AM_LOCAL>
+// BAND: bp is the pair's diagonal range.  Strip s runs the steps [kf, kf + 64 * nch) of its own, the
+// trace is [strip][lane][step - band_trace_origin] with wp.steps dwords a lane (below), and
+// the inflow is what the strip on the left stored -- its rows [olo, ohi] -- and "absent" outside them:
+// the scratch column there holds rows of the strip before last or of an earlier pair.  The column is
+// still used in place: a chunk at k0 stores rows <= k0 + 64 - SW <= k0, a row r is read by the chunk
+// that holds it, k0' <= r, and that read is complete before chunk k0' runs, so before any store of
+// chunk k0 >= k0'; which rows a strip skips changes nothing in that.
+template <int W, int MODE, int AM = AM_LOCAL, bool BAND = false>
 __device__ void matrix_pair(const MatArgs& a, const MatPair& pd, const WalkPair& wp, const int lane, uint2* scr,
                             const signed char* s_tab, const unsigned char* s_code, unsigned char* ckpt = nullptr,
-                            unsigned ckpt_stride = 0) {
+                            unsigned ckpt_stride = 0, const BandPair bp = BandPair{0, 0}) {
     constexpr bool TRACE = MODE != M_SCORE;   // the end cell is kept
     constexpr int SW = 64 * W, C = MAT_C;
     const int m = pd.m;
@@ -318,7 +430,7 @@ __device__ void matrix_pair(const MatArgs& a, const MatPair& pd, const WalkPair&
                         : scr_rsrc;
     unsigned toff = (unsigned)lane * 4u;
     int bM = 0, bD = 0, bJ = 0;   // TRACE: the best of the strips so far: t, i + j, j
-    MStrip<W, MODE, AM> S;
+    MStrip<W, MODE, AM, BAND> S;
     S.M = AM == AM_LOCAL ? 0 : MAT_NEG;
     if constexpr (AM != AM_LOCAL) S.Mj = 0;
     for (int strip = 0; strip < strips; ++strip) {
@@ -330,6 +442,56 @@ __device__ void matrix_pair(const MatArgs& a, const MatPair& pd, const WalkPair&
         }
         const bool has_in = strip > 0;
         const bool has_out = strip < strips - 1;
+        if constexpr (BAND) {
+            const int i0 = strip * SW, kf = band_kf(i0, bp.dlo), nch = band_nch(i0, SW, m, bp.dlo, bp.dhi);
+            const int bw = bp.dhi - bp.dlo;
+            S.band_setup(strip, lane, kf, bp.dlo);
+            // the rows the strip on the left stored: its lane l of chunk k0 stores row k0 + l - (SW - 1)
+            const int kfl = band_kf(i0 - SW, bp.dlo);
+            const int olo = max(0, kfl - (SW - 1)), ohi = min(m - 1, kfl + 64 * band_nch(i0 - SW, SW, m, bp.dlo, bp.dhi) - SW);
+            if constexpr (MODE == M_TRACE) {
+                S.bt = kf - band_trace_origin(i0, lane, bp.dlo);
+                S.bts = wp.steps;
+                toff = (((unsigned)strip * 64u + (unsigned)lane) * (unsigned)wp.steps + (unsigned)S.bt) * 4u;
+            }
+            unsigned raw_nxt = mat_fetch_raw(row_rsrc, kf, lane, m);
+            u32x2 g_nxt = has_in ? mat_fetch_edge_band(scr_rsrc, kf, lane, olo, ohi) : u32x2{0u, 0u};
+            for (int c = 0; c < nch; ++c) {
+                const int k0 = kf + c * C;
+                const unsigned raw = raw_nxt;
+                const u32x2 g = g_nxt;
+                raw_nxt = mat_fetch_raw(row_rsrc, k0 + C, lane, m);
+                if (has_in) g_nxt = mat_fetch_edge_band(scr_rsrc, k0 + C, lane, olo, ohi);
+                const int row = k0 + lane;
+                const bool inr = row >= olo && row <= ohi;
+                S.IOR = row < m ? (int)s_code[raw & 0xFFu] : a.k;
+                if constexpr (AM == AM_LOCAL) {
+                    S.IOH = has_in && inr ? (int)g.x : -go;
+                    S.IOE = has_in && inr ? (int)g.y : -ge;
+                } else {   // strip 0: the left border, which is not masked; else absent outside the stored rows
+                    const int lb = AM == AM_GLOBAL ? -(go + row * min(go, ge)) - go : -go;
+                    S.IOH = has_in ? (inr ? (int)g.x : MAT_NEG) : lb;
+                    S.IOE = has_in && inr ? (int)g.y : MAT_NEG;
+                }
+                S.run(l63, go, ge, s_tab, trc, toff, bw);
+                if (has_out) {
+                    const int row_out = k0 + lane - (SW - 1);
+                    const bool st = row_out >= 0 && row_out < m;
+                    __builtin_amdgcn_raw_buffer_store_b64(u32x2{(unsigned)S.IOH, (unsigned)S.IOE}, scr_rsrc,
+                                                          st ? (unsigned)row_out * 8u : OOR, 0, AUX_SC1);
+                }
+            }
+            if (has_out) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
+            if constexpr (TRACE && AM == AM_LOCAL) {
+                const int k = kf + (S.Mkp >> 3), cl = lane * W + (S.Mkp & 7);
+                const int j = k - cl, d = strip * SW + k;
+                const bool better = S.M > bM || (S.M == bM && (d < bD || (d == bD && j < bJ)));
+                bM = better ? S.M : bM;
+                bD = better ? d : bD;
+                bJ = better ? j : bJ;
+            }
+            continue;
+        }
         __amdgpu_buffer_rsrc_t in_rsrc = scr_rsrc, out_rsrc = scr_rsrc;
         if constexpr (MODE == M_LOCATE) {   // a column that is not there (strip 0's left, the last strip's right) has no bytes
             in_rsrc = __builtin_amdgcn_make_buffer_rsrc(ckpt + (uint64_t)(has_in ? strip - 1 : 0) * ckpt_stride, 0,
@@ -460,6 +622,45 @@ __global__ void __launch_bounds__(256) sw_matrix_kernel(MatArgs a) {
     }
 }
 
+// The band launches: sw_matrix_kernel's claim loop with the pair's diagonal range beside it.  seq1 is
+// always across the lanes (j - i has one meaning), in local mode too.
+template <int W, bool TRACE, int AM>
+__global__ void __launch_bounds__(256) sw_matrix_band_kernel(MatArgs a) {
+    __shared__ unsigned s_tabw[2 * MAT_TAB_BYTES / 4];
+    __shared__ unsigned s_codew[64];
+    for (int i = threadIdx.x; i < 2 * MAT_TAB_BYTES / 4; i += 256) s_tabw[i] = a.tab[i];
+    if (threadIdx.x < 64) s_codew[threadIdx.x] = a.code[threadIdx.x];
+    __syncthreads();
+    const signed char* s_tab = reinterpret_cast<const signed char*>(s_tabw);
+    const unsigned char* s_code = reinterpret_cast<const unsigned char*>(s_codew);
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
+    uint2* scr = a.scratch + (uint64_t)wave * (uint64_t)a.scratch_rows;
+    for (;;) {
+        unsigned item = 0;
+        if (lane == 0) item = atomicAdd(&a.ctrl->next_item, 1u);
+        item = __builtin_amdgcn_readfirstlane(item);
+        if ((int)item >= a.npairs) return;
+        const MatPair raw = a.pairs[item];
+        MatPair pd;   // every field provably wave-uniform (buffer descriptors live in SGPRs)
+        pd.col_off = uniform64(raw.col_off);
+        pd.row_off = uniform64(raw.row_off);
+        pd.n = __builtin_amdgcn_readfirstlane(raw.n);
+        pd.m = __builtin_amdgcn_readfirstlane(raw.m);
+        pd.out_idx = __builtin_amdgcn_readfirstlane(raw.out_idx);
+        pd.swapped = 0;
+        const BandPair bp = band_of(pd.n, pd.m, __builtin_amdgcn_readfirstlane(raw.swapped));
+        WalkPair wp{};
+        if constexpr (TRACE) {
+            const WalkPair wraw = a.walk[item];
+            wp.trace_off = uniform64(wraw.trace_off);
+            wp.trace_bytes = __builtin_amdgcn_readfirstlane(wraw.trace_bytes);
+            wp.steps = __builtin_amdgcn_readfirstlane(wraw.steps);
+        }
+        matrix_pair<W, TRACE ? M_TRACE : M_SCORE, AM, true>(a, pd, wp, lane, scr, s_tab, s_code, nullptr, 0, bp);
+    }
+}
+
 // The walk: one lane a pair, from the end cell in state H along the recorded decisions, the
 // operations (0 M, 1 I, 2 D) written last first.  Priorities (include/algoGPU.h): a cell with
 // H = 0 ends the walk before anything else; in H the diagonal, then E, then F; in E and F opening
@@ -587,6 +788,81 @@ __global__ void __launch_bounds__(64) sw_matrix_walk_kernel(WalkArgs w) {
                 state = (nib & 8u) ? 2 : 0;
                 --j;
             }
+        }
+    }
+    r->bi = i + 1;
+    r->bj = j + 1;
+    r->nops = nops;
+    r->err = err;
+}
+
+// The walk of a band launch, all three modes: the loops above with the band's trace layout
+// (band_trace_origin) and one more check: a cell outside the
+// band is WALK_RANGE, like a cell outside the pair or the buffer.  (The fill never sends the walk
+// there: an absent neighbour offers minus infinity, or in local mode 0, which is the H = 0 stop.)
+__global__ void __launch_bounds__(64) sw_matrix_walk_band_kernel(WalkArgs w) {
+    const int item = (int)(blockIdx.x * 64 + threadIdx.x);
+    if (item >= w.npairs) return;
+    const MatPair pd = w.pairs[item];
+    const WalkPair wp = w.walk[item];
+    const BandPair bp = band_of(pd.n, pd.m, pd.swapped);
+    TraceRes* r = w.res + pd.out_idx;
+    const bool local = w.amode == SW_MODE_LOCAL;
+    int i = r->ei, j = r->ej, state = 0, err = 0, nops = 0;
+    const long long limit = (long long)pd.n + pd.m;
+    const unsigned* tr = reinterpret_cast<const unsigned*>(w.trace + wp.trace_off);
+    unsigned char* ops = w.ops + wp.ops_off;
+    const bool walk = !local || r->score > 0;
+    if (walk && (i < 0 || i >= pd.n || j < 0 || j >= pd.m)) err = WALK_RANGE;
+    while (walk && err == 0 && i >= 0 && j >= 0) {
+        const int cl = i & (64 * TRACE_W - 1), i0 = i - cl;
+        const int st = j + cl - band_trace_origin(i0, cl >> 3, bp.dlo);
+        if (j - i < bp.dlo || j - i > bp.dhi || st < 0 || st >= wp.steps) {
+            err = WALK_RANGE;
+            break;
+        }
+        const unsigned long long dw =
+            ((unsigned long long)(i0 / (64 * TRACE_W)) * 64u + (unsigned)(cl >> 3)) * (unsigned)wp.steps + (unsigned)st;
+        if (dw * 4u >= wp.trace_bytes) {
+            err = WALK_RANGE;
+            break;
+        }
+        const unsigned nib = (tr[dw] >> (4 * (cl & 7))) & 15u;
+        if (state == 0) {
+            const unsigned src = nib & 3u;
+            if (src == 0) {
+                if (!local) err = WALK_RANGE;
+                break;
+            }
+            if (src != 1) state = (int)src - 1;   // E: 1, F: 2
+        }
+        if (nops >= limit) {
+            err = WALK_OVERRUN;
+            break;
+        }
+        if (state == 0) {
+            ops[nops++] = 0;
+            --i;
+            --j;
+        } else if (state == 1) {
+            ops[nops++] = 1;
+            state = (nib & 4u) ? 1 : 0;
+            --i;
+        } else {
+            ops[nops++] = 2;
+            state = (nib & 8u) ? 2 : 0;
+            --j;
+        }
+    }
+    if (!local && err == 0) {   // the border exits (matrix_walk_mode)
+        const bool lead_i = j < 0;
+        const int run = lead_i ? i + 1 : (w.amode == SW_MODE_GLOBAL ? j + 1 : 0);
+        if (nops + (long long)run > limit) {
+            err = WALK_OVERRUN;
+        } else {
+            for (int k = 0; k < run; ++k) ops[nops++] = lead_i ? 1 : 2;
+            if (lead_i) i = -1;
+            else if (run > 0) j = -1;
         }
     }
     r->bi = i + 1;
@@ -841,9 +1117,10 @@ struct MatCtx {
     void* buf[13] = {};     // pairs, ctrl, scratch, arena, scores; traced launches: walk pairs, trace, results, operations;
                             // long pairs: locate items, checkpoints, strip items, walk states
     size_t cap[13] = {};
-    int wgs[17] = {};                     // resident workgroups per CU per W variant; [4]: the traced kernel,
+    int wgs[32] = {};                     // resident workgroups per CU per W variant; [4]: the traced kernel,
                                           // [5], [6]: the locate and the strip-fill kernel; [7 + 5 * (mode - 1) + ...]:
-                                          // the same five for SW_MODE_GLOBAL and SW_MODE_SEMIGLOBAL
+                                          // the same five for SW_MODE_GLOBAL and SW_MODE_SEMIGLOBAL;
+                                          // [17 + 5 * mode + ...]: the five band kernels of each mode
 };
 enum { B_PAIRS = 0, B_CTRL, B_SCRATCH, B_ARENA, B_SCORES, B_WALK, B_TRACE, B_RES, B_OPS, B_LONG, B_CKPT, B_ITEMS, B_STATE };
 thread_local float t_fill_ms = 0.f, t_walk_ms = 0.f;   // sw_last_align_ms
@@ -906,6 +1183,21 @@ const void* kernel_of(int wi, int amode = AM_LOCAL) {
 }
 int wgs_slot(int wi, int amode) { return amode == AM_LOCAL ? wi : 7 + 5 * (amode - 1) + wi; }
 
+template <int AM>
+const void* band_kernel_of_mode(int wi) {   // wi 4: the traced kernel
+    switch (wi) {
+        case 0: return (const void*)sw_matrix_band_kernel<1, false, AM>;
+        case 1: return (const void*)sw_matrix_band_kernel<2, false, AM>;
+        case 2: return (const void*)sw_matrix_band_kernel<4, false, AM>;
+        case 3: return (const void*)sw_matrix_band_kernel<8, false, AM>;
+        default: return (const void*)sw_matrix_band_kernel<TRACE_W, true, AM>;
+    }
+}
+const void* band_kernel_of(int wi, int amode) {
+    return amode == AM_GLOBAL ? band_kernel_of_mode<AM_GLOBAL>(wi) : amode == AM_SEMI ? band_kernel_of_mode<AM_SEMI>(wi) : band_kernel_of_mode<AM_LOCAL>(wi);
+}
+int band_wgs_slot(int wi, int amode) { return 17 + 5 * amode + wi; }
+
 // steps of one pair at W columns per lane with n columns, times an issue-slot estimate of a step
 // (about 9 instructions a cell and 8 a step for the DPP moves and the I/O rotation)
 long long pair_cost(long long n, long long m, int W) {
@@ -913,6 +1205,12 @@ long long pair_cost(long long n, long long m, int W) {
     const long long strips = (n + SW - 1) / SW;
     const long long chunks = (m + SW - 1 + MAT_C - 1) / MAT_C;
     return strips * chunks * MAT_C * (9LL * W + 8);
+}
+// the same for a band: the steps its strips run (about width + 2 * 64 * W each), and 5 more
+// instructions a cell and a step for the mask
+long long band_pair_cost(long long n, long long m, int dlo, int dhi, int W) {
+    long long mx = 0;
+    return band_steps(n, m, dlo, dhi, W, &mx) * (14LL * W + 13);
 }
 
 bool gaps_ok(int gap_init, int gap_ext) {
@@ -947,12 +1245,14 @@ void stage_matrix(MatArgs& a, const sw_matrix* mx) {
 
 // act: the pairs to launch (both lengths > 0); d_scores[idx] receives each score, every other
 // entry of d_scores[0, nscores) is zeroed.  amode != SW_MODE_LOCAL: seq1 always across the lanes.
+// band >= 0: the band launches (seq1 across the lanes in every mode); -1: none.
 int launch(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, std::vector<DevSeq>& act, int gap_init,
-           int gap_ext, int* d_scores, int nscores, bool a_on_lanes, int amode) {
+           int gap_ext, int* d_scores, int nscores, bool a_on_lanes, int amode, int band = -1) {
     const auto t0 = std::chrono::steady_clock::now();
-    if (amode != AM_LOCAL) a_on_lanes = true;
+    const bool banded = band >= 0;
+    if (amode != AM_LOCAL || banded) a_on_lanes = true;
     sw_stats st{};
-    st.mode = MODE_MATRIX;
+    st.mode = banded ? MODE_MATRIX_BAND : MODE_MATRIX;
     st.variant = amode;   // free on score-only matrix launches: the alignment mode (SW_MODE_*)
     st.C = MAT_C;
     st.items = nscores;
@@ -972,6 +1272,12 @@ int launch(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, std::ve
         if (forced > 0 && W_OF[k] != forced) continue;
         long long cost = 0;
         for (const DevSeq& p : act) {
+            if (banded) {
+                int dlo, dhi;
+                band_range(p.alen, p.blen, band, &dlo, &dhi);
+                cost += band_pair_cost(p.alen, p.blen, dlo, dhi, W_OF[k]);
+                continue;
+            }
             const long long ca = pair_cost(p.alen, p.blen, W_OF[k]);
             cost += a_on_lanes ? ca : std::min(ca, pair_cost(p.blen, p.alen, W_OF[k]));
         }
@@ -998,12 +1304,20 @@ int launch(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, std::ve
         d.out_idx = p.idx;
         d.swapped = swap ? 1 : 0;
         if (d.n > SW) scratch_rows = std::max<long long>(scratch_rows, d.m);
-        cells += (long long)d.n * d.m;
+        if (banded) {
+            int dlo, dhi;
+            band_range(d.n, d.m, band, &dlo, &dhi);
+            d.swapped = std::min(band, std::max(d.n, d.m));   // the band, where no pair is swapped
+            cells += band_cells(d.n, d.m, dlo, dhi);
+        } else {
+            cells += (long long)d.n * d.m;
+        }
     }
-    const int ws = wgs_slot(wi, amode);
+    const int ws = banded ? band_wgs_slot(wi, amode) : wgs_slot(wi, amode);
+    const void* kern = banded ? band_kernel_of(wi, amode) : kernel_of(wi, amode);
     if (c->wgs[ws] == 0) {
         int nb = 0;
-        MCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel_of(wi, amode), 256, 0));
+        MCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, 256, 0));
         c->wgs[ws] = std::max(1, std::min(nb, 8));
     }
     long long blocks = sw_get_option("blocks");
@@ -1034,9 +1348,9 @@ int launch(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, std::ve
 
     MCHK(hipEventRecord(c->ev0, c->stream));
     const dim3 grid((unsigned)blocks), block(256);
-    if (amode != AM_LOCAL) {
+    if (amode != AM_LOCAL || banded) {
         void* kargs[] = {&a};
-        MCHK(hipLaunchKernel(kernel_of(wi, amode), grid, block, kargs, 0, c->stream));
+        MCHK(hipLaunchKernel(kern, grid, block, kargs, 0, c->stream));
     } else {
         switch (wi) {
             case 0: hipLaunchKernelGGL(sw_matrix_kernel<1>, grid, block, 0, c->stream, a); break;
@@ -1073,7 +1387,7 @@ bool range_ok(const sw_matrix* mx, int alen, int blen, const char* what, int idx
 constexpr long long MAT_MAX_SEQ = (1LL << 27) - 1;   // the engine's longest sequence (8-B rows in a 32-bit resource)
 
 int score_host(const sw_matrix* mx, const unsigned char* const* a, const int* alen, const unsigned char* const* b,
-               const int* blen, int npairs, int gap_init, int gap_ext, int* out, int amode = AM_LOCAL) {
+               const int* blen, int npairs, int gap_init, int gap_ext, int* out, int amode = AM_LOCAL, int band = -1) {
     if (!gaps_ok(gap_init, gap_ext)) return -1;
     size_t total = 0;
     for (int k = 0; k < npairs; ++k) {
@@ -1122,7 +1436,7 @@ int score_host(const sw_matrix* mx, const unsigned char* const* a, const int* al
     if (ensure(c, B_ARENA, total) || ensure(c, B_SCORES, (size_t)npairs * sizeof(int))) return -1;
     if (total) MCHK(hipMemcpyAsync(c->buf[B_ARENA], arena.data(), total, hipMemcpyHostToDevice, c->stream));
     if (launch(c, mx, (const unsigned char*)c->buf[B_ARENA], act, gap_init, gap_ext, (int*)c->buf[B_SCORES], npairs, false,
-               amode))
+               amode, band))
         return -1;
     MCHK(hipMemcpy(out, c->buf[B_SCORES], (size_t)npairs * sizeof(int), hipMemcpyDeviceToHost));
     if (amode != AM_LOCAL)   // empty sequences are answered on the host
@@ -1145,8 +1459,10 @@ struct TracedOut {
     int blocks = 0;
 };
 int launch_traced(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, const std::vector<DevSeq>& act,
-                  int gap_init, int gap_ext, TracedOut& o, int amode) {
-    const int ws = wgs_slot(4, amode);
+                  int gap_init, int gap_ext, TracedOut& o, int amode, int band = -1) {
+    const bool banded = band >= 0;
+    const int ws = banded ? band_wgs_slot(4, amode) : wgs_slot(4, amode);
+    const void* kern = banded ? band_kernel_of(4, amode) : kernel_of(4, amode);
     constexpr int SW = 64 * TRACE_W;
     const size_t np = act.size();
     // longest first: the waves claim in order
@@ -1177,13 +1493,22 @@ int launch_traced(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, 
         WalkPair& w = walk[s];
         w.trace_off = (uint64_t)trace_total;
         w.ops_off = o.ops_off[(size_t)order[s]];
+        if (banded) {
+            BandPair bp;
+            band_range(p.alen, p.blen, band, &bp.dlo, &bp.dhi);
+            d.swapped = std::min(band, std::max(d.n, d.m));   // the band, where no pair is swapped
+            w.trace_bytes = (unsigned)band_trace_bytes(p.alen, p.blen, bp.dlo, bp.dhi);
+            w.steps = (int)band_trace_steps(p.blen, bp.dlo, bp.dhi);
+            trace_total += (long long)w.trace_bytes;
+            continue;
+        }
         w.trace_bytes = (unsigned)trace_bytes(p.alen, p.blen);
         w.steps = (int)trace_steps(p.blen);
         trace_total += trace_bytes(p.alen, p.blen);
     }
     if (c->wgs[ws] == 0) {
         int nb = 0;
-        MCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel_of(4, amode), 256, 0));
+        MCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, 256, 0));
         c->wgs[ws] = std::max(1, std::min(nb, 8));
     }
     long long blocks = sw_get_option("blocks");
@@ -1219,15 +1544,18 @@ int launch_traced(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, 
     WalkArgs w{a.pairs, a.walk, a.trace, (unsigned char*)c->buf[B_OPS], a.res, (int)np, amode};
 
     MCHK(hipEventRecord(c->ev0, c->stream));
-    if (amode != AM_LOCAL) {
+    if (amode != AM_LOCAL || banded) {
         void* kargs[] = {&a};
-        MCHK(hipLaunchKernel(kernel_of(4, amode), dim3((unsigned)blocks), dim3(256), kargs, 0, c->stream));
+        MCHK(hipLaunchKernel(kern, dim3((unsigned)blocks), dim3(256), kargs, 0, c->stream));
     } else {
         hipLaunchKernelGGL((sw_matrix_kernel<TRACE_W, true>), dim3((unsigned)blocks), dim3(256), 0, c->stream, a);
     }
     MCHK(hipGetLastError());
     MCHK(hipEventRecord(c->ev1, c->stream));
-    hipLaunchKernelGGL(sw_matrix_walk_kernel, dim3((unsigned)((np + 63) / 64)), dim3(64), 0, c->stream, w);
+    if (banded)
+        hipLaunchKernelGGL(sw_matrix_walk_band_kernel, dim3((unsigned)((np + 63) / 64)), dim3(64), 0, c->stream, w);
+    else
+        hipLaunchKernelGGL(sw_matrix_walk_kernel, dim3((unsigned)((np + 63) / 64)), dim3(64), 0, c->stream, w);
     MCHK(hipGetLastError());
     MCHK(hipEventRecord(c->ev2, c->stream));
     o.res.resize(np);
@@ -1502,18 +1830,37 @@ int matrix_align_long_device(const sw_matrix* mx, const unsigned char* d_arena, 
 
 int matrix_align_device(const sw_matrix* mx, const unsigned char* d_arena, const int64_t* a_off, const int* alen,
                         const int64_t* b_off, const int* blen, const int* name_idx, int npairs, int gap_init,
-                        int gap_ext, const char* what, AlignSink& sink, int amode) {
+                        int gap_ext, const char* what, AlignSink& sink, int amode, int band) {
     const auto t0 = std::chrono::steady_clock::now();
     if (!gaps_ok(gap_init, gap_ext)) return -1;
     const long long budget = sw_get_option("trace_mb") << 20;
+    const bool banded = band >= 0;
+    // the trace a pair holds: the whole matrix (section 11), or the band's strips
+    auto pair_trace = [&](int n, int m) {
+        if (!banded) return trace_bytes(n, m);
+        int dlo, dhi;
+        band_range(n, m, band, &dlo, &dhi);
+        return band_trace_bytes(n, m, dlo, dhi);
+    };
+    auto pair_cells = [&](int n, int m) {
+        if (!banded) return (long long)n * m;
+        int dlo, dhi;
+        band_range(n, m, band, &dlo, &dhi);
+        return band_cells(n, m, dlo, dhi);
+    };
     for (int k = 0; k < npairs; ++k) {   // refused before anything is launched
         if (amode != AM_LOCAL && !mode_range_ok(alen[k], blen[k], gap_init, gap_ext, what, name_idx ? name_idx[k] : k))
             return -1;
         if (alen[k] == 0 || blen[k] == 0) continue;
-        const long long need = trace_bytes(alen[k], blen[k]);
+        const long long need = pair_trace(alen[k], blen[k]);
         if (need > budget) {
             char m[320];
-            if (amode != AM_LOCAL)
+            if (banded)
+                std::snprintf(m, sizeof m,
+                              "%s %d: a %d x %d alignment in a band of %d needs %lld bytes of trace memory, more than option "
+                              "trace_mb = %lld MiB: a narrower band or a larger trace_mb aligns this pair",
+                              what, name_idx ? name_idx[k] : k, alen[k], blen[k], band, need, budget >> 20);
+            else if (amode != AM_LOCAL)
                 std::snprintf(m, sizeof m,
                               "%s %d: a %d x %d alignment needs %lld bytes of trace memory, more than option trace_mb = %lld "
                               "MiB, and the checkpointed traceback of long pairs is local only: no global or semi-global "
@@ -1533,7 +1880,7 @@ int matrix_align_device(const sw_matrix* mx, const unsigned char* d_arena, const
     t_fill_ms = t_walk_ms = t_locate_ms = 0.f;
     t_rounds = 0;
     sw_stats st{};
-    st.mode = MODE_MATRIX_TRACE;
+    st.mode = banded ? MODE_MATRIX_BAND_TRACE : MODE_MATRIX_TRACE;
     st.W = TRACE_W;
     st.C = MAT_C;
     st.items = npairs;
@@ -1546,17 +1893,17 @@ int matrix_align_device(const sw_matrix* mx, const unsigned char* d_arena, const
         act.clear();
         for (; hi < npairs; ++hi) {
             if (alen[hi] == 0 || blen[hi] == 0) continue;
-            const long long need = trace_bytes(alen[hi], blen[hi]);
+            const long long need = pair_trace(alen[hi], blen[hi]);
             if (!act.empty() && sum + need > budget) break;
             sum += need;
             act.push_back(DevSeq{a_off[hi], b_off[hi], alen[hi], blen[hi], hi});
-            st.cells += (long long)alen[hi] * blen[hi];
+            st.cells += pair_cells(alen[hi], blen[hi]);
         }
         if (!act.empty()) {
-            if (launch_traced(c, mx, d_arena, act, gap_init, gap_ext, o, amode)) return -1;
+            if (launch_traced(c, mx, d_arena, act, gap_init, gap_ext, o, amode, band)) return -1;
             st.variant += 1;
             st.blocks = o.blocks;
-            st.waves_per_cu = 4 * c->wgs[wgs_slot(4, amode)];
+            st.waves_per_cu = 4 * c->wgs[banded ? band_wgs_slot(4, amode) : wgs_slot(4, amode)];
             st.boundary_bytes = std::max(st.boundary_bytes, o.trace_total);
         }
         size_t s = 0;
@@ -1631,7 +1978,8 @@ int sw_score_matrix(const sw_matrix* mx, const unsigned char* seq1, const unsign
 // whole pairs or (long_pairs) the checkpointed traceback
 static int align_host(const char* fn, bool long_pairs, const sw_matrix* mx, const unsigned char* const* a, const int* alen,
                       const unsigned char* const* b, const int* blen, int npairs, int gap_init, int gap_ext,
-                      sw_alignment* out, unsigned* cigar, long long cigar_cap, long long* cigar_used, int amode = SW_MODE_LOCAL) {
+                      sw_alignment* out, unsigned* cigar, long long cigar_cap, long long* cigar_used, int amode = SW_MODE_LOCAL,
+                      int band = -1) {
     if (align_check(fn, mx, a, alen, b, blen, npairs, gap_init, gap_ext, out, cigar, cigar_cap, cigar_used)) return -1;
     AlignSink sink{out, {}};
     if (npairs == 0) return sink.finish(cigar, cigar_cap, cigar_used);
@@ -1659,9 +2007,30 @@ static int align_host(const char* fn, bool long_pairs, const sw_matrix* mx, cons
     if (long_pairs ? matrix_align_long_device(mx, (const unsigned char*)c->buf[B_ARENA], a_off.data(), alen, b_off.data(), blen,
                                               nullptr, npairs, gap_init, gap_ext, "pair", sink)
                    : matrix_align_device(mx, (const unsigned char*)c->buf[B_ARENA], a_off.data(), alen, b_off.data(), blen,
-                                         nullptr, npairs, gap_init, gap_ext, "pair", sink, amode))
+                                         nullptr, npairs, gap_init, gap_ext, "pair", sink, amode, band))
         return -1;
     return sink.finish(cigar, cigar_cap, cigar_used);
+}
+
+int sw_score_matrix_batch_band(const sw_matrix* mx, const unsigned char* const* a, const int* alen,
+                               const unsigned char* const* b, const int* blen, int npairs, int gap_init, int gap_ext,
+                               int mode, int band, int* scores_out) {
+    if (!mx || npairs < 0 || (npairs > 0 && (!a || !alen || !b || !blen || !scores_out))) {
+        report_error("sw_score_matrix_batch_band: invalid arguments");
+        return -1;
+    }
+    if (!mode_ok("sw_score_matrix_batch_band", mode) || !band_ok("sw_score_matrix_batch_band", band)) return -1;
+    if (npairs == 0) return 0;
+    return score_host(mx, a, alen, b, blen, npairs, gap_init, gap_ext, scores_out, mode, band);
+}
+
+int sw_align_matrix_batch_band(const sw_matrix* mx, const unsigned char* const* a, const int* alen,
+                               const unsigned char* const* b, const int* blen, int npairs, int gap_init, int gap_ext,
+                               int mode, int band, sw_alignment* out, unsigned* cigar, long long cigar_cap,
+                               long long* cigar_used) {
+    if (!mode_ok("sw_align_matrix_batch_band", mode) || !band_ok("sw_align_matrix_batch_band", band)) return -1;
+    return align_host("sw_align_matrix_batch_band", false, mx, a, alen, b, blen, npairs, gap_init, gap_ext, out, cigar,
+                      cigar_cap, cigar_used, mode, band);
 }
 
 int sw_score_matrix_batch_mode(const sw_matrix* mx, const unsigned char* const* a, const int* alen,

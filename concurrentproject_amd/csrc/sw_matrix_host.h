@@ -89,9 +89,30 @@ void align_mode_empty(AlignSink& sink, int k, int alen, int blen, int gap_init, 
 // memory; a pair that does not fit alone is refused (-1; the message names it `what` name_idx[k], or
 // `what` k when name_idx is null).
 // amode: SW_MODE_*; global and semi-global pairs are checked with mode_range_ok here.
+// band >= 0: the band launches (below), whose trace is the band's; -1: the whole matrix.
 int matrix_align_device(const sw_matrix* m, const unsigned char* d_arena, const int64_t* a_off, const int* alen,
                         const int64_t* b_off, const int* blen, const int* name_idx, int npairs, int gap_init,
-                        int gap_ext, const char* what, AlignSink& sink, int amode);
+                        int gap_ext, const char* what, AlignSink& sink, int amode, int band = -1);
+
+// ---- banded alignment (include/algoGPU.h sw_*_band) ----
+// The arithmetic is host only (sw_align_host.cpp); sw_matrix.hip's kernels compute the same per strip.
+// band >= 0, or the message names fn
+bool band_ok(const char* fn, int band);
+// dlo = min(0, m - n) - B, dhi = max(0, m - n) + B with B = min(band, max(n, m)): the same cells as
+// the band itself (at B >= max(n, m) every cell is inside), and no int overflows
+void band_range(int n, int m, int band, int* dlo, int* dhi);
+// cells (i, j), 0 <= i < n, 0 <= j < m, with dlo <= j - i <= dhi
+long long band_cells(long long n, long long m, long long dlo, long long dhi);
+// the strip of columns [i0, i0 + SW): its first step (a multiple of 64) and its chunks of 64 steps
+long long band_first(long long i0, long long dlo);
+long long band_chunks(long long i0, long long SW, long long m, long long dlo, long long dhi);
+// steps of all strips at W columns a lane (the work); *most: the largest of one strip
+long long band_steps(long long n, long long m, long long dlo, long long dhi, int W, long long* most);
+// The traced band launch keeps a run of dwords for every lane of every strip of 512 columns: the steps
+// at which the lane's eight columns meet cells of the band, at most min(dhi - dlo, m - 1) + 15; and
+// the pair's trace bytes: strips * 64 lanes * steps * 4
+long long band_trace_steps(long long m, long long dlo, long long dhi);
+long long band_trace_bytes(long long n, long long m, long long dlo, long long dhi);
 
 // ---- long pairs: checkpointed traceback, one strip at a time (include/algoGPU.h sw_align_matrix_long) ----
 // The arithmetic is host only (sw_align_host.cpp); the kernels and the rounds are in sw_matrix.hip.

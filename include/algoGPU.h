@@ -430,6 +430,60 @@ int  sw_db_align_matrix_mode(sw_db*, const sw_matrix*, const unsigned char* quer
                              const int* record_idx, int nidx, int gap_init, int gap_ext, int mode,
                              sw_alignment* out, unsigned* cigar, long long cigar_cap, long long* cigar_used);
 
+/* ---- banded alignment under a substitution matrix ----
+ * The *_band entry points compute only the cells within a fixed distance of the corner-to-corner
+ * diagonal: work and trace memory fall from n * m to n * width.
+ *
+ * THE BAND.  For a pair with n = len(seq1), m = len(seq2) and a band B >= 0:
+ *     dlo = min(0, m - n) - B        dhi = max(0, m - n) + B
+ *     cell (i, j), 0 <= i < n, 0 <= j < m, is in the band  iff  dlo <= j - i <= dhi
+ *   Both corners (0, 0) and (n-1, m-1) are in the band, and every row and column holds a cell of it.
+ *   A cell outside the band does not exist: in global and semi-global mode its H, E and F are minus
+ *   infinity; in local mode it is the border state H = E = F = 0 (equivalent there), and it is never
+ *   a candidate for the maximum or the end.
+ *   The borders are boundary conditions, not cells, and are NOT masked: H[i][-1] and H[-1][j] are
+ *   what the modes above define (0 in local mode).  Every cell in the band is reachable from a
+ *   border along its own diagonal, so its value is finite.
+ *   Everything else is the local rule (sw_align_matrix_batch) and the modes above, restricted to
+ *   cells in the band.  END CELL: local, the largest t, ties by the smallest i + j, then the smallest
+ *   j; global, (n-1, m-1); semi-global, the largest H[n-1][j] over j in the band, the smallest such j.
+ *   WALK: the same priorities and the same border exits.
+ *   With B >= max(n, m) the band is the whole matrix and the result equals the unbanded call's bit
+ *   for bit.  A call with a band always runs the band kernels.
+ *
+ * sw_score_matrix_batch_band / sw_align_matrix_batch_band: as the *_mode calls, every mode
+ *   (SW_MODE_LOCAL too), seq1 always across the lanes.  band < 0 and an unknown mode return -1 with
+ *   a message that names the function; the alphabet, gap, score-range and (global, semi-global)
+ *   mode-range checks are the *_mode calls'.  The traced launch holds the band's trace only --
+ *   sw_band_plan's trace_bytes a pair -- and a pair whose band does not fit option "trace_mb" alone
+ *   is refused before anything is launched.  Empty sequences are answered on the host as above.
+ *   sw_last_stats: mode 9 (scores) or 10 (traced); variant as modes 6 / 7; cells = the cells in the
+ *   bands.
+ * sw_align_matrix_cpu_band: the plain host aligner restricted to the band (full-matrix storage):
+ *   the yardstick of the GPU path, bit for bit.
+ * sw_band_plan: host arithmetic, no GPU call: dlo and dhi by the formula, the cells in the band,
+ *   the trace bytes the traced band launch holds for the pair and what the unbanded launch would.
+ * Not built with a band: the database calls, the long path, sw_db_search_db_matrix, X-drop or
+ *   adaptive bands, a band given as a diagonal range. */
+typedef struct {
+    long long dlo, dhi;            /* the diagonal range of j - i */
+    long long cells;               /* cells in the band */
+    long long trace_bytes;         /* sw_align_matrix_batch_band holds this much trace for the pair */
+    long long full_trace_bytes;    /* sw_align_matrix_batch(_mode) would hold this much */
+} sw_band_plan_t;
+int  sw_score_matrix_batch_band(const sw_matrix*, const unsigned char* const* a, const int* alen,
+                                const unsigned char* const* b, const int* blen, int npairs,
+                                int gap_init, int gap_ext, int mode, int band, int* scores_out);
+int  sw_align_matrix_batch_band(const sw_matrix*, const unsigned char* const* a, const int* alen,
+                                const unsigned char* const* b, const int* blen, int npairs,
+                                int gap_init, int gap_ext, int mode, int band, sw_alignment* out,
+                                unsigned* cigar, long long cigar_cap, long long* cigar_used);
+int  sw_align_matrix_cpu_band(const sw_matrix*, const unsigned char* const* a, const int* alen,
+                              const unsigned char* const* b, const int* blen, int npairs,
+                              int gap_init, int gap_ext, int mode, int band, sw_alignment* out,
+                              unsigned* cigar, long long cigar_cap, long long* cigar_used);
+int  sw_band_plan(int n, int m, int band, sw_band_plan_t* out);
+
 /* Tuning knobs (process-wide).  Keys:
  *   "W"        columns per lane: 0 = auto, 1, 2, 4, 8
  *   "C"        rows per strip hand-off chunk: 0 = auto, 16, 32, 64
@@ -448,7 +502,8 @@ int  sw_db_align_matrix_mode(sw_db*, const sw_matrix*, const unsigned char* quer
  *              (sw_last_stats also reports mode 6 = wave per pair, substitution matrix: the
  *              sw_*_matrix entry points, which honour "blocks" and "W" only; and mode 7 = the
  *              traced launches of sw_align_matrix_batch / sw_db_align_matrix: "blocks", "trace_mb";
- *              and mode 8 = their _long counterparts, which honour the same two)
+ *              and mode 8 = their _long counterparts, which honour the same two; and modes 9 and 10 =
+ *              the band launches, score-only and traced: sw_*_band, as modes 6 and 7)
  *   "trace_mb" MiB of trace memory one traced launch may hold, 1..3072 (default 1024)
  *   "duo16"    1 = (default) packed duos take max3 through v_pk_maximum3_f16 when every
  *              value stays below 0x7C00 (MATCH*(min(n,m)+1) <= 31743), 0 = u16 max only
@@ -537,7 +592,8 @@ typedef struct {
     long long boundary_bytes;
     int mode;
     int variant;            /* (mode 6: the alignment mode SW_MODE_*; mode 7: launches in bits 0-27, the alignment
-                               mode in bits 28-29; mode 8: strip-fill launches; the bits below are the engine's)
+                               mode in bits 28-29; mode 8: strip-fill launches; modes 9 and 10: as 6 and 7, and
+                               cells = the cells in the bands; the bits below are the engine's)
                                bit 0: duo max3 via v_pk_maximum3_f16; bit 1: flow2 streams row codes;
                                bit 2: flow2 ring edges; bit 3: the linear-gap step;
                                bit 4: flow2 two columns per lane; bit 5: flow2 pair per workgroup;
