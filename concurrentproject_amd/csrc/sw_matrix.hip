@@ -32,9 +32,10 @@
 // score-only instantiations are the code they were.  The traced variant (W = 8, seq1 always across
 // the lanes) stores 4 bits a cell, a dword a lane a step, to a per-pair trace buffer (WalkPair below)
 // and reports the end cell with the maximum; sw_matrix_walk_kernel then follows the recorded
-// decisions from the end cell, one lane a pair, and the host reverses and run-length encodes
-// (sw_align_host.cpp).  The end-cell rule and the walk priorities are in include/algoGPU.h.  A launch
-// holds at most option "trace_mb" MiB of trace; a pair that does not fit alone is refused there.
+// decisions from the end cell, one lane a pair (matrix_walk, the one walk of this file), and the host
+// reverses and run-length encodes (sw_align_host.cpp).  The end-cell rule and the walk priorities
+// are in include/algoGPU.h.  A launch holds at most option "trace_mb" MiB of trace; a pair that does
+// not fit alone is refused there.
 // Such pairs go through sw_align_matrix_long: a locate pass that keeps every strip's right-edge
 // column (a checkpoint), then the strips filled again one at a time, traced, from the checkpoint on
 // their left, and walked right to left -- the same bits, so the same alignment (LONG PAIRS below).
@@ -42,13 +43,15 @@
 // ALIGNMENT MODES.  Everything above is local alignment.  Global and semi-global alignment
 // (include/algoGPU.h SW_MODE_*) are a third template parameter of the same
 // step, pair loop and kernel (AM, below): no clamp, borders made by the set-up and the inflow, the
-// end read from one column.  The local instantiations are the code they were; the long path is local only.
+// end read from one column.  The long path is local only.
 //
 // BANDED ALIGNMENT (include/algoGPU.h sw_*_band) is a fourth template parameter
-// (BAND, below) of the step and the pair loop, launched through sw_matrix_band_kernel: a strip runs
-// only the chunks that hold cells of the band, a cell outside it is forced to the absent state, the
-// inflow is absent outside the rows the strip on the left stored, and the trace holds the band only.
-// Every instantiation above is the code it was.
+// (BAND, below) of the step, the pair loop and the kernel: a strip runs only the chunks that hold
+// cells of the band, a cell outside it is forced to the absent state, the inflow is absent outside
+// the rows the strip on the left stored, and the trace holds the band only.
+//
+// Every fill kernel is the same claim loop (matrix_stage, matrix_claim, matrix_claimed_pair) around matrix_pair, and
+// the host names each instantiation once (MatCtx::fill).
 #include "sw_device.h"
 #include "sw_matrix_host.h"
 #include "../../include/algoGPU.h"
@@ -84,7 +87,7 @@ struct MatPair {
     uint64_t row_off;   // the sequence that streams
     int n, m;           // columns, rows (> 0)
     int out_idx;
-    int swapped;        // 1: the columns are seq2 (table 1)
+    int swap_or_band;   // 1: the columns are seq2 (table 1); a band launch, which never swaps: the pair's band B
 };
 
 // Traced launches.  A cell's 4 bits: bits 0-1 where H came from (0 none: H = 0, 1 the diagonal, 2 E,
@@ -107,8 +110,8 @@ constexpr int WALK_OVERRUN = 1;   // more than n + m operations
 constexpr int WALK_RANGE = 2;     // a cell outside the pair or its trace buffer
 
 // Band launches (BANDED ALIGNMENT below): the pair's diagonal range, dlo <= j - i <= dhi.  A band
-// launch never swaps the sequences, and its MatPair::swapped carries the pair's band B instead
-// (clamped to max(n, m): band_range, sw_align_host.cpp); the kernels derive the range from it.
+// launch never swaps the sequences (j - i has one meaning), and its MatPair::swap_or_band is the pair's
+// band B (clamped to max(n, m): band_range, sw_align_host.cpp); the kernels derive the range from it.
 struct BandPair {
     int dlo, dhi;
 };
@@ -195,7 +198,7 @@ struct MStrip {
         constexpr int SW = 64 * W;
         const int go = a.gap_init, ge = a.gap_ext;
         const unsigned char* colseq = a.seq + pd.col_off;
-        const int tbase = pd.swapped ? MAT_TAB_BYTES : 0;
+        const int tbase = pd.swap_or_band ? MAT_TAB_BYTES : 0;   // (a band launch's claim loop has taken B out)
 #pragma unroll
         for (int p = 0; p < W; ++p) {
             const int c = strip * SW + lane * W + p;
@@ -587,86 +590,175 @@ __device__ void matrix_pair(const MatArgs& a, const MatPair& pd, const WalkPair&
     __builtin_amdgcn_raw_buffer_store_b32(M, sc_rsrc, lane == 0 ? (unsigned)pd.out_idx * 4u : OOR, 0, 0);
 }
 
-template <int W, bool TRACE = false, int AM = AM_LOCAL>
+// THE CLAIM LOOP of every fill kernel: the workgroup stages the byte-to-code map and both tables in
+// LDS, then each wave claims items from Ctrl::next_item until none is left.
+struct MatLds {
+    const signed char* tab;
+    const unsigned char* code;
+};
+__device__ __forceinline__ MatLds matrix_stage(const MatArgs& a) {
+    __shared__ unsigned s_tabw[2 * MAT_TAB_BYTES / 4];
+    __shared__ unsigned s_codew[64];
+    for (int i = threadIdx.x; i < 2 * MAT_TAB_BYTES / 4; i += 256) s_tabw[i] = a.tab[i];
+    if (threadIdx.x < 64) s_codew[threadIdx.x] = a.code[threadIdx.x];
+    __syncthreads();
+    return MatLds{reinterpret_cast<const signed char*>(s_tabw), reinterpret_cast<const unsigned char*>(s_codew)};
+}
+// the wave's next item; false: none is left
+__device__ __forceinline__ bool matrix_claim(const MatArgs& a, const int lane, unsigned& item) {
+    item = 0;
+    if (lane == 0) item = atomicAdd(&a.ctrl->next_item, 1u);
+    item = __builtin_amdgcn_readfirstlane(item);
+    return (int)item < a.npairs;
+}
+// the claimed item's pair, every field provably wave-uniform (buffer descriptors live in SGPRs);
+// TRACE: its trace buffer too
+template <bool TRACE>
+__device__ __forceinline__ void matrix_claimed_pair(const MatArgs& a, const unsigned item, MatPair& pd, WalkPair& wp) {
+    const MatPair raw = a.pairs[item];
+    pd.col_off = uniform64(raw.col_off);
+    pd.row_off = uniform64(raw.row_off);
+    pd.n = __builtin_amdgcn_readfirstlane(raw.n);
+    pd.m = __builtin_amdgcn_readfirstlane(raw.m);
+    pd.out_idx = __builtin_amdgcn_readfirstlane(raw.out_idx);
+    pd.swap_or_band = __builtin_amdgcn_readfirstlane(raw.swap_or_band);
+    wp = WalkPair{};
+    if constexpr (TRACE) {
+        const WalkPair wraw = a.walk[item];
+        wp.trace_off = uniform64(wraw.trace_off);
+        wp.trace_bytes = __builtin_amdgcn_readfirstlane(wraw.trace_bytes);
+        wp.steps = __builtin_amdgcn_readfirstlane(wraw.steps);
+    }
+}
+
+// BAND: the pair's diagonal range beside it; seq1 is across the lanes (table 0) in local mode too.
+template <int W, bool TRACE = false, int AM = AM_LOCAL, bool BAND = false>
 __global__ void __launch_bounds__(256) sw_matrix_kernel(MatArgs a) {
-    __shared__ unsigned s_tabw[2 * MAT_TAB_BYTES / 4];
-    __shared__ unsigned s_codew[64];
-    for (int i = threadIdx.x; i < 2 * MAT_TAB_BYTES / 4; i += 256) s_tabw[i] = a.tab[i];
-    if (threadIdx.x < 64) s_codew[threadIdx.x] = a.code[threadIdx.x];
-    __syncthreads();
-    const signed char* s_tab = reinterpret_cast<const signed char*>(s_tabw);
-    const unsigned char* s_code = reinterpret_cast<const unsigned char*>(s_codew);
+    const MatLds s = matrix_stage(a);
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
     uint2* scr = a.scratch + (uint64_t)wave * (uint64_t)a.scratch_rows;
-    for (;;) {
-        unsigned item = 0;
-        if (lane == 0) item = atomicAdd(&a.ctrl->next_item, 1u);
-        item = __builtin_amdgcn_readfirstlane(item);
-        if ((int)item >= a.npairs) return;
-        const MatPair raw = a.pairs[item];
-        MatPair pd;   // every field provably wave-uniform (buffer descriptors live in SGPRs)
-        pd.col_off = uniform64(raw.col_off);
-        pd.row_off = uniform64(raw.row_off);
-        pd.n = __builtin_amdgcn_readfirstlane(raw.n);
-        pd.m = __builtin_amdgcn_readfirstlane(raw.m);
-        pd.out_idx = __builtin_amdgcn_readfirstlane(raw.out_idx);
-        pd.swapped = __builtin_amdgcn_readfirstlane(raw.swapped);
-        WalkPair wp{};
-        if constexpr (TRACE) {
-            const WalkPair wraw = a.walk[item];
-            wp.trace_off = uniform64(wraw.trace_off);
-            wp.trace_bytes = __builtin_amdgcn_readfirstlane(wraw.trace_bytes);
+    unsigned item;
+    MatPair pd;
+    WalkPair wp;
+    while (matrix_claim(a, lane, item)) {
+        matrix_claimed_pair<TRACE>(a, item, pd, wp);
+        BandPair bp{0, 0};
+        if constexpr (BAND) {
+            bp = band_of(pd.n, pd.m, pd.swap_or_band);
+            pd.swap_or_band = 0;
         }
-        matrix_pair<W, TRACE ? M_TRACE : M_SCORE, AM>(a, pd, wp, lane, scr, s_tab, s_code);
+        matrix_pair<W, TRACE ? M_TRACE : M_SCORE, AM, BAND>(a, pd, wp, lane, scr, s.tab, s.code, nullptr, 0, bp);
     }
 }
 
-// The band launches: sw_matrix_kernel's claim loop with the pair's diagonal range beside it.  seq1 is
-// always across the lanes (j - i has one meaning), in local mode too.
-template <int W, bool TRACE, int AM>
-__global__ void __launch_bounds__(256) sw_matrix_band_kernel(MatArgs a) {
-    __shared__ unsigned s_tabw[2 * MAT_TAB_BYTES / 4];
-    __shared__ unsigned s_codew[64];
-    for (int i = threadIdx.x; i < 2 * MAT_TAB_BYTES / 4; i += 256) s_tabw[i] = a.tab[i];
-    if (threadIdx.x < 64) s_codew[threadIdx.x] = a.code[threadIdx.x];
-    __syncthreads();
-    const signed char* s_tab = reinterpret_cast<const signed char*>(s_tabw);
-    const unsigned char* s_code = reinterpret_cast<const unsigned char*>(s_codew);
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
-    uint2* scr = a.scratch + (uint64_t)wave * (uint64_t)a.scratch_rows;
-    for (;;) {
-        unsigned item = 0;
-        if (lane == 0) item = atomicAdd(&a.ctrl->next_item, 1u);
-        item = __builtin_amdgcn_readfirstlane(item);
-        if ((int)item >= a.npairs) return;
-        const MatPair raw = a.pairs[item];
-        MatPair pd;   // every field provably wave-uniform (buffer descriptors live in SGPRs)
-        pd.col_off = uniform64(raw.col_off);
-        pd.row_off = uniform64(raw.row_off);
-        pd.n = __builtin_amdgcn_readfirstlane(raw.n);
-        pd.m = __builtin_amdgcn_readfirstlane(raw.m);
-        pd.out_idx = __builtin_amdgcn_readfirstlane(raw.out_idx);
-        pd.swapped = 0;
-        const BandPair bp = band_of(pd.n, pd.m, __builtin_amdgcn_readfirstlane(raw.swapped));
-        WalkPair wp{};
-        if constexpr (TRACE) {
-            const WalkPair wraw = a.walk[item];
-            wp.trace_off = uniform64(wraw.trace_off);
-            wp.trace_bytes = __builtin_amdgcn_readfirstlane(wraw.trace_bytes);
-            wp.steps = __builtin_amdgcn_readfirstlane(wraw.steps);
-        }
-        matrix_pair<W, TRACE ? M_TRACE : M_SCORE, AM, true>(a, pd, wp, lane, scr, s_tab, s_code, nullptr, 0, bp);
+// THE WALK: one lane a pair, from the end cell in state H along the recorded decisions, the
+// operations (0 M, 1 I, 2 D) written last first.  Priorities (include/algoGPU.h): in local mode a
+// cell with H = 0 ends the walk before anything else; in H the diagonal, then E, then F; in E and F
+// opening before extending (both already decided by the fill: the bits say which).  Every iteration
+// writes one operation and there are at most n + m; every cell read is checked against the pair and
+// its trace.  Nothing here waits for anything.
+//
+// Global and semi-global: no H = 0 stop (source 0 is unused, and an error if met); the walk leaves
+// the matrix at j < 0 -- the remaining i + 1 residues of seq1 are one leading I run, the top border
+// H[i][-1] -- or at i < 0: global, the remaining j + 1 residues of seq2 are one leading D run;
+// semi-global, it stops there.  A gap is never extended out of a border (E[-1][j] and F[i][-1] are
+// minus infinity, so the fill recorded an opening), hence the walk leaves in state H.  Every M uses
+// a residue of both sequences, an I one of seq1, a D one of seq2: n + m bytes are still enough.
+//
+// Where cell (i, j) lives is the trace's layout, a compile-time parameter: cell() gives the dword and
+// the shift of the cell's nibble, or false for a cell the trace does not hold; first_column() is the
+// column below which the walk has left the trace (on its left side: the resumable walk of LONG PAIRS).
+// [strip - strip0][step][lane] dwords (WalkPair above).  A whole pair: strip0 = 0; the one-strip buffer
+// of a long pair: strip0 = that strip.
+struct StripTrace {
+    int strip0, steps;
+    unsigned bytes;
+    __device__ int first_column() const { return strip0 * (64 * TRACE_W); }
+    __device__ bool cell(int i, int j, unsigned long long& dw, int& shift) const {
+        const int cl = i & (64 * TRACE_W - 1);
+        dw = ((unsigned long long)(unsigned)(i / (64 * TRACE_W) - strip0) * (unsigned)steps + (unsigned)(j + cl)) * 64u +
+             (unsigned)(cl >> 3);
+        shift = 4 * (cl & 7);
+        return dw * 4u < bytes;
     }
+};
+// [strip][lane][step - band_trace_origin] dwords, `steps` a lane; a cell outside the band is not held.
+// (The fill never sends the walk there: an absent neighbour offers minus infinity, or in local mode
+// 0, which is the H = 0 stop.)
+struct BandTrace {
+    BandPair bp;
+    int steps;
+    unsigned bytes;
+    __device__ int first_column() const { return 0; }
+    __device__ bool cell(int i, int j, unsigned long long& dw, int& shift) const {
+        const int cl = i & (64 * TRACE_W - 1), i0 = i - cl;
+        const int st = j + cl - band_trace_origin(i0, cl >> 3, bp.dlo);
+        if (j - i < bp.dlo || j - i > bp.dhi || st < 0 || st >= steps) return false;
+        dw = ((unsigned long long)(i0 / (64 * TRACE_W)) * 64u + (unsigned)(cl >> 3)) * (unsigned)steps + (unsigned)st;
+        shift = 4 * (cl & 7);
+        return dw * 4u < bytes;
+    }
+};
+
+struct Walk {
+    int i, j, state;       // where the walk stands: the cell, and 0 H, 1 E, 2 F
+    int nops, err, done;   // operations written so far, WALK_* error, 1: the walk has ended
+};
+
+// Walks on from w until the walk has ended (done: a cell with H = 0 in local mode, or the walk has
+// left the matrix and the border run is written), failed (err) or left the trace on its left side.
+// The only definition of the nibble decode, the state transition and the operation write.
+template <class TRACE>
+__device__ __forceinline__ void matrix_walk(const TRACE t, const unsigned char* trace, unsigned char* ops, const int n,
+                                            const int m, const int amode, Walk& w) {
+    int i = w.i, j = w.j, state = w.state, nops = w.nops, err = 0;
+    bool h0 = false;   // the walk met a cell with H = 0 in state H
+    const long long limit = (long long)n + m;
+    const unsigned* tr = reinterpret_cast<const unsigned*>(trace);
+    const int lo = t.first_column();
+    if (i < 0 || i >= n || j < 0 || j >= m) err = WALK_RANGE;
+    while (err == 0 && i >= 0 && j >= 0 && i >= lo) {
+        unsigned long long dw;
+        int shift;
+        if (!t.cell(i, j, dw, shift)) {
+            err = WALK_RANGE;
+            break;
+        }
+        const unsigned nib = (tr[dw] >> shift) & 15u;
+        if (state == 0) {
+            const unsigned src = nib & 3u;
+            if (src == 0) {
+                h0 = true;
+                break;
+            }
+            state = (int)src - 1;   // the diagonal: stays in H; E: 1, F: 2
+        }
+        if (nops >= limit) {
+            err = WALK_OVERRUN;
+            break;
+        }
+        ops[nops++] = (unsigned char)state;   // M, I, D: the state's own number
+        i -= state != 2;                      // M and I use a residue of seq1,
+        j -= state != 1;                      // M and D one of seq2
+        state = (nib >> (state + 1)) & 1u ? state : 0;   // E: bit 2, F: bit 3 extend; H stays H
+    }
+    if (h0 && amode != SW_MODE_LOCAL) err = WALK_RANGE;   // source 0 is local's stop only
+    const int done = err == 0 && (h0 || i < 0 || j < 0);
+    if (amode != SW_MODE_LOCAL && done) {   // the border exits
+        const bool lead_i = j < 0;
+        const int run = lead_i ? i + 1 : (amode == SW_MODE_GLOBAL ? j + 1 : 0);
+        if (nops + (long long)run > limit) {
+            err = WALK_OVERRUN;
+        } else {
+            for (int k = 0; k < run; ++k) ops[nops++] = lead_i ? 1 : 2;
+            if (lead_i) i = -1;
+            else if (run > 0) j = -1;
+        }
+    }
+    w = Walk{i, j, state, nops, err, done};
 }
 
-// The walk: one lane a pair, from the end cell in state H along the recorded decisions, the
-// operations (0 M, 1 I, 2 D) written last first.  Priorities (include/algoGPU.h): a cell with
-// H = 0 ends the walk before anything else; in H the diagonal, then E, then F; in E and F opening
-// before extending (both already decided by the fill: the bits say which).  Every iteration writes
-// one operation and there are at most n + m; every cell read is checked against the pair and its
-// buffer.  Nothing here waits for anything.
 struct WalkArgs {
     const MatPair* pairs;
     const WalkPair* walk;
@@ -677,198 +769,29 @@ struct WalkArgs {
     int amode;   // SW_MODE_*
 };
 
-// Global and semi-global: no H = 0 stop (source 0 is unused, and an error if met); the walk leaves
-// the matrix at j < 0 -- the remaining i + 1 residues of seq1 are one leading I run, the top border
-// H[i][-1] -- or at i < 0: global, the remaining j + 1 residues of seq2 are one leading D run;
-// semi-global, it stops there.  A gap is never extended out of a border (E[-1][j] and F[i][-1] are
-// minus infinity, so the fill recorded an opening), hence the walk leaves in state H.  Every M uses
-// a residue of both sequences, an I one of seq1, a D one of seq2: n + m bytes are still enough.
-__device__ void matrix_walk_mode(const WalkArgs& w, const MatPair& pd, const WalkPair& wp, TraceRes* r) {
-    int i = r->ei, j = r->ej, state = 0, err = 0, nops = 0;
-    const long long limit = (long long)pd.n + pd.m;
-    const unsigned* tr = reinterpret_cast<const unsigned*>(w.trace + wp.trace_off);
-    unsigned char* ops = w.ops + wp.ops_off;
-    if (i < 0 || i >= pd.n || j < 0 || j >= pd.m) err = WALK_RANGE;
-    while (err == 0 && i >= 0 && j >= 0) {
-        const int cl = i & (64 * TRACE_W - 1);
-        const unsigned long long dw =
-            ((unsigned long long)(i / (64 * TRACE_W)) * (unsigned)wp.steps + (unsigned)(j + cl)) * 64u + (unsigned)(cl >> 3);
-        if (dw * 4u >= wp.trace_bytes) {
-            err = WALK_RANGE;
-            break;
-        }
-        const unsigned nib = (tr[dw] >> (4 * (cl & 7))) & 15u;
-        if (state == 0) {
-            const unsigned src = nib & 3u;
-            if (src == 0) {
-                err = WALK_RANGE;
-                break;
-            }
-            if (src != 1) state = (int)src - 1;   // E: 1, F: 2
-        }
-        if (nops >= limit) {
-            err = WALK_OVERRUN;
-            break;
-        }
-        if (state == 0) {
-            ops[nops++] = 0;
-            --i;
-            --j;
-        } else if (state == 1) {
-            ops[nops++] = 1;
-            state = (nib & 4u) ? 1 : 0;
-            --i;
-        } else {
-            ops[nops++] = 2;
-            state = (nib & 8u) ? 2 : 0;
-            --j;
-        }
-    }
-    if (err == 0) {   // the border exits
-        const bool lead_i = j < 0;
-        const int run = lead_i ? i + 1 : (w.amode == SW_MODE_GLOBAL ? j + 1 : 0);
-        if (nops + (long long)run > limit) {
-            err = WALK_OVERRUN;
-        } else {
-            for (int k = 0; k < run; ++k) ops[nops++] = lead_i ? 1 : 2;
-            if (lead_i) i = -1;
-            else if (run > 0) j = -1;
-        }
-    }
-    r->bi = i + 1;
-    r->bj = j + 1;
-    r->nops = nops;
-    r->err = err;
-}
-
+// The walk of a whole traced launch, every mode; BAND: of a band launch.  A local pair without an
+// alignment (score 0) never walks.
+template <bool BAND>
 __global__ void __launch_bounds__(64) sw_matrix_walk_kernel(WalkArgs w) {
     const int item = (int)(blockIdx.x * 64 + threadIdx.x);
     if (item >= w.npairs) return;
     const MatPair pd = w.pairs[item];
     const WalkPair wp = w.walk[item];
     TraceRes* r = w.res + pd.out_idx;
-    if (w.amode != SW_MODE_LOCAL) {
-        matrix_walk_mode(w, pd, wp, r);
-        return;
-    }
-    int i = r->ei, j = r->ej, state = 0, err = 0, nops = 0;
-    const long long limit = (long long)pd.n + pd.m;
-    if (r->score > 0) {
-        const unsigned* tr = reinterpret_cast<const unsigned*>(w.trace + wp.trace_off);
+    Walk s{r->ei, r->ej, 0, 0, 0, 0};
+    if (w.amode != SW_MODE_LOCAL || r->score > 0) {
+        const unsigned char* trace = w.trace + wp.trace_off;
         unsigned char* ops = w.ops + wp.ops_off;
-        if (i >= pd.n || j >= pd.m) err = WALK_RANGE;
-        while (err == 0 && i >= 0 && j >= 0) {
-            const int cl = i & (64 * TRACE_W - 1);
-            const unsigned long long dw =
-                ((unsigned long long)(i / (64 * TRACE_W)) * (unsigned)wp.steps + (unsigned)(j + cl)) * 64u + (unsigned)(cl >> 3);
-            if (dw * 4u >= wp.trace_bytes) {
-                err = WALK_RANGE;
-                break;
-            }
-            const unsigned nib = (tr[dw] >> (4 * (cl & 7))) & 15u;
-            if (state == 0) {
-                const unsigned src = nib & 3u;
-                if (src == 0) break;
-                if (src != 1) state = (int)src - 1;   // E: 1, F: 2
-            }
-            if (nops >= limit) {
-                err = WALK_OVERRUN;
-                break;
-            }
-            if (state == 0) {
-                ops[nops++] = 0;
-                --i;
-                --j;
-            } else if (state == 1) {
-                ops[nops++] = 1;
-                state = (nib & 4u) ? 1 : 0;
-                --i;
-            } else {
-                ops[nops++] = 2;
-                state = (nib & 8u) ? 2 : 0;
-                --j;
-            }
-        }
+        if constexpr (BAND)
+            matrix_walk(BandTrace{band_of(pd.n, pd.m, pd.swap_or_band), wp.steps, wp.trace_bytes}, trace, ops, pd.n, pd.m,
+                        w.amode, s);
+        else
+            matrix_walk(StripTrace{0, wp.steps, wp.trace_bytes}, trace, ops, pd.n, pd.m, w.amode, s);
     }
-    r->bi = i + 1;
-    r->bj = j + 1;
-    r->nops = nops;
-    r->err = err;
-}
-
-// The walk of a band launch, all three modes: the loops above with the band's trace layout
-// (band_trace_origin) and one more check: a cell outside the
-// band is WALK_RANGE, like a cell outside the pair or the buffer.  (The fill never sends the walk
-// there: an absent neighbour offers minus infinity, or in local mode 0, which is the H = 0 stop.)
-__global__ void __launch_bounds__(64) sw_matrix_walk_band_kernel(WalkArgs w) {
-    const int item = (int)(blockIdx.x * 64 + threadIdx.x);
-    if (item >= w.npairs) return;
-    const MatPair pd = w.pairs[item];
-    const WalkPair wp = w.walk[item];
-    const BandPair bp = band_of(pd.n, pd.m, pd.swapped);
-    TraceRes* r = w.res + pd.out_idx;
-    const bool local = w.amode == SW_MODE_LOCAL;
-    int i = r->ei, j = r->ej, state = 0, err = 0, nops = 0;
-    const long long limit = (long long)pd.n + pd.m;
-    const unsigned* tr = reinterpret_cast<const unsigned*>(w.trace + wp.trace_off);
-    unsigned char* ops = w.ops + wp.ops_off;
-    const bool walk = !local || r->score > 0;
-    if (walk && (i < 0 || i >= pd.n || j < 0 || j >= pd.m)) err = WALK_RANGE;
-    while (walk && err == 0 && i >= 0 && j >= 0) {
-        const int cl = i & (64 * TRACE_W - 1), i0 = i - cl;
-        const int st = j + cl - band_trace_origin(i0, cl >> 3, bp.dlo);
-        if (j - i < bp.dlo || j - i > bp.dhi || st < 0 || st >= wp.steps) {
-            err = WALK_RANGE;
-            break;
-        }
-        const unsigned long long dw =
-            ((unsigned long long)(i0 / (64 * TRACE_W)) * 64u + (unsigned)(cl >> 3)) * (unsigned)wp.steps + (unsigned)st;
-        if (dw * 4u >= wp.trace_bytes) {
-            err = WALK_RANGE;
-            break;
-        }
-        const unsigned nib = (tr[dw] >> (4 * (cl & 7))) & 15u;
-        if (state == 0) {
-            const unsigned src = nib & 3u;
-            if (src == 0) {
-                if (!local) err = WALK_RANGE;
-                break;
-            }
-            if (src != 1) state = (int)src - 1;   // E: 1, F: 2
-        }
-        if (nops >= limit) {
-            err = WALK_OVERRUN;
-            break;
-        }
-        if (state == 0) {
-            ops[nops++] = 0;
-            --i;
-            --j;
-        } else if (state == 1) {
-            ops[nops++] = 1;
-            state = (nib & 4u) ? 1 : 0;
-            --i;
-        } else {
-            ops[nops++] = 2;
-            state = (nib & 8u) ? 2 : 0;
-            --j;
-        }
-    }
-    if (!local && err == 0) {   // the border exits (matrix_walk_mode)
-        const bool lead_i = j < 0;
-        const int run = lead_i ? i + 1 : (w.amode == SW_MODE_GLOBAL ? j + 1 : 0);
-        if (nops + (long long)run > limit) {
-            err = WALK_OVERRUN;
-        } else {
-            for (int k = 0; k < run; ++k) ops[nops++] = lead_i ? 1 : 2;
-            if (lead_i) i = -1;
-            else if (run > 0) j = -1;
-        }
-    }
-    r->bi = i + 1;
-    r->bj = j + 1;
-    r->nops = nops;
-    r->err = err;
+    r->bi = s.i + 1;
+    r->bj = s.j + 1;
+    r->nops = s.nops;
+    r->err = s.err;
 }
 
 // ---- LONG PAIRS: checkpointed traceback, one strip at a time (sw_align_matrix_long) -----------
@@ -901,9 +824,7 @@ struct StripItem {          // strip fill and walk: one strip of one pair
     unsigned trace_bytes;   // of the item's buffer: at least align_strip_trace_bytes(rows)
     int slot;               // the pair's WalkState
 };
-struct WalkState {          // 32 B a pair, read by the host after every round
-    int i, j, state;        // where the walk stands: the cell, and 0 H, 1 E, 2 F
-    int nops, err, done;    // operations written so far, WALK_* error, 1: the walk has ended
+struct WalkState : Walk {   // 32 B a pair, read by the host after every round
     int pad0, pad1;
 };
 static_assert(sizeof(WalkState) == 32, "walk state");
@@ -914,38 +835,21 @@ struct LongArgs {
     unsigned char* trace;
 };
 
-__device__ __forceinline__ void matrix_stage(const MatArgs& a, unsigned* s_tabw, unsigned* s_codew) {
-    for (int i = threadIdx.x; i < 2 * MAT_TAB_BYTES / 4; i += 256) s_tabw[i] = a.tab[i];
-    if (threadIdx.x < 64) s_codew[threadIdx.x] = a.code[threadIdx.x];
-    __syncthreads();
-}
-
 // The locate pass: sw_matrix_kernel<8, true> without the trace, every strip's right edge kept.
 // a.res[out_idx] receives score, ei, ej (the first half of a TraceRes).
 __global__ void __launch_bounds__(256) sw_matrix_locate_kernel(MatArgs a, LongArgs x) {
-    __shared__ unsigned s_tabw[2 * MAT_TAB_BYTES / 4];
-    __shared__ unsigned s_codew[64];
-    matrix_stage(a, s_tabw, s_codew);
-    const signed char* s_tab = reinterpret_cast<const signed char*>(s_tabw);
-    const unsigned char* s_code = reinterpret_cast<const unsigned char*>(s_codew);
+    const MatLds s = matrix_stage(a);
     const int lane = threadIdx.x & 63;
-    for (;;) {
-        unsigned item = 0;
-        if (lane == 0) item = atomicAdd(&a.ctrl->next_item, 1u);
-        item = __builtin_amdgcn_readfirstlane(item);
-        if ((int)item >= a.npairs) return;
-        const MatPair raw = a.pairs[item];
+    unsigned item;
+    MatPair pd;
+    WalkPair wp;
+    while (matrix_claim(a, lane, item)) {
+        matrix_claimed_pair<false>(a, item, pd, wp);
+        pd.swap_or_band = 0;   // seq1 across the lanes
         const LongPair lraw = x.lp[item];
-        MatPair pd;   // every field provably wave-uniform (buffer descriptors live in SGPRs)
-        pd.col_off = uniform64(raw.col_off);
-        pd.row_off = uniform64(raw.row_off);
-        pd.n = __builtin_amdgcn_readfirstlane(raw.n);
-        pd.m = __builtin_amdgcn_readfirstlane(raw.m);
-        pd.out_idx = __builtin_amdgcn_readfirstlane(raw.out_idx);
-        pd.swapped = 0;
         unsigned char* ckpt = x.ckpt + uniform64(lraw.ckpt_off);
         const unsigned stride = __builtin_amdgcn_readfirstlane(lraw.ckpt_stride);
-        matrix_pair<TRACE_W, M_LOCATE>(a, pd, WalkPair{}, lane, nullptr, s_tab, s_code, ckpt, stride);
+        matrix_pair<TRACE_W, M_LOCATE>(a, pd, wp, lane, nullptr, s.tab, s.code, ckpt, stride);
     }
 }
 
@@ -966,7 +870,7 @@ __device__ void matrix_strip_fill(const MatArgs& a, const LongArgs& x, const Str
     pd.n = it.n;
     pd.m = m;
     pd.out_idx = 0;
-    pd.swapped = 0;
+    pd.swap_or_band = 0;
     const __amdgpu_buffer_rsrc_t row_rsrc =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(a.seq + it.row_off), 0, m, RSRC_FLAGS);
     const __amdgpu_buffer_rsrc_t in_rsrc = __builtin_amdgcn_make_buffer_rsrc(
@@ -997,17 +901,10 @@ __device__ void matrix_strip_fill(const MatArgs& a, const LongArgs& x, const Str
 }
 
 __global__ void __launch_bounds__(256) sw_matrix_strip_kernel(MatArgs a, LongArgs x) {
-    __shared__ unsigned s_tabw[2 * MAT_TAB_BYTES / 4];
-    __shared__ unsigned s_codew[64];
-    matrix_stage(a, s_tabw, s_codew);
-    const signed char* s_tab = reinterpret_cast<const signed char*>(s_tabw);
-    const unsigned char* s_code = reinterpret_cast<const unsigned char*>(s_codew);
+    const MatLds s = matrix_stage(a);
     const int lane = threadIdx.x & 63;
-    for (;;) {
-        unsigned item = 0;
-        if (lane == 0) item = atomicAdd(&a.ctrl->next_item, 1u);
-        item = __builtin_amdgcn_readfirstlane(item);
-        if ((int)item >= a.npairs) return;
+    unsigned item;
+    while (matrix_claim(a, lane, item)) {
         const StripItem raw = x.items[item];
         StripItem it{};   // every field used provably wave-uniform
         it.col_off = uniform64(raw.col_off);
@@ -1018,12 +915,13 @@ __global__ void __launch_bounds__(256) sw_matrix_strip_kernel(MatArgs a, LongArg
         it.strip = __builtin_amdgcn_readfirstlane(raw.strip);
         it.rows = __builtin_amdgcn_readfirstlane(raw.rows);
         it.trace_bytes = __builtin_amdgcn_readfirstlane(raw.trace_bytes);
-        matrix_strip_fill(a, x, it, lane, s_tab, s_code);
+        matrix_strip_fill(a, x, it, lane, s.tab, s.code);
     }
 }
 
-// The resumable walk: sw_matrix_walk_kernel's loop from the pair's WalkState, while the cell is in
-// the item's strip; the cell at column i - 512 * strip of the one-strip buffer.  Operations are
+// The resumable walk: matrix_walk from the pair's WalkState, while the cell is in the item's strip;
+// the cell at column i - 512 * strip of the one-strip buffer (StripTrace with strip0 = strip, so the
+// steps of a strip multiply 0).  Operations are
 // appended at the running offset nops.  done: a cell with H = 0 met in state H, or i < 0, or j < 0.
 // Otherwise the walk left the strip through its left side, in state H (after an M) or E (after an
 // I): the state the last cell's extend bit decided, exactly as inside a strip.
@@ -1039,61 +937,16 @@ __global__ void __launch_bounds__(64) sw_matrix_walk_strip_kernel(WalkStripArgs 
     const int item = (int)(blockIdx.x * 64 + threadIdx.x);
     if (item >= w.nitems) return;
     const StripItem it = w.items[item];
-    WalkState* s = w.st + it.slot;
-    int i = s->i, j = s->j, state = s->state, nops = s->nops, err = s->err, done = s->done;
-    if (done || err) return;
-    const long long limit = (long long)it.n + it.m;
+    WalkState* st = w.st + it.slot;
+    Walk s = *st;
+    if (s.done || s.err) return;
     const int lo = it.strip * (64 * TRACE_W);
-    const unsigned* tr = reinterpret_cast<const unsigned*>(w.trace + it.trace_off);
-    unsigned char* ops = w.ops + it.ops_off;
-    if (i >= it.n || j >= it.m || i < lo || i >= lo + 64 * TRACE_W || j >= it.rows || j < 0 || nops < 0 || state < 0 ||
-        state > 2)
-        err = WALK_RANGE;
-    while (err == 0) {
-        if (i < 0 || j < 0) {
-            done = 1;
-            break;
-        }
-        if (i < lo) break;   // the next round's strip
-        const int cl = i - lo;
-        const unsigned long long dw = (unsigned long long)(unsigned)(j + cl) * 64u + (unsigned)(cl >> 3);
-        if (dw * 4u >= it.trace_bytes) {
-            err = WALK_RANGE;
-            break;
-        }
-        const unsigned nib = (tr[dw] >> (4 * (cl & 7))) & 15u;
-        if (state == 0) {
-            const unsigned src = nib & 3u;
-            if (src == 0) {
-                done = 1;
-                break;
-            }
-            if (src != 1) state = (int)src - 1;   // E: 1, F: 2
-        }
-        if (nops >= limit) {
-            err = WALK_OVERRUN;
-            break;
-        }
-        if (state == 0) {
-            ops[nops++] = 0;
-            --i;
-            --j;
-        } else if (state == 1) {
-            ops[nops++] = 1;
-            state = (nib & 4u) ? 1 : 0;
-            --i;
-        } else {
-            ops[nops++] = 2;
-            state = (nib & 8u) ? 2 : 0;
-            --j;
-        }
-    }
-    s->i = i;
-    s->j = j;
-    s->state = state;
-    s->nops = nops;
-    s->err = err;
-    s->done = done;
+    if (s.i < lo || s.i >= lo + 64 * TRACE_W || s.j >= it.rows || s.nops < 0 || s.state < 0 || s.state > 2)
+        s.err = WALK_RANGE;   // (matrix_walk checks the cell against the pair)
+    else
+        matrix_walk(StripTrace{it.strip, 0, it.trace_bytes}, w.trace + it.trace_off, w.ops + it.ops_off, it.n, it.m,
+                    SW_MODE_LOCAL, s);
+    *static_cast<Walk*>(st) = s;
 }
 
 // ---- host ------------------------------------------------------------------------------------
@@ -1109,20 +962,47 @@ __global__ void __launch_bounds__(64) sw_matrix_walk_strip_kernel(WalkStripArgs 
         }                                                                                    \
     } while (0)
 
+// A fill kernel and, once a launch has asked, its resident workgroups per CU.  One launch is one
+// kernel: the run-time choice among the compiled ones is an index into MatCtx::fill.
+struct FillKernel {
+    const void* fn = nullptr;
+    int wgs = 0;
+};
+constexpr int W_OF[4] = {1, 2, 4, 8};
+constexpr int WI_TRACED = 4;   // a row of the table: the score-only kernels at W_OF, then the traced one
+template <int AM, bool BAND>
+void name_fill_kernels(FillKernel (&row)[5]) {
+    row[0].fn = (const void*)sw_matrix_kernel<1, false, AM, BAND>;
+    row[1].fn = (const void*)sw_matrix_kernel<2, false, AM, BAND>;
+    row[2].fn = (const void*)sw_matrix_kernel<4, false, AM, BAND>;
+    row[3].fn = (const void*)sw_matrix_kernel<8, false, AM, BAND>;
+    row[WI_TRACED].fn = (const void*)sw_matrix_kernel<TRACE_W, true, AM, BAND>;
+}
+
 // device memory and a stream per (thread, device), as the engine's own context (sw_engine.hip)
+enum {
+    B_PAIRS = 0, B_CTRL, B_SCRATCH, B_ARENA, B_SCORES,   // every launch
+    B_WALK, B_TRACE, B_RES, B_OPS,                       // traced launches: walk pairs, trace, results, operations
+    B_LONG, B_CKPT, B_ITEMS, B_STATE,                    // long pairs: locate items, checkpoints, strip items, walk states
+    B_COUNT
+};
 struct MatCtx {
     int cus = 256;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
-    void* buf[13] = {};     // pairs, ctrl, scratch, arena, scores; traced launches: walk pairs, trace, results, operations;
-                            // long pairs: locate items, checkpoints, strip items, walk states
-    size_t cap[13] = {};
-    int wgs[32] = {};                     // resident workgroups per CU per W variant; [4]: the traced kernel,
-                                          // [5], [6]: the locate and the strip-fill kernel; [7 + 5 * (mode - 1) + ...]:
-                                          // the same five for SW_MODE_GLOBAL and SW_MODE_SEMIGLOBAL;
-                                          // [17 + 5 * mode + ...]: the five band kernels of each mode
+    void* buf[B_COUNT] = {};
+    size_t cap[B_COUNT] = {};
+    FillKernel fill[2][3][5];   // [band][SW_MODE_*][index into W_OF, or WI_TRACED]
+    FillKernel locate{(const void*)sw_matrix_locate_kernel}, strip{(const void*)sw_matrix_strip_kernel};
+    MatCtx() {
+        name_fill_kernels<AM_LOCAL, false>(fill[0][AM_LOCAL]);
+        name_fill_kernels<AM_GLOBAL, false>(fill[0][AM_GLOBAL]);
+        name_fill_kernels<AM_SEMI, false>(fill[0][AM_SEMI]);
+        name_fill_kernels<AM_LOCAL, true>(fill[1][AM_LOCAL]);
+        name_fill_kernels<AM_GLOBAL, true>(fill[1][AM_GLOBAL]);
+        name_fill_kernels<AM_SEMI, true>(fill[1][AM_SEMI]);
+    }
 };
-enum { B_PAIRS = 0, B_CTRL, B_SCRATCH, B_ARENA, B_SCORES, B_WALK, B_TRACE, B_RES, B_OPS, B_LONG, B_CKPT, B_ITEMS, B_STATE };
 thread_local float t_fill_ms = 0.f, t_walk_ms = 0.f;   // sw_last_align_ms
 thread_local float t_locate_ms = 0.f;                  // sw_last_align_long_ms: the locate launches' share of t_fill_ms
 thread_local int t_rounds = 0;                         // and the rounds, summed over the call's groups
@@ -1164,39 +1044,6 @@ int ensure(MatCtx* c, int which, size_t bytes) {
     c->cap[which] = want;
     return 0;
 }
-
-constexpr int W_OF[4] = {1, 2, 4, 8};
-
-template <int AM>
-const void* kernel_of_mode(int wi) {   // wi 4: the traced kernel
-    switch (wi) {
-        case 0: return (const void*)sw_matrix_kernel<1, false, AM>;
-        case 1: return (const void*)sw_matrix_kernel<2, false, AM>;
-        case 2: return (const void*)sw_matrix_kernel<4, false, AM>;
-        case 3: return (const void*)sw_matrix_kernel<8, false, AM>;
-        default: return (const void*)sw_matrix_kernel<TRACE_W, true, AM>;
-    }
-}
-// one launch is one mode: the run-time choice among the compiled kernels
-const void* kernel_of(int wi, int amode = AM_LOCAL) {
-    return amode == AM_GLOBAL ? kernel_of_mode<AM_GLOBAL>(wi) : amode == AM_SEMI ? kernel_of_mode<AM_SEMI>(wi) : kernel_of_mode<AM_LOCAL>(wi);
-}
-int wgs_slot(int wi, int amode) { return amode == AM_LOCAL ? wi : 7 + 5 * (amode - 1) + wi; }
-
-template <int AM>
-const void* band_kernel_of_mode(int wi) {   // wi 4: the traced kernel
-    switch (wi) {
-        case 0: return (const void*)sw_matrix_band_kernel<1, false, AM>;
-        case 1: return (const void*)sw_matrix_band_kernel<2, false, AM>;
-        case 2: return (const void*)sw_matrix_band_kernel<4, false, AM>;
-        case 3: return (const void*)sw_matrix_band_kernel<8, false, AM>;
-        default: return (const void*)sw_matrix_band_kernel<TRACE_W, true, AM>;
-    }
-}
-const void* band_kernel_of(int wi, int amode) {
-    return amode == AM_GLOBAL ? band_kernel_of_mode<AM_GLOBAL>(wi) : amode == AM_SEMI ? band_kernel_of_mode<AM_SEMI>(wi) : band_kernel_of_mode<AM_LOCAL>(wi);
-}
-int band_wgs_slot(int wi, int amode) { return 17 + 5 * amode + wi; }
 
 // steps of one pair at W columns per lane with n columns, times an issue-slot estimate of a step
 // (about 9 instructions a cell and 8 a step for the DPP moves and the I/O rotation)
@@ -1243,6 +1090,94 @@ void stage_matrix(MatArgs& a, const sw_matrix* mx) {
     std::memcpy(a.tab, tab, sizeof tab);
 }
 
+// ---- the steps every fill launch takes (launch, launch_traced, long_group) ----
+
+// longest first: the waves claim in order.  launch sorts its pairs themselves (a search launches
+// every record of a database); the traced launches, whose results go back by slot, sort indices.
+struct Longer {
+    bool operator()(const DevSeq& x, const DevSeq& y) const { return (long long)x.alen * x.blen > (long long)y.alen * y.blen; }
+};
+std::vector<int> longest_first(const std::vector<DevSeq>& act) {
+    std::vector<int> order(act.size());
+    std::iota(order.begin(), order.end(), 0);
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return Longer()(act[(size_t)x], act[(size_t)y]); });
+    return order;
+}
+
+// trace bytes of one pair: strips * steps * 256 (WalkPair)
+long long trace_steps(long long m) { return (m + 64 * TRACE_W - 1 + MAT_C - 1) / MAT_C * MAT_C; }
+long long trace_bytes(long long n, long long m) { return (n + 64 * TRACE_W - 1) / (64 * TRACE_W) * trace_steps(m) * 256; }
+
+// The pair as the kernels take it; its result goes to slot out_idx.  swap: seq2 across the lanes.
+// band >= 0: a band launch, which never swaps and carries the pair's B.  w (traced launches): the
+// trace the pair holds, the whole matrix or the band; the offsets are the caller's.
+MatPair make_pair(const DevSeq& p, int out_idx, bool swap, int band, WalkPair* w = nullptr) {
+    MatPair d;
+    d.col_off = (uint64_t)(swap ? p.b_off : p.a_off);
+    d.row_off = (uint64_t)(swap ? p.a_off : p.b_off);
+    d.n = swap ? p.blen : p.alen;
+    d.m = swap ? p.alen : p.blen;
+    d.out_idx = out_idx;
+    d.swap_or_band = band >= 0 ? std::min(band, std::max(d.n, d.m)) : swap ? 1 : 0;
+    if (w && band >= 0) {
+        int dlo, dhi;
+        band_range(d.n, d.m, band, &dlo, &dhi);
+        w->trace_bytes = (unsigned)band_trace_bytes(d.n, d.m, dlo, dhi);
+        w->steps = (int)band_trace_steps(d.m, dlo, dhi);
+    } else if (w) {
+        w->trace_bytes = (unsigned)trace_bytes(d.n, d.m);
+        w->steps = (int)trace_steps(d.m);
+    }
+    return d;
+}
+
+// Workgroups of a claim-loop launch over `items` items: the resident ones (option "blocks" instead),
+// no more than a wave an item, and, where every wave holds a scratch column of scratch_rows entries,
+// at most 1 GiB of scratch in all.
+int fill_blocks(MatCtx* c, FillKernel& k, size_t items, long long scratch_rows, long long* out) {
+    if (k.wgs == 0) {
+        int nb = 0;
+        MCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k.fn, 256, 0));
+        k.wgs = std::max(1, std::min(nb, 8));
+    }
+    long long blocks = sw_get_option("blocks");
+    if (blocks <= 0) blocks = (long long)c->cus * k.wgs;
+    blocks = std::max<long long>(1, std::min<long long>(blocks, ((long long)items + 3) / 4));
+    if (scratch_rows > 0) blocks = std::max<long long>(1, std::min<long long>(blocks, (1LL << 30) / (scratch_rows * 8 * 4)));
+    *out = blocks;
+    return 0;
+}
+
+// The pairs uploaded, the claim counter zeroed, the scratch sized (a right-edge column of scratch_rows
+// entries per wave of `blocks` workgroups), and the MatArgs fields every fill kernel reads.  long_group
+// passes scratch_rows = 0; its kernels never touch the scratch pointer, whatever it holds.
+int fill_args(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, const std::vector<MatPair>& pairs, int nscores,
+              int gap_init, int gap_ext, long long scratch_rows, long long blocks, MatArgs& a) {
+    if (ensure(c, B_PAIRS, pairs.size() * sizeof(MatPair)) || ensure(c, B_CTRL, sizeof(Ctrl)) ||
+        ensure(c, B_SCRATCH, (size_t)scratch_rows * 8 * 4 * (size_t)blocks))
+        return -1;
+    MCHK(hipMemcpyAsync(c->buf[B_PAIRS], pairs.data(), pairs.size() * sizeof(MatPair), hipMemcpyHostToDevice, c->stream));
+    MCHK(hipMemsetAsync(c->buf[B_CTRL], 0, sizeof(Ctrl), c->stream));
+    a.seq = d_arena;
+    a.pairs = (const MatPair*)c->buf[B_PAIRS];
+    a.ctrl = (Ctrl*)c->buf[B_CTRL];
+    a.scratch = (uint2*)c->buf[B_SCRATCH];
+    a.scratch_rows = scratch_rows;
+    a.npairs = (int)pairs.size();
+    a.nscores = nscores;
+    a.gap_init = gap_init;
+    a.gap_ext = gap_ext;
+    stage_matrix(a, mx);
+    return 0;
+}
+// the scratch column of a launch: the rows of its widest pair of more than one strip, in whole chunks
+long long scratch_rows_of(const std::vector<MatPair>& pairs, int SW) {
+    long long rows = 0;
+    for (const MatPair& d : pairs)
+        if (d.n > SW) rows = std::max<long long>(rows, d.m);
+    return (rows + 63) / 64 * 64;
+}
+
 // act: the pairs to launch (both lengths > 0); d_scores[idx] receives each score, every other
 // entry of d_scores[0, nscores) is zeroed.  amode != SW_MODE_LOCAL: seq1 always across the lanes.
 // band >= 0: the band launches (seq1 across the lanes in every mode); -1: none.
@@ -1286,79 +1221,34 @@ int launch(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, std::ve
             wi = k;
         }
     }
-    const int W = W_OF[wi], SW = 64 * W;
-    // longest first: the waves claim in order
-    std::stable_sort(act.begin(), act.end(), [](const DevSeq& x, const DevSeq& y) {
-        return (long long)x.alen * x.blen > (long long)y.alen * y.blen;
-    });
+    const int W = W_OF[wi];
+    std::stable_sort(act.begin(), act.end(), Longer());
     std::vector<MatPair> pairs(act.size());
-    long long scratch_rows = 0, cells = 0;
+    long long cells = 0;
     for (size_t k = 0; k < act.size(); ++k) {
         const DevSeq& p = act[k];
         const bool swap = !a_on_lanes && pair_cost(p.blen, p.alen, W) < pair_cost(p.alen, p.blen, W);
-        MatPair& d = pairs[k];
-        d.col_off = (uint64_t)(swap ? p.b_off : p.a_off);
-        d.row_off = (uint64_t)(swap ? p.a_off : p.b_off);
-        d.n = swap ? p.blen : p.alen;
-        d.m = swap ? p.alen : p.blen;
-        d.out_idx = p.idx;
-        d.swapped = swap ? 1 : 0;
-        if (d.n > SW) scratch_rows = std::max<long long>(scratch_rows, d.m);
+        const MatPair& d = pairs[k] = make_pair(p, p.idx, swap, band);
         if (banded) {
             int dlo, dhi;
             band_range(d.n, d.m, band, &dlo, &dhi);
-            d.swapped = std::min(band, std::max(d.n, d.m));   // the band, where no pair is swapped
             cells += band_cells(d.n, d.m, dlo, dhi);
         } else {
             cells += (long long)d.n * d.m;
         }
     }
-    const int ws = banded ? band_wgs_slot(wi, amode) : wgs_slot(wi, amode);
-    const void* kern = banded ? band_kernel_of(wi, amode) : kernel_of(wi, amode);
-    if (c->wgs[ws] == 0) {
-        int nb = 0;
-        MCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, 256, 0));
-        c->wgs[ws] = std::max(1, std::min(nb, 8));
-    }
-    long long blocks = sw_get_option("blocks");
-    if (blocks <= 0) blocks = (long long)c->cus * c->wgs[ws];
-    blocks = std::max<long long>(1, std::min<long long>(blocks, ((long long)act.size() + 3) / 4));
-    // the scratch: a right-edge column per resident wave, at most 1 GiB in all
-    scratch_rows = (scratch_rows + 63) / 64 * 64;
-    if (scratch_rows > 0) blocks = std::max<long long>(1, std::min<long long>(blocks, (1LL << 30) / (scratch_rows * 8 * 4)));
-    const size_t scratch_bytes = (size_t)scratch_rows * 8 * 4 * (size_t)blocks;
-    if (ensure(c, B_PAIRS, pairs.size() * sizeof(MatPair)) || ensure(c, B_CTRL, sizeof(Ctrl)) ||
-        ensure(c, B_SCRATCH, scratch_bytes))
-        return -1;
-    MCHK(hipMemcpyAsync(c->buf[B_PAIRS], pairs.data(), pairs.size() * sizeof(MatPair), hipMemcpyHostToDevice, c->stream));
-    MCHK(hipMemsetAsync(c->buf[B_CTRL], 0, sizeof(Ctrl), c->stream));
-
+    FillKernel& kern = c->fill[banded][amode][wi];
+    const long long scratch_rows = scratch_rows_of(pairs, 64 * W);
+    long long blocks = 0;
     MatArgs a{};
-    a.seq = d_arena;
-    a.pairs = (const MatPair*)c->buf[B_PAIRS];
-    a.ctrl = (Ctrl*)c->buf[B_CTRL];
+    if (fill_blocks(c, kern, pairs.size(), scratch_rows, &blocks) ||
+        fill_args(c, mx, d_arena, pairs, nscores, gap_init, gap_ext, scratch_rows, blocks, a))
+        return -1;
     a.scores = d_scores;
-    a.scratch = (uint2*)c->buf[B_SCRATCH];
-    a.scratch_rows = scratch_rows;
-    a.npairs = (int)pairs.size();
-    a.nscores = nscores;
-    a.gap_init = gap_init;
-    a.gap_ext = gap_ext;
-    stage_matrix(a, mx);
 
     MCHK(hipEventRecord(c->ev0, c->stream));
-    const dim3 grid((unsigned)blocks), block(256);
-    if (amode != AM_LOCAL || banded) {
-        void* kargs[] = {&a};
-        MCHK(hipLaunchKernel(kern, grid, block, kargs, 0, c->stream));
-    } else {
-        switch (wi) {
-            case 0: hipLaunchKernelGGL(sw_matrix_kernel<1>, grid, block, 0, c->stream, a); break;
-            case 1: hipLaunchKernelGGL(sw_matrix_kernel<2>, grid, block, 0, c->stream, a); break;
-            case 2: hipLaunchKernelGGL(sw_matrix_kernel<4>, grid, block, 0, c->stream, a); break;
-            default: hipLaunchKernelGGL(sw_matrix_kernel<8>, grid, block, 0, c->stream, a); break;
-        }
-    }
+    void* kargs[] = {&a};
+    MCHK(hipLaunchKernel(kern.fn, dim3((unsigned)blocks), dim3(256), kargs, 0, c->stream));
     MCHK(hipGetLastError());
     MCHK(hipEventRecord(c->ev1, c->stream));
     MCHK(hipStreamSynchronize(c->stream));
@@ -1366,8 +1256,8 @@ int launch(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, std::ve
     st.W = W;
     st.cells = cells;
     st.blocks = (int)blocks;
-    st.waves_per_cu = 4 * c->wgs[ws];
-    st.boundary_bytes = (long long)scratch_bytes;
+    st.waves_per_cu = 4 * kern.wgs;
+    st.boundary_bytes = scratch_rows * 8 * 4 * blocks;
     st.total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     report_stats(st);
     return 0;
@@ -1445,10 +1335,6 @@ int score_host(const sw_matrix* mx, const unsigned char* const* a, const int* al
     return 0;
 }
 
-// trace bytes of one pair: strips * steps * 256 (WalkPair)
-long long trace_steps(long long m) { return (m + 64 * TRACE_W - 1 + MAT_C - 1) / MAT_C * MAT_C; }
-long long trace_bytes(long long n, long long m) { return (n + 64 * TRACE_W - 1) / (64 * TRACE_W) * trace_steps(m) * 256; }
-
 // One traced launch: fill, then walk.  act: the pairs (both lengths > 0, idx = the slot of res and
 // of ops_off), in input order.  res[idx] and the operations (ops, at ops_off[idx]) come back to the host.
 struct TracedOut {
@@ -1461,16 +1347,9 @@ struct TracedOut {
 int launch_traced(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, const std::vector<DevSeq>& act,
                   int gap_init, int gap_ext, TracedOut& o, int amode, int band = -1) {
     const bool banded = band >= 0;
-    const int ws = banded ? band_wgs_slot(4, amode) : wgs_slot(4, amode);
-    const void* kern = banded ? band_kernel_of(4, amode) : kernel_of(4, amode);
-    constexpr int SW = 64 * TRACE_W;
+    FillKernel& kern = c->fill[banded][amode][WI_TRACED];
     const size_t np = act.size();
-    // longest first: the waves claim in order
-    std::vector<int> order(np);
-    std::iota(order.begin(), order.end(), 0);
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) {
-        return (long long)act[x].alen * act[x].blen > (long long)act[y].alen * act[y].blen;
-    });
+    const std::vector<int> order = longest_first(act);
     std::vector<MatPair> pairs(np);
     std::vector<WalkPair> walk(np);
     o.ops_off.assign(np, 0);
@@ -1479,83 +1358,36 @@ int launch_traced(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, 
         o.ops_off[k] = ops_total;
         ops_total += (uint64_t)act[k].alen + (uint64_t)act[k].blen;
     }
-    long long scratch_rows = 0, trace_total = 0;
+    long long trace_total = 0;
     for (size_t s = 0; s < np; ++s) {
-        const DevSeq& p = act[(size_t)order[s]];
-        MatPair& d = pairs[s];
-        d.col_off = (uint64_t)p.a_off;
-        d.row_off = (uint64_t)p.b_off;
-        d.n = p.alen;
-        d.m = p.blen;
-        d.out_idx = order[s];
-        d.swapped = 0;
-        if (d.n > SW) scratch_rows = std::max<long long>(scratch_rows, d.m);
         WalkPair& w = walk[s];
+        pairs[s] = make_pair(act[(size_t)order[s]], order[s], false, band, &w);
         w.trace_off = (uint64_t)trace_total;
         w.ops_off = o.ops_off[(size_t)order[s]];
-        if (banded) {
-            BandPair bp;
-            band_range(p.alen, p.blen, band, &bp.dlo, &bp.dhi);
-            d.swapped = std::min(band, std::max(d.n, d.m));   // the band, where no pair is swapped
-            w.trace_bytes = (unsigned)band_trace_bytes(p.alen, p.blen, bp.dlo, bp.dhi);
-            w.steps = (int)band_trace_steps(p.blen, bp.dlo, bp.dhi);
-            trace_total += (long long)w.trace_bytes;
-            continue;
-        }
-        w.trace_bytes = (unsigned)trace_bytes(p.alen, p.blen);
-        w.steps = (int)trace_steps(p.blen);
-        trace_total += trace_bytes(p.alen, p.blen);
+        trace_total += (long long)w.trace_bytes;
     }
-    if (c->wgs[ws] == 0) {
-        int nb = 0;
-        MCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, 256, 0));
-        c->wgs[ws] = std::max(1, std::min(nb, 8));
-    }
-    long long blocks = sw_get_option("blocks");
-    if (blocks <= 0) blocks = (long long)c->cus * c->wgs[ws];
-    blocks = std::max<long long>(1, std::min<long long>(blocks, ((long long)np + 3) / 4));
-    scratch_rows = (scratch_rows + 63) / 64 * 64;
-    if (scratch_rows > 0) blocks = std::max<long long>(1, std::min<long long>(blocks, (1LL << 30) / (scratch_rows * 8 * 4)));
-    const size_t scratch_bytes = (size_t)scratch_rows * 8 * 4 * (size_t)blocks;
-    if (ensure(c, B_PAIRS, np * sizeof(MatPair)) || ensure(c, B_CTRL, sizeof(Ctrl)) || ensure(c, B_SCRATCH, scratch_bytes) ||
+    const long long scratch_rows = scratch_rows_of(pairs, 64 * TRACE_W);
+    long long blocks = 0;
+    MatArgs a{};
+    if (fill_blocks(c, kern, np, scratch_rows, &blocks) ||
+        fill_args(c, mx, d_arena, pairs, (int)np, gap_init, gap_ext, scratch_rows, blocks, a) ||
         ensure(c, B_WALK, np * sizeof(WalkPair)) || ensure(c, B_TRACE, (size_t)trace_total) ||
         ensure(c, B_RES, np * sizeof(TraceRes)) || ensure(c, B_OPS, (size_t)ops_total))
         return -1;
-    MCHK(hipMemcpyAsync(c->buf[B_PAIRS], pairs.data(), np * sizeof(MatPair), hipMemcpyHostToDevice, c->stream));
     MCHK(hipMemcpyAsync(c->buf[B_WALK], walk.data(), np * sizeof(WalkPair), hipMemcpyHostToDevice, c->stream));
-    MCHK(hipMemsetAsync(c->buf[B_CTRL], 0, sizeof(Ctrl), c->stream));
     MCHK(hipMemsetAsync(c->buf[B_RES], 0, np * sizeof(TraceRes), c->stream));
-
-    MatArgs a{};
-    a.seq = d_arena;
-    a.pairs = (const MatPair*)c->buf[B_PAIRS];
-    a.ctrl = (Ctrl*)c->buf[B_CTRL];
-    a.scores = nullptr;
-    a.scratch = (uint2*)c->buf[B_SCRATCH];
-    a.scratch_rows = scratch_rows;
-    a.npairs = (int)np;
-    a.nscores = (int)np;
-    a.gap_init = gap_init;
-    a.gap_ext = gap_ext;
-    stage_matrix(a, mx);
     a.walk = (const WalkPair*)c->buf[B_WALK];
     a.trace = (unsigned char*)c->buf[B_TRACE];
     a.res = (TraceRes*)c->buf[B_RES];
     WalkArgs w{a.pairs, a.walk, a.trace, (unsigned char*)c->buf[B_OPS], a.res, (int)np, amode};
 
     MCHK(hipEventRecord(c->ev0, c->stream));
-    if (amode != AM_LOCAL || banded) {
-        void* kargs[] = {&a};
-        MCHK(hipLaunchKernel(kern, dim3((unsigned)blocks), dim3(256), kargs, 0, c->stream));
-    } else {
-        hipLaunchKernelGGL((sw_matrix_kernel<TRACE_W, true>), dim3((unsigned)blocks), dim3(256), 0, c->stream, a);
-    }
+    void* kargs[] = {&a};
+    MCHK(hipLaunchKernel(kern.fn, dim3((unsigned)blocks), dim3(256), kargs, 0, c->stream));
     MCHK(hipGetLastError());
     MCHK(hipEventRecord(c->ev1, c->stream));
-    if (banded)
-        hipLaunchKernelGGL(sw_matrix_walk_band_kernel, dim3((unsigned)((np + 63) / 64)), dim3(64), 0, c->stream, w);
-    else
-        hipLaunchKernelGGL(sw_matrix_walk_kernel, dim3((unsigned)((np + 63) / 64)), dim3(64), 0, c->stream, w);
+    if (banded) hipLaunchKernelGGL(sw_matrix_walk_kernel<true>, dim3((unsigned)((np + 63) / 64)), dim3(64), 0, c->stream, w);
+    else hipLaunchKernelGGL(sw_matrix_walk_kernel<false>, dim3((unsigned)((np + 63) / 64)), dim3(64), 0, c->stream, w);
     MCHK(hipGetLastError());
     MCHK(hipEventRecord(c->ev2, c->stream));
     o.res.resize(np);
@@ -1574,19 +1406,6 @@ int launch_traced(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, 
 }
 
 // ---- long pairs: the host side of the checkpointed traceback ----
-
-// workgroups of a claim-loop launch over `items` items (option "blocks" as in launch_traced)
-int long_blocks(MatCtx* c, int which, const void* kernel, size_t items, long long* out) {
-    if (c->wgs[which] == 0) {
-        int nb = 0;
-        MCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, 256, 0));
-        c->wgs[which] = std::max(1, std::min(nb, 8));
-    }
-    long long blocks = sw_get_option("blocks");
-    if (blocks <= 0) blocks = (long long)c->cus * c->wgs[which];
-    *out = std::max<long long>(1, std::min<long long>(blocks, ((long long)items + 3) / 4));
-    return 0;
-}
 
 int walk_failed(const char* what, int idx, int err) {
     char m[200];
@@ -1611,11 +1430,7 @@ struct LongOut {
 int long_group(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, const std::vector<DevSeq>& act, int gap_init,
                int gap_ext, long long trace_budget, const char* what, const int* name_idx, sw_stats& st, LongOut& o) {
     const size_t np = act.size();
-    std::vector<int> order(np);
-    std::iota(order.begin(), order.end(), 0);
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) {   // longest first: the waves claim in order
-        return (long long)act[x].alen * act[x].blen > (long long)act[y].alen * act[y].blen;
-    });
+    const std::vector<int> order = longest_first(act);
     std::vector<uint64_t> ckpt_off(np);
     o.ops_off.assign(np, 0);
     uint64_t ops_total = 0, ckpt_total = 0;
@@ -1631,36 +1446,26 @@ int long_group(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, con
     std::vector<LongPair> lp(np);
     for (size_t k = 0; k < np; ++k) {
         const DevSeq& p = act[(size_t)order[k]];
-        pairs[k] = MatPair{(uint64_t)p.a_off, (uint64_t)p.b_off, p.alen, p.blen, order[k], 0};
+        pairs[k] = make_pair(p, order[k], false, -1);
         lp[k] = LongPair{ckpt_off[(size_t)order[k]], (unsigned)align_ckpt_stride(p.blen), 0u};
     }
     long long blocks = 0;
-    if (long_blocks(c, 5, (const void*)sw_matrix_locate_kernel, np, &blocks)) return -1;
-    if (ensure(c, B_PAIRS, np * sizeof(MatPair)) || ensure(c, B_CTRL, sizeof(Ctrl)) || ensure(c, B_LONG, np * sizeof(LongPair)) ||
-        ensure(c, B_CKPT, (size_t)ckpt_total) || ensure(c, B_RES, np * sizeof(TraceRes)) ||
-        ensure(c, B_OPS, (size_t)ops_total) || ensure(c, B_STATE, np * sizeof(WalkState)))
+    MatArgs a{};   // no scratch: every strip's right edge goes to a checkpoint column
+    if (fill_blocks(c, c->locate, np, 0, &blocks) || fill_args(c, mx, d_arena, pairs, (int)np, gap_init, gap_ext, 0, blocks, a) ||
+        ensure(c, B_LONG, np * sizeof(LongPair)) || ensure(c, B_CKPT, (size_t)ckpt_total) ||
+        ensure(c, B_RES, np * sizeof(TraceRes)) || ensure(c, B_OPS, (size_t)ops_total) ||
+        ensure(c, B_STATE, np * sizeof(WalkState)))
         return -1;
-    MCHK(hipMemcpyAsync(c->buf[B_PAIRS], pairs.data(), np * sizeof(MatPair), hipMemcpyHostToDevice, c->stream));
     MCHK(hipMemcpyAsync(c->buf[B_LONG], lp.data(), np * sizeof(LongPair), hipMemcpyHostToDevice, c->stream));
-    MCHK(hipMemsetAsync(c->buf[B_CTRL], 0, sizeof(Ctrl), c->stream));
     MCHK(hipMemsetAsync(c->buf[B_RES], 0, np * sizeof(TraceRes), c->stream));
-
-    MatArgs a{};
-    a.seq = d_arena;
-    a.pairs = (const MatPair*)c->buf[B_PAIRS];
-    a.ctrl = (Ctrl*)c->buf[B_CTRL];
-    a.npairs = (int)np;
-    a.nscores = (int)np;
-    a.gap_init = gap_init;
-    a.gap_ext = gap_ext;
-    stage_matrix(a, mx);
     a.res = (TraceRes*)c->buf[B_RES];
     LongArgs x{};
     x.lp = (const LongPair*)c->buf[B_LONG];
     x.ckpt = (unsigned char*)c->buf[B_CKPT];
+    void* kargs[] = {&a, &x};
 
     MCHK(hipEventRecord(c->ev0, c->stream));
-    hipLaunchKernelGGL(sw_matrix_locate_kernel, dim3((unsigned)blocks), dim3(256), 0, c->stream, a, x);
+    MCHK(hipLaunchKernel(c->locate.fn, dim3((unsigned)blocks), dim3(256), kargs, 0, c->stream));
     MCHK(hipGetLastError());
     MCHK(hipEventRecord(c->ev1, c->stream));
     o.res.resize(np);
@@ -1671,7 +1476,7 @@ int long_group(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, con
     t_fill_ms += ms;
     t_locate_ms += ms;
     st.blocks = (int)blocks;
-    st.waves_per_cu = 4 * c->wgs[5];
+    st.waves_per_cu = 4 * c->locate.wgs;
     st.boundary_bytes = std::max(st.boundary_bytes, (long long)ckpt_total);
 
     // every walk starts at its end cell in state H; a pair without an alignment never walks
@@ -1727,7 +1532,7 @@ int long_group(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, con
             }
             std::stable_sort(items.begin(), items.end(), [](const StripItem& p, const StripItem& q) { return p.rows > q.rows; });
             const size_t ni = items.size();
-            if (long_blocks(c, 6, (const void*)sw_matrix_strip_kernel, ni, &blocks)) return -1;
+            if (fill_blocks(c, c->strip, ni, 0, &blocks)) return -1;
             if (ensure(c, B_ITEMS, ni * sizeof(StripItem)) || ensure(c, B_TRACE, (size_t)trace_total)) return -1;
             MCHK(hipMemcpyAsync(c->buf[B_ITEMS], items.data(), ni * sizeof(StripItem), hipMemcpyHostToDevice, c->stream));
             MCHK(hipMemsetAsync(c->buf[B_CTRL], 0, sizeof(Ctrl), c->stream));
@@ -1737,7 +1542,7 @@ int long_group(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, con
             x.trace = (unsigned char*)c->buf[B_TRACE];
             WalkStripArgs w{x.items, x.trace, (unsigned char*)c->buf[B_OPS], (WalkState*)c->buf[B_STATE], (int)ni};
             MCHK(hipEventRecord(c->ev0, c->stream));
-            hipLaunchKernelGGL(sw_matrix_strip_kernel, dim3((unsigned)blocks), dim3(256), 0, c->stream, a, x);
+            MCHK(hipLaunchKernel(c->strip.fn, dim3((unsigned)blocks), dim3(256), kargs, 0, c->stream));
             MCHK(hipGetLastError());
             MCHK(hipEventRecord(c->ev1, c->stream));
             hipLaunchKernelGGL(sw_matrix_walk_strip_kernel, dim3((unsigned)((ni + 63) / 64)), dim3(64), 0, c->stream, w);
@@ -1752,7 +1557,7 @@ int long_group(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, con
             t_walk_ms += wk;
             st.variant += 1;
             st.blocks = (int)blocks;
-            st.waves_per_cu = 4 * c->wgs[6];
+            st.waves_per_cu = 4 * c->strip.wgs;
             st.boundary_bytes = std::max(st.boundary_bytes, (long long)(ckpt_total + trace_total));
             for (const StripItem& it : items) {   // an error stops the call; a walk that goes on stands in the strip on the left
                 const WalkState& s = o.ws[(size_t)it.slot];
@@ -1903,7 +1708,7 @@ int matrix_align_device(const sw_matrix* mx, const unsigned char* d_arena, const
             if (launch_traced(c, mx, d_arena, act, gap_init, gap_ext, o, amode, band)) return -1;
             st.variant += 1;
             st.blocks = o.blocks;
-            st.waves_per_cu = 4 * c->wgs[banded ? band_wgs_slot(4, amode) : wgs_slot(4, amode)];
+            st.waves_per_cu = 4 * c->fill[banded][amode][WI_TRACED].wgs;
             st.boundary_bytes = std::max(st.boundary_bytes, o.trace_total);
         }
         size_t s = 0;
