@@ -25,7 +25,7 @@ __all__ = [
     "SwError", "LIB_PATH", "SW_FLAG_DNA", "SW_FLAG_BYTES", "slab_bounds", "SlabBuffer", "slab_alloc",
     "ipc_open", "ipc_close", "score_slab_device", "Database", "Matrix", "score_matrix", "score_matrix_batch",
     "SW_MATRIX_FOLD_CASE", "Alignment", "align_matrix", "align_matrix_batch", "last_align_ms",
-    "align_matrix_long", "align_long_plan", "last_align_long_ms",
+    "align_matrix_long", "align_long_plan", "last_align_long_ms", "coop_plan",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -67,6 +67,11 @@ class _AlignPlan(ctypes.Structure):
 class _BandPlan(ctypes.Structure):
     _fields_ = [("dlo", ctypes.c_longlong), ("dhi", ctypes.c_longlong), ("cells", ctypes.c_longlong),
                 ("trace_bytes", ctypes.c_longlong), ("full_trace_bytes", ctypes.c_longlong)]
+
+
+class _CoopPlan(ctypes.Structure):
+    _fields_ = [("W", ctypes.c_int), ("strips", ctypes.c_int), ("swap", ctypes.c_int), ("edge_bytes", ctypes.c_longlong),
+                ("items", ctypes.c_longlong)]
 
 
 _lib = None
@@ -255,6 +260,12 @@ def lib() -> ctypes.CDLL:
             f.restype = i
         L.sw_band_plan.argtypes = [i, i, i, ctypes.POINTER(_BandPlan)]
         L.sw_band_plan.restype = i
+    if hasattr(L, "sw_score_matrix_batch_coop"):   # one pair's strips on many waves (include/algoGPU.h)
+        L.sw_score_matrix_batch_coop.argtypes = [vp, ctypes.POINTER(u8p), ctypes.POINTER(i), ctypes.POINTER(u8p),
+                                                 ctypes.POINTER(i), i, i, i, i, ctypes.POINTER(i)]
+        L.sw_score_matrix_batch_coop.restype = i
+        L.sw_matrix_coop_plan.argtypes = [i, i, i, ctypes.POINTER(_CoopPlan)]
+        L.sw_matrix_coop_plan.restype = i
     _lib = L
     return L
 
@@ -589,24 +600,32 @@ def _band(band) -> int:
 
 
 def score_matrix(seq1, seq2, matrix: Matrix, gap_init: int, gap_ext: int, mode: str = "local",
-                 band: int | None = None) -> int:
+                 band: int | None = None, coop: bool = False) -> int:
     """Best local-alignment score under ``matrix``; a gap of L residues costs gap_init + (L-1)*gap_ext
     (BLAST's "open 11, extend 1" is gap_init=12, gap_ext=1).  ``mode="global"`` / ``"semiglobal"``:
     the end-to-end / query-inside-record score (include/algoGPU.h SW_MODE_*), which may be negative.
-    ``band``: see :func:`score_matrix_batch`."""
-    if _mode(mode) != SW_MODE_LOCAL or band is not None:
-        return score_matrix_batch([(seq1, seq2)], matrix, gap_init, gap_ext, mode=mode, band=band)[0]
+    ``band`` and ``coop``: see :func:`score_matrix_batch`."""
+    if _mode(mode) != SW_MODE_LOCAL or band is not None or coop:
+        return score_matrix_batch([(seq1, seq2)], matrix, gap_init, gap_ext, mode=mode, band=band, coop=coop)[0]
     a, b = _u8(seq1), _u8(seq2)
     return _check(lib().sw_score_matrix(matrix._handle(), _ptr(a), _ptr(b), len(a), len(b), int(gap_init), int(gap_ext)))
 
 
 def score_matrix_batch(pairs: Iterable[Sequence], matrix: Matrix, gap_init: int, gap_ext: int, mode: str = "local",
-                       band: int | None = None) -> list:
+                       band: int | None = None, coop: bool = False) -> list:
     """Scores of many independent pairs under ``matrix`` in one launch (sw_score_matrix_batch; with
     ``mode`` "global" or "semiglobal" sw_score_matrix_batch_mode: one launch is one mode).
     ``band=B`` (sw_score_matrix_batch_band, any mode): only the cells (i, j) of a pair with
-    min(0, m - n) - B <= j - i <= max(0, m - n) + B exist (include/algoGPU.h; :func:`band_plan`)."""
+    min(0, m - n) - B <= j - i <= max(0, m - n) + B exist (include/algoGPU.h; :func:`band_plan`).
+    ``coop=True`` (sw_score_matrix_batch_coop, any mode, no band): the same scores with the strips of
+    every pair on as many waves as it has strips, for one or a few long pairs (:func:`coop_plan`)."""
     am = _mode(mode)
+    if coop:
+        if band is not None:
+            raise ValueError("band= is not built for coop=True (the cooperative score path)")
+        if not isinstance(matrix, Matrix):
+            raise ValueError("coop=True needs a substitution matrix (Matrix.equality gives equality scoring as one)")
+        return _score_matrix_batch(pairs, matrix, gap_init, gap_ext, am, coop=True)
     if band is not None:
         if not isinstance(matrix, Matrix):
             raise ValueError("band= needs a substitution matrix (Matrix.equality gives equality scoring as one)")
@@ -616,9 +635,9 @@ def score_matrix_batch(pairs: Iterable[Sequence], matrix: Matrix, gap_init: int,
     return _score_matrix_batch(pairs, matrix, gap_init, gap_ext, am if am != SW_MODE_LOCAL else None)
 
 
-def _score_matrix_batch(pairs, matrix, gap_init: int, gap_ext: int, am, band=None) -> list:
+def _score_matrix_batch(pairs, matrix, gap_init: int, gap_ext: int, am, band=None, coop=False) -> list:
     """am None: sw_score_matrix_batch; else sw_score_matrix_batch_mode with that SW_MODE_* value, or with
-    a band sw_score_matrix_batch_band."""
+    a band sw_score_matrix_batch_band, or (coop) sw_score_matrix_batch_coop."""
     arrs = [(_u8(a), _u8(b)) for a, b in pairs]
     n = len(arrs)
     if n == 0:
@@ -629,7 +648,9 @@ def _score_matrix_batch(pairs, matrix, gap_init: int, gap_ext: int, am, band=Non
     AL = (ctypes.c_int * n)(*[len(x) for x, _ in arrs])
     BL = (ctypes.c_int * n)(*[len(y) for _, y in arrs])
     out = (ctypes.c_int * n)()
-    if band is not None:
+    if coop:
+        _check(lib().sw_score_matrix_batch_coop(matrix._handle(), A, AL, B, BL, n, int(gap_init), int(gap_ext), am, out))
+    elif band is not None:
         _check(lib().sw_score_matrix_batch_band(matrix._handle(), A, AL, B, BL, n, int(gap_init), int(gap_ext), am, band, out))
     elif am is not None:
         _check(lib().sw_score_matrix_batch_mode(matrix._handle(), A, AL, B, BL, n, int(gap_init), int(gap_ext), am, out))
@@ -803,6 +824,15 @@ def band_plan(n: int, m: int, band: int) -> dict:
     _check(lib().sw_band_plan(int(n), int(m), _band(band), ctypes.byref(p)))
     return {"dlo": p.dlo, "dhi": p.dhi, "cells": p.cells, "trace_bytes": p.trace_bytes,
             "full_trace_bytes": p.full_trace_bytes}
+
+
+def coop_plan(n: int, m: int, mode: str = "local") -> dict:
+    """What ``score_matrix(..., coop=True)`` would choose for one n x m pair under the current options
+    (sw_matrix_coop_plan, no GPU call): ``W``, ``strips``, ``swap`` (seq2 across the lanes),
+    ``edge_bytes`` and ``items``.  Raises :class:`SwError` when the pair would be refused."""
+    p = _CoopPlan()
+    _check(lib().sw_matrix_coop_plan(int(n), int(m), _mode(mode), ctypes.byref(p)))
+    return {"W": p.W, "strips": p.strips, "swap": p.swap, "edge_bytes": p.edge_bytes, "items": p.items}
 
 
 def last_align_ms() -> tuple:

@@ -134,9 +134,18 @@ bool opt_pow2_ok(long long v) { return (v & (v - 1)) == 0; }
     X(slab_plain, 0, 0, 1, nullptr, false)                                                                            \
     /* tests only: flow2's compute waves skip this item (-1 = none) */                                                \
     X(stall_item, -1, -1, ANY_HI, nullptr, false)
+// The keys of one entry point, sw_score_matrix_batch_coop (sw_matrix.hip), set and read like the ones above but
+// documented with that entry point and not listed by sw_option_name, whose list is the "Tuning knobs" of the header.
+#define SW_OPTIONS_COOP(X)                                                                                            \
+    /* MiB of edge columns a cooperative matrix launch may hold */                                                    \
+    X(coop_mb, 1024, 1, 3072, nullptr, false)                                                                         \
+    /* 1: the edge columns are filled with 0x3F bytes before every cooperative launch (tests) */                      \
+    X(coop_poison, 0, 0, 1, nullptr, false)
 
 #define X(key, def, lo, hi, ok, flag) O_##key,
-enum Opt : int { SW_OPTIONS(X) OPT_COUNT };
+// OPT_COUNT: the listed keys; the rows of SW_OPTIONS_COOP follow them (OPT_REWIND_ puts the count back by one, so
+// that the first of them takes the value OPT_COUNT); OPT_ALL: every row
+enum Opt : int { SW_OPTIONS(X) OPT_COUNT, OPT_REWIND_ = OPT_COUNT - 1, SW_OPTIONS_COOP(X) OPT_ALL };
 #undef X
 struct OptRow {
     const char* key;
@@ -145,10 +154,10 @@ struct OptRow {
     bool flag;
 };
 #define X(key, def, lo, hi, ok, flag) {#key, def, lo, hi, ok, flag},
-constexpr OptRow OPT_ROWS[OPT_COUNT] = {SW_OPTIONS(X)};
+constexpr OptRow OPT_ROWS[OPT_ALL] = {SW_OPTIONS(X) SW_OPTIONS_COOP(X)};
 #undef X
 #define X(key, def, lo, hi, ok, flag) {def},
-std::atomic<long long> g_opt[OPT_COUNT] = {SW_OPTIONS(X)};
+std::atomic<long long> g_opt[OPT_ALL] = {SW_OPTIONS(X) SW_OPTIONS_COOP(X)};
 #undef X
 
 // The options as one call sees them: every entry point that plans or launches takes one snapshot and
@@ -187,7 +196,7 @@ Opts snapshot_opts() {
     return o;
 }
 int find_opt(const char* key) {
-    for (int i = 0; i < OPT_COUNT; ++i)
+    for (int i = 0; i < OPT_ALL; ++i)
         if (std::strcmp(key, OPT_ROWS[i].key) == 0) return i;
     return -1;
 }

@@ -52,6 +52,11 @@
 //
 // Every fill kernel is the same claim loop (matrix_stage, matrix_claim, matrix_claimed_pair) around matrix_pair, and
 // the host names each instantiation once (MatCtx::fill).
+//
+// THE COOPERATIVE SCORE PATH (include/algoGPU.h sw_score_matrix_batch_coop) is the one
+// exception to "one wave owns one pair" and to "no wave waits for another": its kernels, sw_matrix_coop_kernel<W, AM>,
+// claim one strip of a pair at a time, and the wave of strip s + 1 follows the wave of strip s through the pair's edge
+// columns with a bounded poll (option "timeout").  Opt-in, score-only, no band (COOPERATIVE SCORE below).
 #include "sw_device.h"
 #include "sw_matrix_host.h"
 #include "../../include/algoGPU.h"
@@ -949,9 +954,190 @@ __global__ void __launch_bounds__(64) sw_matrix_walk_strip_kernel(WalkStripArgs 
     *static_cast<Walk*>(st) = s;
 }
 
+// ---- COOPERATIVE SCORE: the strips of one pair on as many waves (sw_score_matrix_batch_coop) -----
+//
+// DESIGN.md section 16.  A work item is one strip of one pair, numbered pair-major and strip-minor,
+// and the waves claim items strictly in order (matrix_claim).  The wave that holds strip s stores its
+// right edge to edge column s of the pair -- a column of its own, m rows of 8 bytes {H - G_INIT,
+// E - G_EXT}, the layout of the locate pass's checkpoints -- and the wave that holds strip s + 1 reads
+// that column as its inflow while strip s is still running.  A column is written once and read once in
+// a launch and never reused.  One 32-bit progress word an item says how many rows of the item's
+// right edge are stored: after the stores of a chunk the producer drains them (s_waitcnt vmcnt(0); the
+// stores are sc1, write-through) and one lane publishes the count with an sc1 store (what a relaxed
+// agent-scope atomic store is on gfx950: cdna_hip_programming.md Guideline 16, form R1); the consumer polls
+// its left neighbour's word, relaxed, until the rows of its next fetch are covered, then fences
+// (acquire, agent scope) and fetches.  The words are zeroed by the host before every launch.
+// Score-only, no band; the step (MStrip) is the one of every other fill kernel.
+
+struct CoopPair {           // per pair, beside its MatPair
+    uint64_t edge_off;      // bytes, from CoopArgs::edge: edge column 0 of the pair
+    unsigned stride;        // bytes a column: m * 8
+    int strips;
+};
+struct CoopItem {
+    int pair, strip;
+};
+struct CoopArgs {
+    const CoopPair* cp;
+    const CoopItem* items;      // MatArgs::npairs of them
+    unsigned char* edge;
+    unsigned* progress;         // a word an item: rows [0, r) of the item's right edge are stored
+    long long timeout_ticks;    // s_memrealtime ticks (100 MHz) before a poll gives up
+};
+
+// The slow path of the consumer's poll, out of line as await_slow (sw_device.h) and for its reason.
+// Polls the word at byte woff of the progress block until it is at least `need`: the rows published,
+// or -1 when the launch has failed -- another wave's poll has given up (Ctrl::error is set), or this
+// one's deadline has passed (it sets ERR_TIMEOUT and the item; every lane adds the same bits, so no
+// branch on the lane).  Relaxed sc1 loads, a sleep between polls.
+__device__ __noinline__ int coop_await(__amdgpu_buffer_rsrc_t prog_rsrc, __amdgpu_buffer_rsrc_t ctrl_rsrc, const unsigned woff,
+                                       const unsigned need, const long long timeout_ticks, Ctrl* ctrl, const unsigned item) {
+    SpinDeadline dl((long long)__builtin_amdgcn_s_memrealtime(), timeout_ticks);
+    for (;;) {
+        __builtin_amdgcn_s_sleep(SW_SPIN_SLEEP);
+        const unsigned r = __builtin_amdgcn_readfirstlane(__builtin_amdgcn_raw_buffer_load_b32(prog_rsrc, woff, 0, AUX_SC1));
+        if (r >= need) return (int)r;
+        const unsigned e = __builtin_amdgcn_readfirstlane(
+            __builtin_amdgcn_raw_buffer_load_b32(ctrl_rsrc, (unsigned)offsetof(Ctrl, error), 0, AUX_SC1));
+        if (e != 0) return -1;
+        if (dl.expired()) {
+            atomicOr(&ctrl->error, ERR_TIMEOUT);
+            atomicMax(&ctrl->err_item, item);
+            return -1;
+        }
+    }
+}
+
+// One strip of one pair.  false: the launch has failed (coop_await) and the wave leaves.
+template <int W, int AM>
+__device__ __forceinline__ bool matrix_coop_strip(const MatArgs& a, const CoopArgs& x, const MatPair& pd, const CoopPair& cp,
+                                                  const unsigned item, const int strip, const int lane,
+                                                  const signed char* s_tab, const unsigned char* s_code) {
+    constexpr int SW = 64 * W, C = MAT_C;
+    const int m = pd.m;
+    const int go = a.gap_init, ge = a.gap_ext;
+    const bool l63 = lane == 63;
+    const bool has_in = strip > 0;
+    const bool has_out = strip < cp.strips - 1;
+    const __amdgpu_buffer_rsrc_t row_rsrc =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(a.seq + pd.row_off), 0, m, RSRC_FLAGS);
+    // a column that is not there (strip 0's left, the last strip's right) has no bytes
+    unsigned char* col0 = x.edge + cp.edge_off;
+    const __amdgpu_buffer_rsrc_t in_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+        col0 + (uint64_t)(has_in ? strip - 1 : 0) * cp.stride, 0, has_in ? (int)((unsigned)m * 8u) : 0, RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t out_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+        col0 + (uint64_t)(has_out ? strip : 0) * cp.stride, 0, has_out ? (int)((unsigned)m * 8u) : 0, RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t prog_rsrc =
+        __builtin_amdgcn_make_buffer_rsrc(x.progress, 0, (int)((unsigned)a.npairs * 4u), RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t ctrl_rsrc = __builtin_amdgcn_make_buffer_rsrc(a.ctrl, 0, (int)sizeof(Ctrl), RSRC_FLAGS);
+    const int nchunks = (m + SW - 1 + C - 1) / C;
+    unsigned toff = 0;
+    MStrip<W, M_SCORE, AM> S;
+    S.M = AM == AM_LOCAL ? 0 : MAT_NEG;
+    S.setup(a, pd, strip, lane, s_code);
+    // THE CONSUMER.  `seen` rows of the left edge are known to be stored (strip 0 has no left edge).
+    // Before the fetch of rows [k, k + 64) the word of item - 1 -- strip - 1 of this pair: items are
+    // pair-major, strip-minor -- must have reached min(m, k + 64).  A poll that has matched is followed
+    // by one agent-scope acquire: the edge loads are sc1, past the CU's cache, but each producing
+    // wave signals for itself, several workgroups share a CU and the loads are 8-B buffer loads, which
+    // is no row of the table of forms measured without the acquire, so it stays.
+    int seen = has_in ? 0 : m;
+    auto await_rows = [&](const int k) __attribute__((always_inline)) -> bool {
+        const int need = min(m, k + C);
+        if (seen >= need) return true;
+        const unsigned woff = (item - 1u) * 4u;
+        int r = (int)__builtin_amdgcn_readfirstlane(__builtin_amdgcn_raw_buffer_load_b32(prog_rsrc, woff, 0, AUX_SC1));
+        if (r < need)   // (a call's result arrives in a vector register: made uniform again)
+            r = __builtin_amdgcn_readfirstlane(coop_await(prog_rsrc, ctrl_rsrc, woff, (unsigned)need, x.timeout_ticks, a.ctrl, item));
+        if (r < 0) return false;
+        seen = r;
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        return true;
+    };
+    if (!await_rows(0)) return false;
+    unsigned raw_nxt = mat_fetch_raw(row_rsrc, 0, lane, m);
+    u32x2 g_nxt = has_in ? mat_fetch_edge(in_rsrc, 0, lane, m) : u32x2{0u, 0u};
+    for (int c = 0; c < nchunks; ++c) {
+        const int k0 = c * C;
+        const unsigned raw = raw_nxt;
+        const u32x2 g = g_nxt;
+        // the next chunk's rows in flight while this chunk computes
+        if (k0 + C < m && !await_rows(k0 + C)) return false;
+        raw_nxt = mat_fetch_raw(row_rsrc, k0 + C, lane, m);
+        if (has_in) g_nxt = mat_fetch_edge(in_rsrc, k0 + C, lane, m);
+        const bool live = k0 + lane < m;
+        S.IOR = live ? (int)s_code[raw & 0xFFu] : a.k;
+        if constexpr (AM == AM_LOCAL) {
+            S.IOH = has_in && live ? (int)g.x : -go;
+            S.IOE = has_in && live ? (int)g.y : -ge;
+        } else {   // strip 0: the left border H[-1][j], and no E to extend out of it
+            const int lb = AM == AM_GLOBAL ? -(go + (k0 + lane) * min(go, ge)) - go : -go;
+            S.IOH = has_in && live ? (int)g.x : lb;
+            S.IOE = has_in && live ? (int)g.y : MAT_NEG;
+        }
+        S.run(l63, go, ge, s_tab, row_rsrc, toff);
+        // THE PRODUCER.  Lane l holds the right edge of row k0 + l - (SW - 1): after this chunk's
+        // stores rows [0, k0 + 65 - SW) are stored, all m of them after the last chunk (k0 + 64 >=
+        // m + SW - 1 there).  The count is published once the stores have left the wave's queue, by
+        // lane 0 through a store that is out of range on every other lane (no branch on the lane:
+        // the comment at matrix_pair's score store).
+        const int pub = min(m, k0 + C + 1 - SW);
+        if (has_out && pub > 0) {
+            const int row_out = k0 + lane - (SW - 1);
+            const bool st = row_out >= 0 && row_out < m;
+            __builtin_amdgcn_raw_buffer_store_b64(u32x2{(unsigned)S.IOH, (unsigned)S.IOE}, out_rsrc,
+                                                  st ? (unsigned)row_out * 8u : OOR, 0, AUX_SC1);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __builtin_amdgcn_raw_buffer_store_b32((unsigned)pub, prog_rsrc, lane == 0 ? item * 4u : OOR, 0, AUX_SC1);
+        }
+    }
+    int M = S.M;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) M = max(M, __shfl_xor(M, off));
+    if constexpr (AM == AM_LOCAL) {
+        // every strip's maximum into the pair's score word, which the host has zeroed; every lane
+        // offers the same value (no branch on the lane)
+        atomicMax(a.scores + pd.out_idx, M);
+    } else {   // the last strip alone holds the end cell / the last column; M is H - G_INIT
+        const __amdgpu_buffer_rsrc_t sc_rsrc =
+            __builtin_amdgcn_make_buffer_rsrc(a.scores, 0, (int)((unsigned)a.nscores * 4u), RSRC_FLAGS);
+        __builtin_amdgcn_raw_buffer_store_b32(M + go, sc_rsrc, lane == 0 && !has_out ? (unsigned)pd.out_idx * 4u : OOR, 0, 0);
+    }
+    return true;
+}
+
+// PROGRESS, for any grid.  Claim: every claimed item finishes or the launch fails within the poll's
+// deadline.  Items are claimed in order from one counter, and a wave claims its next item only after
+// finishing the one it holds.  Item i = (pair, strip s) waits only for item i - 1 = (pair, s - 1),
+// and only if s > 0.  Item i - 1 was claimed before item i, so by a wave that is already running: it
+// holds i - 1 now or has finished it.  By induction over i, item i - 1 finishes (strip 0, and item 0,
+// wait for nothing), publishing all m rows on the way, so every poll of item i is answered.  Nothing
+// here asks two waves to be resident together, a dispatch order or a placement: a grid of one
+// workgroup works through 20 strips four at a time.
+template <int W, int AM>
+__global__ void __launch_bounds__(256) sw_matrix_coop_kernel(MatArgs a, CoopArgs x) {
+    const MatLds s = matrix_stage(a);
+    const int lane = threadIdx.x & 63;
+    unsigned item;
+    MatPair pd;
+    WalkPair wp;
+    while (matrix_claim(a, lane, item)) {
+        const CoopItem iraw = x.items[item];
+        const int pair = __builtin_amdgcn_readfirstlane(iraw.pair);
+        const int strip = __builtin_amdgcn_readfirstlane(iraw.strip);
+        matrix_claimed_pair<false>(a, (unsigned)pair, pd, wp);
+        const CoopPair craw = x.cp[pair];
+        CoopPair cp;
+        cp.edge_off = uniform64(craw.edge_off);
+        cp.stride = __builtin_amdgcn_readfirstlane(craw.stride);
+        cp.strips = __builtin_amdgcn_readfirstlane(craw.strips);
+        if (!matrix_coop_strip<W, AM>(a, x, pd, cp, item, strip, lane, s.tab, s.code)) return;
+    }
+}
+
 // ---- host ------------------------------------------------------------------------------------
 
-#define MCHK(expr)                                                                           \
+#define MCHK(expr)                                                                          \
     do {                                                                                     \
         hipError_t e_ = (expr);                                                              \
         if (e_ != hipSuccess) {                                                              \
@@ -979,11 +1165,20 @@ void name_fill_kernels(FillKernel (&row)[5]) {
     row[WI_TRACED].fn = (const void*)sw_matrix_kernel<TRACE_W, true, AM, BAND>;
 }
 
+template <int AM>
+void name_coop_kernels(FillKernel (&row)[4]) {   // the cooperative score kernels at W_OF
+    row[0].fn = (const void*)sw_matrix_coop_kernel<1, AM>;
+    row[1].fn = (const void*)sw_matrix_coop_kernel<2, AM>;
+    row[2].fn = (const void*)sw_matrix_coop_kernel<4, AM>;
+    row[3].fn = (const void*)sw_matrix_coop_kernel<8, AM>;
+}
+
 // device memory and a stream per (thread, device), as the engine's own context (sw_engine.hip)
 enum {
     B_PAIRS = 0, B_CTRL, B_SCRATCH, B_ARENA, B_SCORES,   // every launch
     B_WALK, B_TRACE, B_RES, B_OPS,                       // traced launches: walk pairs, trace, results, operations
     B_LONG, B_CKPT, B_ITEMS, B_STATE,                    // long pairs: locate items, checkpoints, strip items, walk states
+    B_CPAIRS, B_CITEMS, B_EDGE, B_PROGRESS,              // cooperative score: pairs, items, edge columns, progress words
     B_COUNT
 };
 struct MatCtx {
@@ -994,7 +1189,11 @@ struct MatCtx {
     size_t cap[B_COUNT] = {};
     FillKernel fill[2][3][5];   // [band][SW_MODE_*][index into W_OF, or WI_TRACED]
     FillKernel locate{(const void*)sw_matrix_locate_kernel}, strip{(const void*)sw_matrix_strip_kernel};
+    FillKernel coop[3][4];      // [SW_MODE_*][index into W_OF]
     MatCtx() {
+        name_coop_kernels<AM_LOCAL>(coop[AM_LOCAL]);
+        name_coop_kernels<AM_GLOBAL>(coop[AM_GLOBAL]);
+        name_coop_kernels<AM_SEMI>(coop[AM_SEMI]);
         name_fill_kernels<AM_LOCAL, false>(fill[0][AM_LOCAL]);
         name_fill_kernels<AM_GLOBAL, false>(fill[0][AM_GLOBAL]);
         name_fill_kernels<AM_SEMI, false>(fill[0][AM_SEMI]);
@@ -1263,6 +1462,192 @@ int launch(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, std::ve
     return 0;
 }
 
+// ---- the cooperative score path, host side (COOPERATIVE SCORE above) ----
+
+constexpr int MODE_MATRIX_COOP = 11;
+// Nanoseconds of a step by index into W_OF, measured (a global 32768 x 32768 pair, one
+// wave a SIMD).  A lone wave's step is bound by its dependent chain -- the table lookup, the DPP moves, the
+// maxima -- not by its instruction count (section 13's table: 22.75 / 34.75 / 56.25 / 103.25), so the
+// counts overrate the cost of W = 2 and put the automatic W one notch too low at every N measured.
+constexpr int COOP_STEP_NS[4] = {93, 106, 147, 263};
+
+// One pair at one W: which sequence lies across the lanes, and what that costs.  The last strip is
+// done after about m + strips * 64 * (W + 1) steps: its own m + 64 * W, and every hand-off before it
+// starts it 64 * (W + 1) steps after its left neighbour (the first 64 rows of an edge are stored
+// W chunks into a strip, and a chunk is fetched one chunk ahead).  The edge columns, (strips - 1)
+// of m rows of 8 bytes, must fit the budget.  Semi-global keeps seq1 across the lanes; local and
+// global take the cheaper orientation that fits (the plain one on a tie), or the one option "orient"
+// names (1: seq1 across the lanes, 2: seq2).
+struct CoopShape {
+    int swap;
+    long long strips, edge_bytes, cost;
+};
+bool coop_shape(long long alen, long long blen, int amode, int wi, long long budget, CoopShape& out, long long* least) {
+    const long long SW = 64LL * W_OF[wi];
+    const long long orient = amode == AM_SEMI ? 1 : sw_get_option("orient");
+    bool found = false;
+    for (int swap = 0; swap < 2; ++swap) {
+        if ((orient == 1 && swap) || (orient == 2 && !swap)) continue;
+        const long long n = swap ? blen : alen, m = swap ? alen : blen;
+        CoopShape s;
+        s.swap = swap;
+        s.strips = (n + SW - 1) / SW;
+        s.edge_bytes = (s.strips - 1) * m * 8;
+        s.cost = (m + s.strips * 64 * (W_OF[wi] + 1)) * COOP_STEP_NS[wi];
+        if (least && (*least < 0 || s.edge_bytes < *least)) *least = s.edge_bytes;
+        if (s.edge_bytes > budget) continue;
+        if (!found || s.cost < out.cost) out = s;
+        found = true;
+    }
+    return found;
+}
+
+// The W of a launch over pairs (alen[k], blen[k]) with both lengths > 0: the cheapest estimate among
+// the W at which every pair fits the budget (option "W" forces one).  A pair's bytes fall with W, so
+// a pair that fits no allowed W does not fit the largest: it is refused with the bytes it needs there.
+int coop_choose_w(const int* alen, const int* blen, int npairs, int amode, long long budget, const char* what) {
+    const long long forced = sw_get_option("W");
+    int wi = -1;
+    long long best = -1;
+    for (int k = 0; k < 4; ++k) {
+        if (forced > 0 && W_OF[k] != forced) continue;
+        long long cost = 0;
+        bool fits = true;
+        for (int p = 0; p < npairs && fits; ++p) {
+            if (alen[p] == 0 || blen[p] == 0) continue;
+            CoopShape s;
+            fits = coop_shape(alen[p], blen[p], amode, k, budget, s, nullptr);
+            if (fits) cost += s.cost;
+        }
+        if (fits && (best < 0 || cost < best)) {
+            best = cost;
+            wi = k;
+        }
+    }
+    if (wi >= 0) return wi;
+    const int kmax = forced > 0 ? (forced == 1 ? 0 : forced == 2 ? 1 : forced == 4 ? 2 : 3) : 3;
+    for (int p = 0; p < npairs; ++p) {
+        if (alen[p] == 0 || blen[p] == 0) continue;
+        CoopShape s;
+        long long least = -1;
+        if (coop_shape(alen[p], blen[p], amode, kmax, budget, s, &least)) continue;
+        char m[320];
+        std::snprintf(m, sizeof m,
+                      "%s %d: a %d x %d pair needs %lld bytes of edge columns on the cooperative path at W = %d, more than "
+                      "option coop_mb = %lld MiB (edge columns are not recycled inside a launch)",
+                      what, p, alen[p], blen[p], least, W_OF[kmax], budget >> 20);
+        report_error(m);
+        break;
+    }
+    return -1;
+}
+
+// One cooperative launch: act (both lengths > 0, idx = the slot of d_scores, which the caller has
+// zeroed), every pair at W_OF[wi] in the orientation coop_shape gives.
+int launch_coop(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, const std::vector<DevSeq>& act, int wi,
+                long long budget, int gap_init, int gap_ext, int* d_scores, int nscores, int amode, sw_stats& st) {
+    const std::vector<int> order = longest_first(act);
+    std::vector<MatPair> pairs(act.size());
+    std::vector<CoopPair> cp(act.size());
+    std::vector<CoopItem> items;
+    uint64_t edge_total = 0;
+    for (size_t k = 0; k < act.size(); ++k) {
+        const DevSeq& p = act[(size_t)order[k]];
+        CoopShape s;
+        if (!coop_shape(p.alen, p.blen, amode, wi, budget, s, nullptr)) {
+            report_error("sw_score_matrix_batch_coop: a pair of the launch does not fit its plan");
+            return -1;
+        }
+        pairs[k] = make_pair(p, p.idx, s.swap != 0, -1);
+        cp[k] = CoopPair{edge_total, (unsigned)((unsigned long long)pairs[k].m * 8u), (int)s.strips};
+        edge_total += (uint64_t)s.edge_bytes;
+        for (int q = 0; q < (int)s.strips; ++q) items.push_back(CoopItem{(int)k, q});
+        st.cells += (long long)p.alen * p.blen;
+    }
+    const size_t ni = items.size();
+    const size_t prog_bytes = (ni * 4 + 15) / 16 * 16;   // a block of its own, whole 16 bytes, zeroed as a whole
+    FillKernel& kern = c->coop[amode][wi];
+    long long blocks = 0;
+    MatArgs a{};
+    if (fill_blocks(c, kern, ni, 0, &blocks) || fill_args(c, mx, d_arena, pairs, nscores, gap_init, gap_ext, 0, blocks, a) ||
+        ensure(c, B_CPAIRS, cp.size() * sizeof(CoopPair)) || ensure(c, B_CITEMS, ni * sizeof(CoopItem)) ||
+        ensure(c, B_EDGE, (size_t)edge_total) || ensure(c, B_PROGRESS, prog_bytes))
+        return -1;
+    a.scores = d_scores;
+    a.npairs = (int)ni;   // what the waves claim
+    MCHK(hipMemcpyAsync(c->buf[B_CPAIRS], cp.data(), cp.size() * sizeof(CoopPair), hipMemcpyHostToDevice, c->stream));
+    MCHK(hipMemcpyAsync(c->buf[B_CITEMS], items.data(), ni * sizeof(CoopItem), hipMemcpyHostToDevice, c->stream));
+    MCHK(hipMemsetAsync(c->buf[B_PROGRESS], 0, prog_bytes, c->stream));
+    // option "coop_poison": a row consumed before it was stored then carries H of about 10^9
+    if (sw_get_option("coop_poison") && edge_total) MCHK(hipMemsetAsync(c->buf[B_EDGE], 0x3F, (size_t)edge_total, c->stream));
+    CoopArgs x{};
+    x.cp = (const CoopPair*)c->buf[B_CPAIRS];
+    x.items = (const CoopItem*)c->buf[B_CITEMS];
+    x.edge = (unsigned char*)c->buf[B_EDGE];
+    x.progress = (unsigned*)c->buf[B_PROGRESS];
+    x.timeout_ticks = sw_get_option("timeout") * 100000000LL;   // s_memrealtime: 100 MHz
+    void* kargs[] = {&a, &x};
+    MCHK(hipEventRecord(c->ev0, c->stream));
+    MCHK(hipLaunchKernel(kern.fn, dim3((unsigned)blocks), dim3(256), kargs, 0, c->stream));
+    MCHK(hipGetLastError());
+    MCHK(hipEventRecord(c->ev1, c->stream));
+    Ctrl ctrl{};
+    MCHK(hipMemcpyAsync(&ctrl, c->buf[B_CTRL], sizeof ctrl, hipMemcpyDeviceToHost, c->stream));
+    MCHK(hipStreamSynchronize(c->stream));
+    float ms = 0.f;
+    MCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    st.kernel_ms += ms;
+    st.items += (int)ni;
+    st.blocks = (int)blocks;
+    st.waves_per_cu = 4 * kern.wgs;
+    st.boundary_bytes = std::max(st.boundary_bytes, (long long)edge_total);
+    if (ctrl.error != 0) {
+        const unsigned it = std::min<unsigned>(ctrl.err_item, (unsigned)ni - 1);
+        char m[256];
+        std::snprintf(m, sizeof m,
+                      "sw_score_matrix_batch_coop: item %u (pair %d, strip %d of %d) waited longer than option timeout = %lld s "
+                      "for the strip on its left (error bits 0x%x)",
+                      it, pairs[(size_t)items[it].pair].out_idx, items[it].strip, cp[(size_t)items[it].pair].strips,
+                      (long long)sw_get_option("timeout"), ctrl.error);
+        report_error(m);
+        return -1;
+    }
+    return 0;
+}
+
+// act: the pairs of the call with both lengths > 0, in input order (idx = the input index), at the
+// call's W (coop_choose_w under `budget`, the bytes of option "coop_mb"); the pairs packed in input
+// order into launches of at most `budget` bytes of edge columns.
+int score_coop(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, const std::vector<DevSeq>& act, int wi,
+               long long budget, int gap_init, int gap_ext, int* d_scores, int nscores, int amode) {
+    const auto t0 = std::chrono::steady_clock::now();
+    sw_stats st{};
+    st.mode = MODE_MATRIX_COOP;
+    st.variant = amode;
+    st.C = MAT_C;
+    st.W = W_OF[wi];
+    MCHK(hipMemsetAsync(d_scores, 0, (size_t)std::max(nscores, 1) * sizeof(int), c->stream));
+    std::vector<long long> need(act.size());
+    for (size_t k = 0; k < act.size(); ++k) {
+        CoopShape s{};
+        coop_shape(act[k].alen, act[k].blen, amode, wi, budget, s, nullptr);
+        need[k] = s.edge_bytes;
+    }
+    std::vector<int> ends;
+    align_pack(need.data(), (int)act.size(), budget, ends);
+    int lo = 0;
+    for (const int hi : ends) {
+        const std::vector<DevSeq> part(act.begin() + lo, act.begin() + hi);
+        if (!part.empty() && launch_coop(c, mx, d_arena, part, wi, budget, gap_init, gap_ext, d_scores, nscores, amode, st))
+            return -1;
+        lo = hi;
+    }
+    MCHK(hipStreamSynchronize(c->stream));
+    st.total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    report_stats(st);
+    return 0;
+}
+
 // refused like check_range (sw_db.hip): the int32 engine's score range
 bool range_ok(const sw_matrix* mx, int alen, int blen, const char* what, int idx) {
     if ((long long)std::min(alen, blen) * std::max(mx->max_entry, 0) >= (1LL << 28)) {
@@ -1277,7 +1662,8 @@ bool range_ok(const sw_matrix* mx, int alen, int blen, const char* what, int idx
 constexpr long long MAT_MAX_SEQ = (1LL << 27) - 1;   // the engine's longest sequence (8-B rows in a 32-bit resource)
 
 int score_host(const sw_matrix* mx, const unsigned char* const* a, const int* alen, const unsigned char* const* b,
-               const int* blen, int npairs, int gap_init, int gap_ext, int* out, int amode = AM_LOCAL, int band = -1) {
+               const int* blen, int npairs, int gap_init, int gap_ext, int* out, int amode = AM_LOCAL, int band = -1,
+               bool coop = false) {
     if (!gaps_ok(gap_init, gap_ext)) return -1;
     size_t total = 0;
     for (int k = 0; k < npairs; ++k) {
@@ -1304,6 +1690,9 @@ int score_host(const sw_matrix* mx, const unsigned char* const* a, const int* al
         }
         total += ((size_t)alen[k] + 15) / 16 * 16 + ((size_t)blen[k] + 15) / 16 * 16;
     }
+    const long long coop_budget = coop ? sw_get_option("coop_mb") << 20 : 0;
+    int coop_wi = 0;   // refused before anything is launched
+    if (coop && (coop_wi = coop_choose_w(alen, blen, npairs, amode, coop_budget, "pair")) < 0) return -1;
     MatCtx* c = get_mctx();
     if (!c) return -1;
     std::vector<unsigned char> arena(total);
@@ -1325,8 +1714,10 @@ int score_host(const sw_matrix* mx, const unsigned char* const* a, const int* al
     }
     if (ensure(c, B_ARENA, total) || ensure(c, B_SCORES, (size_t)npairs * sizeof(int))) return -1;
     if (total) MCHK(hipMemcpyAsync(c->buf[B_ARENA], arena.data(), total, hipMemcpyHostToDevice, c->stream));
-    if (launch(c, mx, (const unsigned char*)c->buf[B_ARENA], act, gap_init, gap_ext, (int*)c->buf[B_SCORES], npairs, false,
-               amode, band))
+    if (coop ? score_coop(c, mx, (const unsigned char*)c->buf[B_ARENA], act, coop_wi, coop_budget, gap_init, gap_ext,
+                          (int*)c->buf[B_SCORES], npairs, amode)
+             : launch(c, mx, (const unsigned char*)c->buf[B_ARENA], act, gap_init, gap_ext, (int*)c->buf[B_SCORES], npairs, false,
+                      amode, band))
         return -1;
     MCHK(hipMemcpy(out, c->buf[B_SCORES], (size_t)npairs * sizeof(int), hipMemcpyDeviceToHost));
     if (amode != AM_LOCAL)   // empty sequences are answered on the host
@@ -1848,6 +2239,41 @@ int sw_score_matrix_batch_mode(const sw_matrix* mx, const unsigned char* const* 
     if (!mode_ok("sw_score_matrix_batch_mode", mode)) return -1;
     if (npairs == 0) return 0;
     return score_host(mx, a, alen, b, blen, npairs, gap_init, gap_ext, scores_out, mode);
+}
+
+int sw_score_matrix_batch_coop(const sw_matrix* mx, const unsigned char* const* a, const int* alen,
+                               const unsigned char* const* b, const int* blen, int npairs, int gap_init, int gap_ext,
+                               int mode, int* scores_out) {
+    if (!mx || npairs < 0 || (npairs > 0 && (!a || !alen || !b || !blen || !scores_out))) {
+        report_error("sw_score_matrix_batch_coop: invalid arguments");
+        return -1;
+    }
+    if (!mode_ok("sw_score_matrix_batch_coop", mode)) return -1;
+    if (npairs == 0) return 0;
+    return score_host(mx, a, alen, b, blen, npairs, gap_init, gap_ext, scores_out, mode, -1, true);
+}
+
+int sw_matrix_coop_plan(int n, int m, int mode, sw_coop_plan* out) {
+    if (n < 0 || m < 0 || n > MAT_MAX_SEQ || m > MAT_MAX_SEQ || !out) {
+        report_error("sw_matrix_coop_plan: invalid arguments");
+        return -1;
+    }
+    if (!mode_ok("sw_matrix_coop_plan", mode)) return -1;
+    sw_coop_plan p{0, 0, 0, 0, 0};
+    if (n > 0 && m > 0) {
+        const long long budget = sw_get_option("coop_mb") << 20;
+        const int wi = coop_choose_w(&n, &m, 1, mode, budget, "pair");
+        if (wi < 0) return -1;
+        CoopShape s{};
+        coop_shape(n, m, mode, wi, budget, s, nullptr);
+        p.W = W_OF[wi];
+        p.strips = (int)s.strips;
+        p.swap = s.swap;
+        p.edge_bytes = s.edge_bytes;
+        p.items = s.strips;
+    }
+    *out = p;
+    return 0;
 }
 
 int sw_align_matrix_batch_mode(const sw_matrix* mx, const unsigned char* const* a, const int* alen,

@@ -484,6 +484,48 @@ int  sw_align_matrix_cpu_band(const sw_matrix*, const unsigned char* const* a, c
                               unsigned* cigar, long long cigar_cap, long long* cigar_used);
 int  sw_band_plan(int n, int m, int band, sw_band_plan_t* out);
 
+/* ---- one long pair on many waves: the cooperative score path ----
+ *
+ * Every call above runs one pair on one wave.  sw_score_matrix_batch_coop runs the strips of a pair
+ * -- a strip is the 64 * W columns one wave sweeps top to bottom -- on as many waves as there are
+ * strips, each wave handing its strip's right edge to the wave on its right inside one launch.
+ * Scores only, no band; opt-in: no other call takes this path.
+ *
+ * sw_score_matrix_batch_coop: the arguments, checks, messages and return value of
+ *   sw_score_matrix_batch_mode, and the same scores bit for bit.  Semi-global lays seq1 across the
+ *   lanes; local and global lay a pair either way, by the estimate below, unless option "orient"
+ *   names one (1: seq1 across the lanes, 2: seq2).
+ *   W: option "W" when set; else, per call, the W with the smallest estimate of steps,
+ *   m + strips * 64 * (W + 1), times the measured time of a step at that W, among the W whose edge
+ *   columns fit.
+ *   MEMORY: a pair of more than one strip holds (strips - 1) * m * 8 bytes of edge columns (m: the
+ *   sequence that streams), every column written once and read once in a launch.  Columns are NOT
+ *   recycled through a ring inside a launch.  Option "coop_mb" (MiB, default 1024, 1 .. 3072) caps a
+ *   launch: a batch that does not fit runs as several launches, pairs packed in input order, and a
+ *   pair that does not fit alone at the largest W allowed is refused before anything is launched,
+ *   with a message that gives the bytes it needs.
+ *   A wave waits only for the strip on its left, which an earlier claim holds; the wait is bounded
+ *   by option "timeout", after which the call returns -1 and sw_last_error names the item (pair and
+ *   strip).
+ *   Option "coop_poison" (0 / 1, default 0; tests): the host fills the edge columns with 0x3F bytes
+ *   before every launch, so that a row consumed before it was stored carries H of about 10^9 into
+ *   the score.  Both options are set and read with sw_set_option / sw_get_option.
+ *   sw_last_stats: mode 11; W; items = the strips of all pairs; cells; boundary_bytes = the edge
+ *   bytes of the largest launch; variant = the alignment mode.
+ * sw_matrix_coop_plan: host arithmetic, no GPU call: what the call would choose for one n x m pair
+ *   under the current options.  -1 with the refusal's message where the call would refuse. */
+typedef struct {
+    int W;                  /* columns per lane */
+    int strips;             /* = waves the pair can use */
+    int swap;               /* 1: seq2 lies across the lanes */
+    long long edge_bytes;   /* (strips - 1) * rows * 8 */
+    long long items;        /* work items: strips */
+} sw_coop_plan;
+int  sw_score_matrix_batch_coop(const sw_matrix*, const unsigned char* const* a, const int* alen,
+                                const unsigned char* const* b, const int* blen, int npairs,
+                                int gap_init, int gap_ext, int mode, int* scores_out);
+int  sw_matrix_coop_plan(int n, int m, int mode, sw_coop_plan* out);
+
 /* Tuning knobs (process-wide).  Keys:
  *   "W"        columns per lane: 0 = auto, 1, 2, 4, 8
  *   "C"        rows per strip hand-off chunk: 0 = auto, 16, 32, 64
