@@ -25,7 +25,7 @@ __all__ = [
     "SwError", "LIB_PATH", "SW_FLAG_DNA", "SW_FLAG_BYTES", "slab_bounds", "SlabBuffer", "slab_alloc",
     "ipc_open", "ipc_close", "score_slab_device", "Database", "Matrix", "score_matrix", "score_matrix_batch",
     "SW_MATRIX_FOLD_CASE", "Alignment", "align_matrix", "align_matrix_batch", "last_align_ms",
-    "align_matrix_long", "align_long_plan", "last_align_long_ms", "coop_plan",
+    "align_matrix_long", "align_long_plan", "last_align_long_ms", "coop_plan", "align_long_coop_plan",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -72,6 +72,11 @@ class _BandPlan(ctypes.Structure):
 class _CoopPlan(ctypes.Structure):
     _fields_ = [("W", ctypes.c_int), ("strips", ctypes.c_int), ("swap", ctypes.c_int), ("edge_bytes", ctypes.c_longlong),
                 ("items", ctypes.c_longlong)]
+
+
+class _AlignCoopPlan(ctypes.Structure):
+    _fields_ = [("strips", ctypes.c_int), ("ckpt_bytes", ctypes.c_longlong), ("progress_bytes", ctypes.c_longlong),
+                ("end_bytes", ctypes.c_longlong), ("window", ctypes.c_int), ("window_trace_bytes", ctypes.c_longlong)]
 
 
 _lib = None
@@ -266,6 +271,13 @@ def lib() -> ctypes.CDLL:
         L.sw_score_matrix_batch_coop.restype = i
         L.sw_matrix_coop_plan.argtypes = [i, i, i, ctypes.POINTER(_CoopPlan)]
         L.sw_matrix_coop_plan.restype = i
+    if hasattr(L, "sw_align_matrix_long_coop"):   # long pairs on many waves (include/algoGPU.h)
+        L.sw_align_matrix_long_coop.argtypes = L.sw_align_matrix_batch.argtypes
+        L.sw_align_matrix_long_coop.restype = i
+        L.sw_db_align_matrix_long_coop.argtypes = L.sw_db_align_matrix.argtypes
+        L.sw_db_align_matrix_long_coop.restype = i
+        L.sw_align_long_coop_plan.argtypes = [i, i, ctypes.POINTER(_AlignCoopPlan)]
+        L.sw_align_long_coop_plan.restype = i
     _lib = L
     return L
 
@@ -763,7 +775,7 @@ def _align_pairs(f, pairs, matrix, gap_init: int, gap_ext: int, cap: int = 0, mo
 
 
 def align_matrix_batch(pairs: Iterable[Sequence], matrix: Matrix, gap_init: int, gap_ext: int, cpu: bool = False,
-                       mode: str = "local", long: bool = False, band: int | None = None) -> list:
+                       mode: str = "local", long: bool = False, band: int | None = None, coop: bool = False) -> list:
     """An :class:`Alignment` per pair under ``matrix`` (seq1 is its first index) with affine gaps, on
     the GPU (sw_align_matrix_batch: the traced matrix kernel and a walk) or, with ``cpu=True``, from
     the library's plain full-matrix aligner on the host (sw_align_matrix_cpu), which gives the same
@@ -772,8 +784,14 @@ def align_matrix_batch(pairs: Iterable[Sequence], matrix: Matrix, gap_init: int,
     seq2); ``long=True`` is :func:`align_matrix_long`, which is local only.
     ``band=B`` (any mode, not with ``long=True``): the alignment within the band of
     :func:`score_matrix_batch`, from the band kernels (sw_align_matrix_batch_band), which hold only the
-    band's trace (:func:`band_plan`), or with ``cpu=True`` from the host aligner restricted to it."""
+    band's trace (:func:`band_plan`), or with ``cpu=True`` from the host aligner restricted to it.
+    ``coop=True`` (with ``long=True`` only): :func:`align_matrix_long` with ``coop=True``."""
     am = _mode(mode)
+    if coop:
+        if band is not None:
+            raise ValueError("band= is not built for coop=True (the cooperative long path)")
+        if not long:
+            raise ValueError("coop=True is not built without long=True (it is the checkpointed traceback on many waves)")
     if band is not None:
         if long:
             raise ValueError("band= is not built for long=True (checkpointed traceback)")
@@ -784,19 +802,34 @@ def align_matrix_batch(pairs: Iterable[Sequence], matrix: Matrix, gap_init: int,
             raise ValueError("mode=%r is not built for long=True (checkpointed traceback): it is local only" % mode)
         if cpu:
             raise ValueError("long=True is a GPU path: not with cpu=True")
-        return align_matrix_long(pairs, matrix, gap_init, gap_ext)
+        return align_matrix_long(pairs, matrix, gap_init, gap_ext, coop=coop)
     if am != SW_MODE_LOCAL:
         f = lib().sw_align_matrix_cpu_mode if cpu else lib().sw_align_matrix_batch_mode
         return _align_pairs(f, pairs, matrix, gap_init, gap_ext, mode=am)
     return _align_pairs(lib().sw_align_matrix_cpu if cpu else lib().sw_align_matrix_batch, pairs, matrix, gap_init, gap_ext)
 
 
-def align_matrix_long(pairs: Iterable[Sequence], matrix: Matrix, gap_init: int, gap_ext: int) -> list:
+def align_matrix_long(pairs: Iterable[Sequence], matrix: Matrix, gap_init: int, gap_ext: int, coop: bool = False) -> list:
     """:func:`align_matrix_batch` for pairs whose whole trace does not fit option ``trace_mb``: the same
     alignments, bit for bit, by checkpointed traceback (sw_align_matrix_long): a locate pass keeps the
     right-edge column of every strip of 512 seq1 positions, then the strips are filled again and
-    walked one at a time, right to left.  Memory: :func:`align_long_plan`."""
-    return _align_pairs(lib().sw_align_matrix_long, pairs, matrix, gap_init, gap_ext, _LONG_CIGAR_CAP)
+    walked one at a time, right to left.  Memory: :func:`align_long_plan`.
+    ``coop=True`` (sw_align_matrix_long_coop): the same alignments with the locate pass of a pair on as
+    many waves as it has strips and a window of strips filled a round (option ``long_window``), for one or
+    a few long pairs.  Memory: :func:`align_long_coop_plan`."""
+    f = lib().sw_align_matrix_long_coop if coop else lib().sw_align_matrix_long
+    return _align_pairs(f, pairs, matrix, gap_init, gap_ext, _LONG_CIGAR_CAP)
+
+
+def align_long_coop_plan(n: int, m: int) -> dict:
+    """What ``align_matrix_long(..., coop=True)`` needs for one n x m pair under the current ``trace_mb``,
+    SWMI_ALIGN_CKPT_MB and ``long_window`` (sw_align_long_coop_plan, no GPU call): ``strips``, ``ckpt_bytes``,
+    ``progress_bytes``, ``end_bytes``, the ``window`` of strips a round would fill for the pair alone and its
+    ``window_trace_bytes``.  Raises :class:`SwError` where :func:`align_long_plan` does."""
+    p = _AlignCoopPlan()
+    _check(lib().sw_align_long_coop_plan(int(n), int(m), ctypes.byref(p)))
+    return {"strips": p.strips, "ckpt_bytes": p.ckpt_bytes, "progress_bytes": p.progress_bytes, "end_bytes": p.end_bytes,
+            "window": p.window, "window_trace_bytes": p.window_trace_bytes}
 
 
 def align_long_plan(n: int, m: int) -> dict:
@@ -811,9 +844,10 @@ def align_long_plan(n: int, m: int) -> dict:
 
 
 def align_matrix(seq1, seq2, matrix: Matrix, gap_init: int, gap_ext: int, cpu: bool = False, mode: str = "local",
-                 long: bool = False, band: int | None = None) -> Alignment:
+                 long: bool = False, band: int | None = None, coop: bool = False) -> Alignment:
     """One pair (see :func:`align_matrix_batch`)."""
-    return align_matrix_batch([(seq1, seq2)], matrix, gap_init, gap_ext, cpu=cpu, mode=mode, long=long, band=band)[0]
+    return align_matrix_batch([(seq1, seq2)], matrix, gap_init, gap_ext, cpu=cpu, mode=mode, long=long, band=band,
+                              coop=coop)[0]
 
 
 def band_plan(n: int, m: int, band: int) -> dict:
@@ -843,8 +877,8 @@ def last_align_ms() -> tuple:
 
 
 def last_align_long_ms() -> dict:
-    """Device time of this thread's last :func:`align_matrix_long` / ``Database.align(long=True)`` call:
-    ``locate_ms``, ``strip_ms`` (the strip fills), ``walk_ms``, and its ``rounds``."""
+    """Device time of this thread's last :func:`align_matrix_long` / ``Database.align(long=True)`` call
+    (with or without ``coop=True``): ``locate_ms``, ``strip_ms`` (the strip fills), ``walk_ms``, and its ``rounds``."""
     lo, st, wk, r = ctypes.c_float(), ctypes.c_float(), ctypes.c_float(), ctypes.c_int()
     lib().sw_last_align_long_ms(ctypes.byref(lo), ctypes.byref(st), ctypes.byref(wk), ctypes.byref(r))
     return {"locate_ms": lo.value, "strip_ms": st.value, "walk_ms": wk.value, "rounds": r.value}

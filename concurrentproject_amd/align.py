@@ -16,7 +16,8 @@ pair, I a query residue against a gap, D a record residue against a gap; ``*`` f
 Only the top K of each query are aligned.  Without --matrix the alignments are made under the
 equality table of --params over the bytes present (at most 32 distinct ones).  --long makes the
 same alignments by checkpointed traceback (Database.align(long=True)): for hits so long that a
-whole pair's trace does not fit option trace_mb; the lines are the same.
+whole pair's trace does not fit option trace_mb; the lines are the same.  --coop (with --long) makes
+them on many waves (Database.align(long=True, coop=True)); the lines are the same again.
 
 --mode global|semiglobal (with --matrix; default local): the query and the record end to end, or
 the whole query inside the record with the record's flanks free.  Scores may be negative, an
@@ -43,12 +44,16 @@ def main(argv=None) -> int:
     ap.add_argument("--alignments", action="store_true", help="align the top K hits: ranges and cigar per line")
     ap.add_argument("--long", action="store_true",
                     help="with --alignments: checkpointed traceback, for hits whose whole trace does not fit (same lines)")
+    ap.add_argument("--coop", action="store_true",
+                    help="with --long: the locate pass on many waves and a window of strips a round (same lines)")
     ap.add_argument("--mode", choices=("local", "global", "semiglobal"), default="local",
                     help="alignment mode of a --matrix search: global = query and record end to end, semiglobal = the "
                          "whole query inside the record")
     a = ap.parse_args(argv)
     if a.long and not a.alignments:
         ap.error("--long goes with --alignments")
+    if a.coop and not a.long:
+        ap.error("--coop goes with --long")
     if a.mode != "local" and a.matrix is None:
         ap.error("--mode %s requires --matrix (and --gaps)" % a.mode)
     if a.mode != "local" and a.long:
@@ -93,7 +98,8 @@ def main(argv=None) -> int:
             sc = scores[q]
             order = np.lexsort((np.arange(len(sc)), -sc.astype(np.int64)))[:a.top]
             if a.alignments:
-                al = db.align(qs.record(q)[1], [int(i) for i in order], amatrix, agaps[0], agaps[1], long=a.long, mode=a.mode)
+                al = db.align(qs.record(q)[1], [int(i) for i in order], amatrix, agaps[0], agaps[1], long=a.long, mode=a.mode,
+                              coop=a.coop)
                 for r, (i, x) in enumerate(zip(order, al)):
                     out.write("%d\t%s\t%d\t%d\t%d\t%s\t%d\t%d\t%d\t%d\t%s\n"
                               % (q, qh, r + 1, int(sc[i]), int(i), db.header(int(i)), x.beg1, x.end1, x.beg2, x.end2,

@@ -6,7 +6,9 @@
 // fallback for a machine without a device; it needs n * m bytes a pair.  Also the arithmetic of
 // the checkpointed traceback of long pairs (sw_align_matrix_long): strips, checkpoint and strip
 // trace bytes, the two budgets' refusals and the greedy packing of groups and rounds; the exported
-// sw_align_long_plan (sw_matrix.hip) only reads option "trace_mb" and calls it.
+// sw_align_long_plan (sw_matrix.hip) only reads option "trace_mb" and calls it.  The same for the long path on
+// many waves (sw_align_matrix_long_coop): the merge of the strips' end-cell records, the window of strips a round
+// fills, and the plan behind sw_align_long_coop_plan.
 // And the host side of global and semi-global alignment (SW_MODE_*): the mode and score-range checks,
 // the answers for empty sequences, and sw_align_matrix_cpu_mode, the same plain aligner for those modes.
 // And banded alignment (sw_*_band): the band's arithmetic (range, cells, the strips' chunks, trace bytes),
@@ -185,6 +187,51 @@ void align_pack(const long long* need, int n, long long budget, std::vector<int>
         }
         end.push_back(k);
     }
+}
+
+// ---- long pairs on many waves: records, windows and the plan (sw_matrix_host.h) ----
+
+void align_merge_ends(const AlignEnd* rec, int nrec, int* score, int* ei, int* ej) {
+    int bM = 0, bD = 0, bJ = 0;
+    for (int k = 0; k < nrec; ++k) {
+        const AlignEnd& r = rec[k];
+        if (r.t <= 0) continue;   // a strip without a cell
+        const bool better = r.t > bM || (r.t == bM && (r.d < bD || (r.d == bD && r.j < bJ)));
+        bM = better ? r.t : bM;
+        bD = better ? r.d : bD;
+        bJ = better ? r.j : bJ;
+    }
+    *score = bM;
+    *ei = bM > 0 ? bD - bJ : 0;
+    *ej = bM > 0 ? bJ : 0;
+}
+
+long long align_progress_bytes(long long items) { return (items * 4 + 15) / 16 * 16; }
+long long align_end_bytes(long long items) { return items * (long long)sizeof(AlignEnd); }
+
+int align_window(long long strip_bytes, long long live_bytes, long long trace_budget, int long_window, int strip) {
+    long long g = long_window > 0 ? std::min<long long>(long_window, trace_budget / std::max<long long>(strip_bytes, 1))
+                                  : trace_budget / std::max<long long>(live_bytes, 1);
+    g = std::min<long long>(g, ALIGN_WINDOW_MAX);
+    g = std::min<long long>(g, (long long)strip + 1);
+    return (int)std::max<long long>(g, 1);
+}
+
+int align_long_coop_plan(int n, int m, long long trace_budget, long long ckpt_budget, int long_window, const char* what,
+                         int idx, sw_align_coop_plan* out) {
+    sw_align_plan p;
+    const int rc = align_long_plan(n, m, trace_budget, ckpt_budget, what, idx, &p);
+    sw_align_coop_plan q{0, 0, 0, 0, 0, 0};
+    if (p.strips > 0) {
+        q.strips = p.strips;
+        q.ckpt_bytes = p.ckpt_bytes;
+        q.progress_bytes = align_progress_bytes(p.strips);
+        q.end_bytes = align_end_bytes(p.strips);
+        q.window = align_window(p.strip_trace_bytes, p.strip_trace_bytes, trace_budget, long_window, p.strips - 1);
+        q.window_trace_bytes = q.window * p.strip_trace_bytes;
+    }
+    *out = q;
+    return rc;
 }
 
 bool mode_ok(const char* fn, int mode) {

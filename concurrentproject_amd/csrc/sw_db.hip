@@ -270,15 +270,15 @@ int search_matrix(sw_db* db, const sw_matrix* mx, const unsigned char* query, in
 }
 
 // the query (seq1, across the lanes) aligned with the chosen records, out of the device arena;
-// long_pairs: by checkpointed traceback (sw_db_align_matrix_long)
+// long_pairs: by checkpointed traceback (sw_db_align_matrix_long); coop: on many waves (sw_db_align_matrix_long_coop)
 int align_matrix(sw_db* db, const sw_matrix* mx, const unsigned char* query, int qlen, const int* record_idx, int nidx,
-                 int gap_init, int gap_ext, AlignSink& sink, bool long_pairs, int amode = SW_MODE_LOCAL) {
+                 int gap_init, int gap_ext, AlignSink& sink, bool long_pairs, int amode = SW_MODE_LOCAL, bool coop = false) {
     const int nrec = (int)db->len.size();
     for (int k = 0; k < nidx; ++k)
         if (record_idx[k] < 0 || record_idx[k] >= nrec) {
             char m[120];
             std::snprintf(m, sizeof m, "sw_db_align_matrix%s: record index %d (entry %d) is outside [0, %d)",
-                          long_pairs ? "_long" : "", record_idx[k], k, nrec);
+                          coop ? "_long_coop" : long_pairs ? "_long" : "", record_idx[k], k, nrec);
             report_error(m);
             return -1;
         }
@@ -296,7 +296,7 @@ int align_matrix(sw_db* db, const sw_matrix* mx, const unsigned char* query, int
     }
     if (long_pairs)
         return matrix_align_long_device(mx, v->arena, a_off.data(), alen.data(), b_off.data(), blen.data(), record_idx, nidx,
-                                        gap_init, gap_ext, "record", sink);
+                                        gap_init, gap_ext, "record", sink, coop);
     return matrix_align_device(mx, v->arena, a_off.data(), alen.data(), b_off.data(), blen.data(), record_idx, nidx, gap_init,
                                gap_ext, "record", sink, amode);
 }
@@ -387,6 +387,20 @@ int sw_db_align_matrix_long(sw_db* db, const sw_matrix* mx, const unsigned char*
     std::lock_guard<std::mutex> g(db->mu);
     AlignSink sink{out, {}};
     if (align_matrix(db, mx, query, qlen, record_idx, nidx, gap_init, gap_ext, sink, true)) return -1;
+    return sink.finish(cigar, cigar_cap, cigar_used);
+}
+
+int sw_db_align_matrix_long_coop(sw_db* db, const sw_matrix* mx, const unsigned char* query, int qlen, const int* record_idx,
+                                 int nidx, int gap_init, int gap_ext, sw_alignment* out, unsigned* cigar, long long cigar_cap,
+                                 long long* cigar_used) {
+    if (!db || !mx || qlen < 0 || (qlen > 0 && !query) || nidx < 0 || cigar_cap < 0 || !cigar_used ||
+        (cigar_cap > 0 && !cigar) || (nidx > 0 && (!record_idx || !out))) {
+        report_error("sw_db_align_matrix_long_coop: invalid arguments");
+        return -1;
+    }
+    std::lock_guard<std::mutex> g(db->mu);
+    AlignSink sink{out, {}};
+    if (align_matrix(db, mx, query, qlen, record_idx, nidx, gap_init, gap_ext, sink, true, SW_MODE_LOCAL, true)) return -1;
     return sink.finish(cigar, cigar_cap, cigar_used);
 }
 

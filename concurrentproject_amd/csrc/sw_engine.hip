@@ -134,13 +134,16 @@ bool opt_pow2_ok(long long v) { return (v & (v - 1)) == 0; }
     X(slab_plain, 0, 0, 1, nullptr, false)                                                                            \
     /* tests only: flow2's compute waves skip this item (-1 = none) */                                                \
     X(stall_item, -1, -1, ANY_HI, nullptr, false)
-// The keys of one entry point, sw_score_matrix_batch_coop (sw_matrix.hip), set and read like the ones above but
-// documented with that entry point and not listed by sw_option_name, whose list is the "Tuning knobs" of the header.
+// The keys of the cooperative entry points, sw_score_matrix_batch_coop and sw_align_matrix_long_coop (sw_matrix.hip),
+// set and read like the ones above but documented with those entry points and not listed by sw_option_name, whose
+// list is the "Tuning knobs" of the header.
 #define SW_OPTIONS_COOP(X)                                                                                            \
     /* MiB of edge columns a cooperative matrix launch may hold */                                                    \
     X(coop_mb, 1024, 1, 3072, nullptr, false)                                                                         \
     /* 1: the edge columns are filled with 0x3F bytes before every cooperative launch (tests) */                      \
-    X(coop_poison, 0, 0, 1, nullptr, false)
+    X(coop_poison, 0, 0, 1, nullptr, false)                                                                           \
+    /* strips of a pair a round of sw_align_matrix_long_coop fills at once: 0 = automatic, 1 .. 64 */                 \
+    X(long_window, 0, 0, 64, nullptr, false)
 
 #define X(key, def, lo, hi, ok, flag) O_##key,
 // OPT_COUNT: the listed keys; the rows of SW_OPTIONS_COOP follow them (OPT_REWIND_ puts the count back by one, so

@@ -57,6 +57,10 @@
 // exception to "one wave owns one pair" and to "no wave waits for another": its kernels, sw_matrix_coop_kernel<W, AM>,
 // claim one strip of a pair at a time, and the wave of strip s + 1 follows the wave of strip s through the pair's edge
 // columns with a bounded poll (option "timeout").  Opt-in, score-only, no band (COOPERATIVE SCORE below).
+//
+// LONG PAIRS ON MANY WAVES (include/algoGPU.h sw_align_matrix_long_coop) puts the locate pass of
+// the long path on that hand-off -- the edge columns are the checkpoint columns -- and lets a round fill a window of
+// consecutive strips of a pair, which do not depend on one another.  Opt-in, local only; the same alignments.
 #include "sw_device.h"
 #include "sw_matrix_host.h"
 #include "../../include/algoGPU.h"
@@ -983,6 +987,7 @@ struct CoopArgs {
     unsigned char* edge;
     unsigned* progress;         // a word an item: rows [0, r) of the item's right edge are stored
     long long timeout_ticks;    // s_memrealtime ticks (100 MHz) before a poll gives up
+    AlignEnd* ends;             // the cooperative locate pass only (below): an end-cell record an item
 };
 
 // The slow path of the consumer's poll, out of line as await_slow (sw_device.h) and for its reason.
@@ -1009,7 +1014,11 @@ __device__ __noinline__ int coop_await(__amdgpu_buffer_rsrc_t prog_rsrc, __amdgp
 }
 
 // One strip of one pair.  false: the launch has failed (coop_await) and the wave leaves.
-template <int W, int AM>
+// MODE: M_SCORE, the score path; M_LOCATE (local, W = TRACE_W, seq1 across the lanes), the cooperative
+// locate pass of LONG PAIRS ON MANY WAVES below: the same consumer and producer on the pair's checkpoint
+// columns, the end-cell bookkeeping of matrix_pair for this one strip, and an end-cell record an item
+// instead of the atomicMax.  The score instantiations are the code they were.
+template <int W, int AM, int MODE = M_SCORE>
 __device__ __forceinline__ bool matrix_coop_strip(const MatArgs& a, const CoopArgs& x, const MatPair& pd, const CoopPair& cp,
                                                   const unsigned item, const int strip, const int lane,
                                                   const signed char* s_tab, const unsigned char* s_code) {
@@ -1032,9 +1041,13 @@ __device__ __forceinline__ bool matrix_coop_strip(const MatArgs& a, const CoopAr
     const __amdgpu_buffer_rsrc_t ctrl_rsrc = __builtin_amdgcn_make_buffer_rsrc(a.ctrl, 0, (int)sizeof(Ctrl), RSRC_FLAGS);
     const int nchunks = (m + SW - 1 + C - 1) / C;
     unsigned toff = 0;
-    MStrip<W, M_SCORE, AM> S;
+    MStrip<W, MODE, AM> S;
     S.M = AM == AM_LOCAL ? 0 : MAT_NEG;
     S.setup(a, pd, strip, lane, s_code);
+    if constexpr (MODE == M_LOCATE) {   // as matrix_pair starts every strip
+        S.Mkp = 0;
+        S.kp8 = 0;
+    }
     // THE CONSUMER.  `seen` rows of the left edge are known to be stored (strip 0 has no left edge).
     // Before the fetch of rows [k, k + 64) the word of item - 1 -- strip - 1 of this pair: items are
     // pair-major, strip-minor -- must have reached min(m, k + 64).  A poll that has matched is followed
@@ -1091,6 +1104,28 @@ __device__ __forceinline__ bool matrix_coop_strip(const MatArgs& a, const CoopAr
             __builtin_amdgcn_raw_buffer_store_b32((unsigned)pub, prog_rsrc, lane == 0 ? item * 4u : OOR, 0, AUX_SC1);
         }
     }
+    if constexpr (MODE == M_LOCATE) {
+        // The item's end cell: the lane's cell of this strip (column lane * W + p, reached at step k), the
+        // lanes merged by the three-key rule at the end of matrix_pair: the largest t, then the smallest
+        // i + j, then the smallest j.  The host merges a pair's records by the same rule (align_merge_ends),
+        // so no wave writes where another does: no atomics.  (t = 0: no cell, and d and j mean nothing.)
+        const int k = S.Mkp >> 3, cl = lane * W + (S.Mkp & 7);
+        int bM = S.M, bD = strip * SW + k, bJ = k - cl;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const int oM = __shfl_xor(bM, off), oD = __shfl_xor(bD, off), oJ = __shfl_xor(bJ, off);
+            const bool better = oM > bM || (oM == bM && (oD < bD || (oD == bD && oJ < bJ)));
+            bM = better ? oM : bM;
+            bD = better ? oD : bD;
+            bJ = better ? oJ : bJ;
+        }
+        // lane 0's store without a branch on the lane (the comment at matrix_pair's score store)
+        const __amdgpu_buffer_rsrc_t end_rsrc =
+            __builtin_amdgcn_make_buffer_rsrc(x.ends, 0, (int)((unsigned)a.npairs * (unsigned)sizeof(AlignEnd)), RSRC_FLAGS);
+        __builtin_amdgcn_raw_buffer_store_b128(u32x4{(unsigned)bM, (unsigned)bD, (unsigned)bJ, 0u}, end_rsrc,
+                                               lane == 0 ? item * (unsigned)sizeof(AlignEnd) : OOR, 0, 0);
+        return true;
+    }
     int M = S.M;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) M = max(M, __shfl_xor(M, off));
@@ -1133,6 +1168,78 @@ __global__ void __launch_bounds__(256) sw_matrix_coop_kernel(MatArgs a, CoopArgs
         cp.strips = __builtin_amdgcn_readfirstlane(craw.strips);
         if (!matrix_coop_strip<W, AM>(a, x, pd, cp, item, strip, lane, s.tab, s.code)) return;
     }
+}
+
+// ---- LONG PAIRS ON MANY WAVES: a cooperative locate pass, and rounds that trace a window of strips
+// (sw_align_matrix_long_coop) -----
+//
+// The cooperative kernel's edge columns are the locate pass's checkpoint columns byte for byte: m rows of
+// 8 bytes {H - G_INIT, E - G_EXT}, a column a strip.  So the locate pass of a long pair is the kernel above
+// at W = 8 with seq1 across the lanes, MStrip<TRACE_W, M_LOCATE> for the step, column `strip` of the pair's
+// checkpoints (CoopPair::edge_off from CoopArgs::edge, CoopPair::stride = align_ckpt_stride(m)) for the
+// edge, and an end-cell record an item.  The hand-off and the progress argument are the ones above,
+// unchanged: items are claimed in the same order and an item waits for the same one item.  It writes
+// exactly what sw_matrix_locate_kernel writes, so sw_matrix_strip_kernel reads it as it is.
+__global__ void __launch_bounds__(256) sw_matrix_locate_coop_kernel(MatArgs a, CoopArgs x) {
+    const MatLds s = matrix_stage(a);
+    const int lane = threadIdx.x & 63;
+    unsigned item;
+    MatPair pd;
+    WalkPair wp;
+    while (matrix_claim(a, lane, item)) {
+        const CoopItem iraw = x.items[item];
+        const int pair = __builtin_amdgcn_readfirstlane(iraw.pair);
+        const int strip = __builtin_amdgcn_readfirstlane(iraw.strip);
+        matrix_claimed_pair<false>(a, (unsigned)pair, pd, wp);
+        pd.swap_or_band = 0;   // seq1 across the lanes
+        const CoopPair craw = x.cp[pair];
+        CoopPair cp;
+        cp.edge_off = uniform64(craw.edge_off);
+        cp.stride = __builtin_amdgcn_readfirstlane(craw.stride);
+        cp.strips = __builtin_amdgcn_readfirstlane(craw.strips);
+        if (!matrix_coop_strip<TRACE_W, AM_LOCAL, M_LOCATE>(a, x, pd, cp, item, strip, lane, s.tab, s.code)) return;
+    }
+}
+
+// The strip fills of a pair do not depend on one another: each reads only the checkpoint on its left.  The
+// walk's j never grows as it moves left, so the row j at which it enters strip s bounds the rows of every
+// strip further left, and a round may fill a WINDOW of G consecutive strips [s - G + 1, s] of a pair, all
+// over rows [0, j], as G items of sw_matrix_strip_kernel on G waves.  Their one-strip buffers, `steps`
+// steps each, lie end to end, which is StripTrace's [strip - strip0][step][lane] with strip0 = s - G + 1:
+// matrix_walk crosses the strip boundaries inside the window as it does in a whole trace.
+struct WindowItem {
+    uint64_t trace_off;     // bytes, from WalkWindowArgs::trace: the buffer of the window's first strip
+    uint64_t ops_off;       // bytes, from WalkWindowArgs::ops: the pair's n + m operation bytes
+    int n, m;               // the pair
+    int strip0, nstrips;    // seq1 positions [512 * strip0, 512 * (strip0 + nstrips))
+    int steps;              // of every one-strip buffer of the window
+    int rows;               // j + 1: rows [0, j] are filled
+    unsigned trace_bytes;   // of the whole window: nstrips * steps * 256
+    int slot;               // the pair's WalkState
+};
+struct WalkWindowArgs {
+    const WindowItem* items;
+    const unsigned char* trace;
+    unsigned char* ops;
+    WalkState* st;
+    int nitems;
+};
+
+// sw_matrix_walk_strip_kernel for a window; a window of one strip walks what that kernel walks.
+__global__ void __launch_bounds__(64) sw_matrix_walk_window_kernel(WalkWindowArgs w) {
+    const int item = (int)(blockIdx.x * 64 + threadIdx.x);
+    if (item >= w.nitems) return;
+    const WindowItem it = w.items[item];
+    WalkState* st = w.st + it.slot;
+    Walk s = *st;
+    if (s.done || s.err) return;
+    const long long lo = (long long)it.strip0 * (64 * TRACE_W), hi = lo + (long long)it.nstrips * (64 * TRACE_W);
+    if (s.i < lo || s.i >= hi || s.j >= it.rows || s.nops < 0 || s.state < 0 || s.state > 2 || it.nstrips < 1)
+        s.err = WALK_RANGE;   // (matrix_walk checks the cell against the pair and the window's bytes)
+    else
+        matrix_walk(StripTrace{it.strip0, it.steps, it.trace_bytes}, w.trace + it.trace_off, w.ops + it.ops_off, it.n, it.m,
+                    SW_MODE_LOCAL, s);
+    *static_cast<Walk*>(st) = s;
 }
 
 // ---- host ------------------------------------------------------------------------------------
@@ -1179,6 +1286,7 @@ enum {
     B_WALK, B_TRACE, B_RES, B_OPS,                       // traced launches: walk pairs, trace, results, operations
     B_LONG, B_CKPT, B_ITEMS, B_STATE,                    // long pairs: locate items, checkpoints, strip items, walk states
     B_CPAIRS, B_CITEMS, B_EDGE, B_PROGRESS,              // cooperative score: pairs, items, edge columns, progress words
+    B_ENDS, B_WINDOWS,                                   // long pairs on many waves: end-cell records, a round's windows
     B_COUNT
 };
 struct MatCtx {
@@ -1190,6 +1298,7 @@ struct MatCtx {
     FillKernel fill[2][3][5];   // [band][SW_MODE_*][index into W_OF, or WI_TRACED]
     FillKernel locate{(const void*)sw_matrix_locate_kernel}, strip{(const void*)sw_matrix_strip_kernel};
     FillKernel coop[3][4];      // [SW_MODE_*][index into W_OF]
+    FillKernel locate_coop{(const void*)sw_matrix_locate_coop_kernel};
     MatCtx() {
         name_coop_kernels<AM_LOCAL>(coop[AM_LOCAL]);
         name_coop_kernels<AM_GLOBAL>(coop[AM_GLOBAL]);
@@ -1818,8 +1927,90 @@ struct LongOut {
     std::vector<unsigned char> ops;
     std::vector<uint64_t> ops_off;
 };
+constexpr int MODE_MATRIX_LONG_COOP = 12;   // sw_align_matrix_long_coop: cooperative locate, a window of strips a round
+
+// The cooperative locate launch of one group (LONG PAIRS ON MANY WAVES above): the items are the strips of
+// its pairs, pair-major and strip-minor, the pairs longest first (pairs[k], with the checkpoint column 0 of
+// pairs[k] at byte ckpt_off[pairs[k].out_idx] of B_CKPT).  o.res[slot] receives score, ei, ej of every pair,
+// merged on the host from the records of its strips.  a: the launch's arguments, which the strip fills go on
+// using.  *extra: the bytes of progress words and end records.
+int locate_coop(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, const std::vector<MatPair>& pairs,
+                const std::vector<uint64_t>& ckpt_off, uint64_t ckpt_total, int gap_init, int gap_ext, const char* fn,
+                const char* what, const std::vector<int>& name_of, MatArgs& a, sw_stats& st, LongOut& o, long long* extra) {
+    const size_t np = pairs.size();
+    std::vector<CoopPair> cp(np);
+    std::vector<CoopItem> items;
+    std::vector<size_t> first(np);
+    for (size_t k = 0; k < np; ++k) {
+        const MatPair& d = pairs[k];
+        cp[k] = CoopPair{ckpt_off[(size_t)d.out_idx], (unsigned)align_ckpt_stride(d.m), (int)align_strips(d.n)};
+        first[k] = items.size();
+        for (int q = 0; q < cp[k].strips; ++q) items.push_back(CoopItem{(int)k, q});
+    }
+    const size_t ni = items.size();
+    const size_t prog_bytes = (size_t)align_progress_bytes((long long)ni), end_bytes = (size_t)align_end_bytes((long long)ni);
+    long long blocks = 0;
+    if (fill_blocks(c, c->locate_coop, ni, 0, &blocks) || fill_args(c, mx, d_arena, pairs, (int)np, gap_init, gap_ext, 0, blocks, a) ||
+        ensure(c, B_CPAIRS, np * sizeof(CoopPair)) || ensure(c, B_CITEMS, ni * sizeof(CoopItem)) ||
+        ensure(c, B_PROGRESS, prog_bytes) || ensure(c, B_ENDS, end_bytes))
+        return -1;
+    a.npairs = (int)ni;   // what the waves claim
+    MCHK(hipMemcpyAsync(c->buf[B_CPAIRS], cp.data(), np * sizeof(CoopPair), hipMemcpyHostToDevice, c->stream));
+    MCHK(hipMemcpyAsync(c->buf[B_CITEMS], items.data(), ni * sizeof(CoopItem), hipMemcpyHostToDevice, c->stream));
+    MCHK(hipMemsetAsync(c->buf[B_PROGRESS], 0, prog_bytes, c->stream));
+    MCHK(hipMemsetAsync(c->buf[B_ENDS], 0, end_bytes, c->stream));
+    // option "coop_poison": a row consumed before it was stored then carries H of about 10^9
+    if (sw_get_option("coop_poison") && ckpt_total) MCHK(hipMemsetAsync(c->buf[B_CKPT], 0x3F, (size_t)ckpt_total, c->stream));
+    CoopArgs x{};
+    x.cp = (const CoopPair*)c->buf[B_CPAIRS];
+    x.items = (const CoopItem*)c->buf[B_CITEMS];
+    x.edge = (unsigned char*)c->buf[B_CKPT];
+    x.progress = (unsigned*)c->buf[B_PROGRESS];
+    x.timeout_ticks = sw_get_option("timeout") * 100000000LL;   // s_memrealtime: 100 MHz
+    x.ends = (AlignEnd*)c->buf[B_ENDS];
+    void* kargs[] = {&a, &x};
+    MCHK(hipEventRecord(c->ev0, c->stream));
+    MCHK(hipLaunchKernel(c->locate_coop.fn, dim3((unsigned)blocks), dim3(256), kargs, 0, c->stream));
+    MCHK(hipGetLastError());
+    MCHK(hipEventRecord(c->ev1, c->stream));
+    Ctrl ctrl{};
+    std::vector<AlignEnd> ends(ni);
+    MCHK(hipMemcpyAsync(&ctrl, c->buf[B_CTRL], sizeof ctrl, hipMemcpyDeviceToHost, c->stream));
+    MCHK(hipMemcpyAsync(ends.data(), c->buf[B_ENDS], end_bytes, hipMemcpyDeviceToHost, c->stream));
+    MCHK(hipStreamSynchronize(c->stream));
+    float ms = 0.f;
+    MCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    t_fill_ms += ms;
+    t_locate_ms += ms;
+    st.items += (int)ni;
+    st.blocks = (int)blocks;
+    st.waves_per_cu = 4 * c->locate_coop.wgs;
+    *extra = (long long)(prog_bytes + end_bytes);
+    if (ctrl.error != 0) {
+        const unsigned it = std::min<unsigned>(ctrl.err_item, (unsigned)ni - 1);
+        char m[256];
+        std::snprintf(m, sizeof m,
+                      "%s: item %u (%s %d, strip %d of %d) waited longer than option timeout = %lld s for the strip on its "
+                      "left (error bits 0x%x)",
+                      fn, it, what, name_of[(size_t)pairs[(size_t)items[it].pair].out_idx], items[it].strip,
+                      cp[(size_t)items[it].pair].strips, (long long)sw_get_option("timeout"), ctrl.error);
+        report_error(m);
+        return -1;
+    }
+    o.res.assign(np, TraceRes{});
+    for (size_t k = 0; k < np; ++k) {
+        TraceRes& r = o.res[(size_t)pairs[k].out_idx];
+        align_merge_ends(ends.data() + first[k], cp[k].strips, &r.score, &r.ei, &r.ej);
+    }
+    return 0;
+}
+
+// coop: the cooperative locate launch instead of the one-wave one, and rounds that fill a window of strips
+// a pair (align_window) and walk it with sw_matrix_walk_window_kernel; else a window is one strip and the
+// launches are the ones they were.
 int long_group(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, const std::vector<DevSeq>& act, int gap_init,
-               int gap_ext, long long trace_budget, const char* what, const int* name_idx, sw_stats& st, LongOut& o) {
+               int gap_ext, long long trace_budget, const char* what, const int* name_idx, sw_stats& st, LongOut& o,
+               bool coop = false) {
     const size_t np = act.size();
     const std::vector<int> order = longest_first(act);
     std::vector<uint64_t> ckpt_off(np);
@@ -1841,34 +2032,46 @@ int long_group(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, con
         lp[k] = LongPair{ckpt_off[(size_t)order[k]], (unsigned)align_ckpt_stride(p.blen), 0u};
     }
     long long blocks = 0;
+    long long held = (long long)ckpt_total;   // bytes held beside the traces: checkpoints; coop: progress words, end records
     MatArgs a{};   // no scratch: every strip's right edge goes to a checkpoint column
-    if (fill_blocks(c, c->locate, np, 0, &blocks) || fill_args(c, mx, d_arena, pairs, (int)np, gap_init, gap_ext, 0, blocks, a) ||
-        ensure(c, B_LONG, np * sizeof(LongPair)) || ensure(c, B_CKPT, (size_t)ckpt_total) ||
-        ensure(c, B_RES, np * sizeof(TraceRes)) || ensure(c, B_OPS, (size_t)ops_total) ||
-        ensure(c, B_STATE, np * sizeof(WalkState)))
-        return -1;
-    MCHK(hipMemcpyAsync(c->buf[B_LONG], lp.data(), np * sizeof(LongPair), hipMemcpyHostToDevice, c->stream));
-    MCHK(hipMemsetAsync(c->buf[B_RES], 0, np * sizeof(TraceRes), c->stream));
-    a.res = (TraceRes*)c->buf[B_RES];
     LongArgs x{};
-    x.lp = (const LongPair*)c->buf[B_LONG];
-    x.ckpt = (unsigned char*)c->buf[B_CKPT];
     void* kargs[] = {&a, &x};
+    if (ensure(c, B_CKPT, (size_t)ckpt_total) || ensure(c, B_OPS, (size_t)ops_total) || ensure(c, B_STATE, np * sizeof(WalkState)))
+        return -1;
+    if (coop) {
+        std::vector<int> name_of(np);
+        for (size_t s = 0; s < np; ++s) name_of[s] = name_idx ? name_idx[act[s].idx] : act[s].idx;
+        long long extra = 0;
+        if (locate_coop(c, mx, d_arena, pairs, ckpt_off, ckpt_total, gap_init, gap_ext,
+                        name_idx ? "sw_db_align_matrix_long_coop" : "sw_align_matrix_long_coop", what, name_of, a, st, o, &extra))
+            return -1;
+        held += extra;
+        x.ckpt = (unsigned char*)c->buf[B_CKPT];
+    } else {
+        if (fill_blocks(c, c->locate, np, 0, &blocks) || fill_args(c, mx, d_arena, pairs, (int)np, gap_init, gap_ext, 0, blocks, a) ||
+            ensure(c, B_LONG, np * sizeof(LongPair)) || ensure(c, B_RES, np * sizeof(TraceRes)))
+            return -1;
+        MCHK(hipMemcpyAsync(c->buf[B_LONG], lp.data(), np * sizeof(LongPair), hipMemcpyHostToDevice, c->stream));
+        MCHK(hipMemsetAsync(c->buf[B_RES], 0, np * sizeof(TraceRes), c->stream));
+        a.res = (TraceRes*)c->buf[B_RES];
+        x.lp = (const LongPair*)c->buf[B_LONG];
+        x.ckpt = (unsigned char*)c->buf[B_CKPT];
 
-    MCHK(hipEventRecord(c->ev0, c->stream));
-    MCHK(hipLaunchKernel(c->locate.fn, dim3((unsigned)blocks), dim3(256), kargs, 0, c->stream));
-    MCHK(hipGetLastError());
-    MCHK(hipEventRecord(c->ev1, c->stream));
-    o.res.resize(np);
-    MCHK(hipMemcpyAsync(o.res.data(), c->buf[B_RES], np * sizeof(TraceRes), hipMemcpyDeviceToHost, c->stream));
-    MCHK(hipStreamSynchronize(c->stream));
-    float ms = 0.f;
-    MCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    t_fill_ms += ms;
-    t_locate_ms += ms;
-    st.blocks = (int)blocks;
-    st.waves_per_cu = 4 * c->locate.wgs;
-    st.boundary_bytes = std::max(st.boundary_bytes, (long long)ckpt_total);
+        MCHK(hipEventRecord(c->ev0, c->stream));
+        MCHK(hipLaunchKernel(c->locate.fn, dim3((unsigned)blocks), dim3(256), kargs, 0, c->stream));
+        MCHK(hipGetLastError());
+        MCHK(hipEventRecord(c->ev1, c->stream));
+        o.res.resize(np);
+        MCHK(hipMemcpyAsync(o.res.data(), c->buf[B_RES], np * sizeof(TraceRes), hipMemcpyDeviceToHost, c->stream));
+        MCHK(hipStreamSynchronize(c->stream));
+        float ms = 0.f;
+        MCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+        t_fill_ms += ms;
+        t_locate_ms += ms;
+        st.blocks = (int)blocks;
+        st.waves_per_cu = 4 * c->locate.wgs;
+    }
+    st.boundary_bytes = std::max(st.boundary_bytes, held);
 
     // every walk starts at its end cell in state H; a pair without an alignment never walks
     o.ws.assign(np, WalkState{});
@@ -1884,59 +2087,98 @@ int long_group(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, con
 
     // rounds: every pair still walking has its current strip filled and walked; each round moves a
     // walk that has not ended exactly one strip to the left, so there are at most max_strips rounds
-    std::vector<int> live, ends;
+    // coop: a pair contributes a window of g strips (align_window), g items that end at its current strip, all over
+    // the rows of that strip, their buffers end to end; a round still moves every walk that goes on to the strip
+    // left of what was filled for it.  g = 1 otherwise, and the launches are the ones they were.
+    const int long_window = coop ? (int)sw_get_option("long_window") : 1;
+    std::vector<int> live, ends, win;
     std::vector<long long> need;
     std::vector<StripItem> items;
+    std::vector<WindowItem> windows;
     for (long long round = 0;; ++round) {
         live.clear();
         need.clear();
+        win.clear();
+        long long live_bytes = 0;
         for (size_t s = 0; s < np; ++s)
             if (!o.ws[s].done) {
                 live.push_back((int)s);
-                need.push_back(align_strip_trace_bytes(act[s].blen));
+                live_bytes += align_strip_trace_bytes(act[s].blen);
             }
         if (live.empty()) break;
         if (round >= max_strips) return walk_failed(what, name_idx ? name_idx[act[(size_t)live[0]].idx] : act[(size_t)live[0]].idx, 0);
+        for (const int s : live) {
+            const long long one = align_strip_trace_bytes(act[(size_t)s].blen);
+            const int g = coop ? align_window(one, live_bytes, trace_budget, long_window, o.ws[(size_t)s].i / ALIGN_STRIP) : 1;
+            win.push_back(g);
+            need.push_back(g * one);
+        }
         align_pack(need.data(), (int)live.size(), trace_budget, ends);
         t_rounds += 1;
         int lo = 0;
         for (const int hi : ends) {   // one launch pair: strip fill, walk
             items.clear();
+            windows.clear();
             uint64_t trace_total = 0;
             for (int k = lo; k < hi; ++k) {
                 const size_t s = (size_t)live[(size_t)k];
                 const DevSeq& p = act[s];
-                StripItem it{};
-                it.col_off = (uint64_t)p.a_off;
-                it.row_off = (uint64_t)p.b_off;
-                it.n = p.alen;
-                it.m = p.blen;
-                it.strip = o.ws[s].i / ALIGN_STRIP;
-                it.rows = o.ws[s].j + 1;
-                it.ckpt_in = it.strip > 0 ? ckpt_off[s] + (uint64_t)(it.strip - 1) * (uint64_t)align_ckpt_stride(p.blen) : 0;
-                it.trace_off = trace_total;
-                it.trace_bytes = (unsigned)need[(size_t)k];
-                it.ops_off = o.ops_off[s];
-                it.slot = (int)s;
-                trace_total += (uint64_t)need[(size_t)k];
-                items.push_back(it);
+                const int g = win[(size_t)k], last = o.ws[s].i / ALIGN_STRIP;
+                const uint64_t one = (uint64_t)need[(size_t)k] / (uint64_t)g;
+                WindowItem wi{};
+                wi.trace_off = trace_total;
+                wi.ops_off = o.ops_off[s];
+                wi.n = p.alen;
+                wi.m = p.blen;
+                wi.strip0 = last - g + 1;
+                wi.nstrips = g;
+                wi.steps = (int)align_strip_steps(p.blen);
+                wi.rows = o.ws[s].j + 1;
+                wi.trace_bytes = (unsigned)need[(size_t)k];
+                wi.slot = (int)s;
+                windows.push_back(wi);
+                for (int q = 0; q < g; ++q) {
+                    StripItem it{};
+                    it.col_off = (uint64_t)p.a_off;
+                    it.row_off = (uint64_t)p.b_off;
+                    it.n = p.alen;
+                    it.m = p.blen;
+                    it.strip = wi.strip0 + q;
+                    it.rows = wi.rows;
+                    it.ckpt_in = it.strip > 0 ? ckpt_off[s] + (uint64_t)(it.strip - 1) * (uint64_t)align_ckpt_stride(p.blen) : 0;
+                    it.trace_off = trace_total;
+                    it.trace_bytes = (unsigned)one;
+                    it.ops_off = o.ops_off[s];
+                    it.slot = (int)s;
+                    trace_total += one;
+                    items.push_back(it);
+                }
             }
             std::stable_sort(items.begin(), items.end(), [](const StripItem& p, const StripItem& q) { return p.rows > q.rows; });
-            const size_t ni = items.size();
+            const size_t ni = items.size(), nw = windows.size();
             if (fill_blocks(c, c->strip, ni, 0, &blocks)) return -1;
             if (ensure(c, B_ITEMS, ni * sizeof(StripItem)) || ensure(c, B_TRACE, (size_t)trace_total)) return -1;
+            if (coop && ensure(c, B_WINDOWS, nw * sizeof(WindowItem))) return -1;
             MCHK(hipMemcpyAsync(c->buf[B_ITEMS], items.data(), ni * sizeof(StripItem), hipMemcpyHostToDevice, c->stream));
+            if (coop)
+                MCHK(hipMemcpyAsync(c->buf[B_WINDOWS], windows.data(), nw * sizeof(WindowItem), hipMemcpyHostToDevice, c->stream));
             MCHK(hipMemsetAsync(c->buf[B_CTRL], 0, sizeof(Ctrl), c->stream));
             a.pairs = nullptr;
             a.npairs = (int)ni;
             x.items = (const StripItem*)c->buf[B_ITEMS];
             x.trace = (unsigned char*)c->buf[B_TRACE];
-            WalkStripArgs w{x.items, x.trace, (unsigned char*)c->buf[B_OPS], (WalkState*)c->buf[B_STATE], (int)ni};
             MCHK(hipEventRecord(c->ev0, c->stream));
             MCHK(hipLaunchKernel(c->strip.fn, dim3((unsigned)blocks), dim3(256), kargs, 0, c->stream));
             MCHK(hipGetLastError());
             MCHK(hipEventRecord(c->ev1, c->stream));
-            hipLaunchKernelGGL(sw_matrix_walk_strip_kernel, dim3((unsigned)((ni + 63) / 64)), dim3(64), 0, c->stream, w);
+            if (coop) {
+                WalkWindowArgs w{(const WindowItem*)c->buf[B_WINDOWS], x.trace, (unsigned char*)c->buf[B_OPS],
+                                 (WalkState*)c->buf[B_STATE], (int)nw};
+                hipLaunchKernelGGL(sw_matrix_walk_window_kernel, dim3((unsigned)((nw + 63) / 64)), dim3(64), 0, c->stream, w);
+            } else {
+                WalkStripArgs w{x.items, x.trace, (unsigned char*)c->buf[B_OPS], (WalkState*)c->buf[B_STATE], (int)ni};
+                hipLaunchKernelGGL(sw_matrix_walk_strip_kernel, dim3((unsigned)((ni + 63) / 64)), dim3(64), 0, c->stream, w);
+            }
             MCHK(hipGetLastError());
             MCHK(hipEventRecord(c->ev2, c->stream));
             MCHK(hipMemcpyAsync(o.ws.data(), c->buf[B_STATE], np * sizeof(WalkState), hipMemcpyDeviceToHost, c->stream));
@@ -1949,12 +2191,12 @@ int long_group(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, con
             st.variant += 1;
             st.blocks = (int)blocks;
             st.waves_per_cu = 4 * c->strip.wgs;
-            st.boundary_bytes = std::max(st.boundary_bytes, (long long)(ckpt_total + trace_total));
-            for (const StripItem& it : items) {   // an error stops the call; a walk that goes on stands in the strip on the left
+            st.boundary_bytes = std::max(st.boundary_bytes, held + (long long)trace_total);
+            for (const WindowItem& it : windows) {   // an error stops the call; a walk that goes on stands in the strip left of the window
                 const WalkState& s = o.ws[(size_t)it.slot];
                 const int idx = name_idx ? name_idx[act[(size_t)it.slot].idx] : act[(size_t)it.slot].idx;
                 if (s.err != 0 || s.nops < 0 || s.nops > (long long)it.n + it.m) return walk_failed(what, idx, s.err ? s.err : WALK_OVERRUN);
-                if (!s.done && (it.strip == 0 || s.i != it.strip * ALIGN_STRIP - 1 || s.j < 0 || s.j >= it.rows || s.state < 0 ||
+                if (!s.done && (it.strip0 == 0 || s.i != it.strip0 * ALIGN_STRIP - 1 || s.j < 0 || s.j >= it.rows || s.state < 0 ||
                                 s.state > 1))
                     return walk_failed(what, idx, 0);
             }
@@ -1970,7 +2212,7 @@ int long_group(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, con
 
 int matrix_align_long_device(const sw_matrix* mx, const unsigned char* d_arena, const int64_t* a_off, const int* alen,
                              const int64_t* b_off, const int* blen, const int* name_idx, int npairs, int gap_init,
-                             int gap_ext, const char* what, AlignSink& sink) {
+                             int gap_ext, const char* what, AlignSink& sink, bool coop) {
     const auto t0 = std::chrono::steady_clock::now();
     if (!gaps_ok(gap_init, gap_ext)) return -1;
     const long long trace_budget = sw_get_option("trace_mb") << 20;
@@ -1987,10 +2229,10 @@ int matrix_align_long_device(const sw_matrix* mx, const unsigned char* d_arena, 
     t_fill_ms = t_walk_ms = t_locate_ms = 0.f;
     t_rounds = 0;
     sw_stats st{};
-    st.mode = MODE_MATRIX_LONG;
+    st.mode = coop ? MODE_MATRIX_LONG_COOP : MODE_MATRIX_LONG;
     st.W = TRACE_W;
     st.C = MAT_C;
-    st.items = npairs;
+    st.items = coop ? 0 : npairs;   // coop: the items of the locate launches (locate_coop)
     std::vector<int> ends;
     align_pack(need.data(), npairs, ckpt_budget, ends);   // groups: the checkpoints held at once
     std::vector<DevSeq> act;
@@ -2003,7 +2245,7 @@ int matrix_align_long_device(const sw_matrix* mx, const unsigned char* d_arena, 
                 act.push_back(DevSeq{a_off[k], b_off[k], alen[k], blen[k], k});
                 st.cells += (long long)alen[k] * blen[k];
             }
-        if (!act.empty() && long_group(c, mx, d_arena, act, gap_init, gap_ext, trace_budget, what, name_idx, st, o)) return -1;
+        if (!act.empty() && long_group(c, mx, d_arena, act, gap_init, gap_ext, trace_budget, what, name_idx, st, o, coop)) return -1;
         size_t s = 0;
         for (int k = lo; k < hi; ++k) {
             if (alen[k] == 0 || blen[k] == 0) {
@@ -2171,8 +2413,8 @@ int sw_score_matrix(const sw_matrix* mx, const unsigned char* seq1, const unsign
 }
 
 // sw_align_matrix_batch and sw_align_matrix_long: the checks, the upload, then the traced launches of
-// whole pairs or (long_pairs) the checkpointed traceback
-static int align_host(const char* fn, bool long_pairs, const sw_matrix* mx, const unsigned char* const* a, const int* alen,
+// whole pairs or (long_pairs; 2: on many waves, sw_align_matrix_long_coop) the checkpointed traceback
+static int align_host(const char* fn, int long_pairs, const sw_matrix* mx, const unsigned char* const* a, const int* alen,
                       const unsigned char* const* b, const int* blen, int npairs, int gap_init, int gap_ext,
                       sw_alignment* out, unsigned* cigar, long long cigar_cap, long long* cigar_used, int amode = SW_MODE_LOCAL,
                       int band = -1) {
@@ -2201,7 +2443,7 @@ static int align_host(const char* fn, bool long_pairs, const sw_matrix* mx, cons
     // (synchronous: a refusal below returns before anything is launched or waited for)
     if (total) MCHK(hipMemcpy(c->buf[B_ARENA], arena.data(), total, hipMemcpyHostToDevice));
     if (long_pairs ? matrix_align_long_device(mx, (const unsigned char*)c->buf[B_ARENA], a_off.data(), alen, b_off.data(), blen,
-                                              nullptr, npairs, gap_init, gap_ext, "pair", sink)
+                                              nullptr, npairs, gap_init, gap_ext, "pair", sink, long_pairs == 2)
                    : matrix_align_device(mx, (const unsigned char*)c->buf[B_ARENA], a_off.data(), alen, b_off.data(), blen,
                                          nullptr, npairs, gap_init, gap_ext, "pair", sink, amode, band))
         return -1;
@@ -2225,7 +2467,7 @@ int sw_align_matrix_batch_band(const sw_matrix* mx, const unsigned char* const* 
                                int mode, int band, sw_alignment* out, unsigned* cigar, long long cigar_cap,
                                long long* cigar_used) {
     if (!mode_ok("sw_align_matrix_batch_band", mode) || !band_ok("sw_align_matrix_batch_band", band)) return -1;
-    return align_host("sw_align_matrix_batch_band", false, mx, a, alen, b, blen, npairs, gap_init, gap_ext, out, cigar,
+    return align_host("sw_align_matrix_batch_band", 0, mx, a, alen, b, blen, npairs, gap_init, gap_ext, out, cigar,
                       cigar_cap, cigar_used, mode, band);
 }
 
@@ -2280,22 +2522,40 @@ int sw_align_matrix_batch_mode(const sw_matrix* mx, const unsigned char* const* 
                                const unsigned char* const* b, const int* blen, int npairs, int gap_init, int gap_ext,
                                int mode, sw_alignment* out, unsigned* cigar, long long cigar_cap, long long* cigar_used) {
     if (!mode_ok("sw_align_matrix_batch_mode", mode)) return -1;
-    return align_host("sw_align_matrix_batch_mode", false, mx, a, alen, b, blen, npairs, gap_init, gap_ext, out, cigar,
+    return align_host("sw_align_matrix_batch_mode", 0, mx, a, alen, b, blen, npairs, gap_init, gap_ext, out, cigar,
                       cigar_cap, cigar_used, mode);
 }
 
 int sw_align_matrix_batch(const sw_matrix* mx, const unsigned char* const* a, const int* alen,
                           const unsigned char* const* b, const int* blen, int npairs, int gap_init, int gap_ext,
                           sw_alignment* out, unsigned* cigar, long long cigar_cap, long long* cigar_used) {
-    return align_host("sw_align_matrix_batch", false, mx, a, alen, b, blen, npairs, gap_init, gap_ext, out, cigar, cigar_cap,
+    return align_host("sw_align_matrix_batch", 0, mx, a, alen, b, blen, npairs, gap_init, gap_ext, out, cigar, cigar_cap,
                       cigar_used);
 }
 
 int sw_align_matrix_long(const sw_matrix* mx, const unsigned char* const* a, const int* alen,
                          const unsigned char* const* b, const int* blen, int npairs, int gap_init, int gap_ext,
                          sw_alignment* out, unsigned* cigar, long long cigar_cap, long long* cigar_used) {
-    return align_host("sw_align_matrix_long", true, mx, a, alen, b, blen, npairs, gap_init, gap_ext, out, cigar, cigar_cap,
+    return align_host("sw_align_matrix_long", 1, mx, a, alen, b, blen, npairs, gap_init, gap_ext, out, cigar, cigar_cap,
                       cigar_used);
+}
+
+int sw_align_matrix_long_coop(const sw_matrix* mx, const unsigned char* const* a, const int* alen,
+                              const unsigned char* const* b, const int* blen, int npairs, int gap_init, int gap_ext,
+                              sw_alignment* out, unsigned* cigar, long long cigar_cap, long long* cigar_used) {
+    return align_host("sw_align_matrix_long_coop", 2, mx, a, alen, b, blen, npairs, gap_init, gap_ext, out, cigar, cigar_cap,
+                      cigar_used);
+}
+
+int sw_align_long_coop_plan(int n, int m, sw_align_coop_plan* out) {
+    if (n < 0 || m < 0 || n > MAT_MAX_SEQ || m > MAT_MAX_SEQ || !out) {
+        report_error("sw_align_long_coop_plan: invalid arguments");
+        return -1;
+    }
+    long long ckpt_budget = 0;
+    if (align_ckpt_budget(&ckpt_budget)) return -1;
+    return align_long_coop_plan(n, m, sw_get_option("trace_mb") << 20, ckpt_budget, (int)sw_get_option("long_window"), "pair", 0,
+                                out);
 }
 
 int sw_align_long_plan(int n, int m, sw_align_plan* out) {

@@ -136,8 +136,37 @@ int align_ckpt_budget(long long* bytes);
 // never close a part).  Used for the groups (checkpoint bytes) and for a round's launches (strip traces).
 void align_pack(const long long* need, int n, long long budget, std::vector<int>& end);
 
-// as matrix_align_device, by checkpointed traceback: pairs of any length that the two budgets admit
+// as matrix_align_device, by checkpointed traceback: pairs of any length that the two budgets admit.
+// coop: the locate pass on many waves and rounds that trace a window of strips (below); the same alignments.
 int matrix_align_long_device(const sw_matrix* m, const unsigned char* d_arena, const int64_t* a_off, const int* alen,
                              const int64_t* b_off, const int* blen, const int* name_idx, int npairs, int gap_init,
-                             int gap_ext, const char* what, AlignSink& sink);
+                             int gap_ext, const char* what, AlignSink& sink, bool coop = false);
+
+// ---- long pairs on many waves (include/algoGPU.h sw_align_matrix_long_coop) ----
+// The arithmetic is host only (sw_align_host.cpp); the kernels, the launch and the rounds are in sw_matrix.hip.
+
+constexpr int ALIGN_WINDOW_MAX = 64;   // the most strips of a pair a round fills (option "long_window")
+// What one (pair, strip) item of the cooperative locate pass reports: the largest t of the strip and its
+// cell as i + j and j.  t = 0: the strip has no cell, and d and j mean nothing.
+struct AlignEnd {
+    int t, d, j, pad;
+};
+// The end cell of a pair from the records of its strips: the largest t, then the smallest i + j, then the
+// smallest j -- the rule by which the one-wave locate pass merges its strips and lanes.  *score = 0 (and
+// *ei = *ej = 0) when no record has t > 0.
+void align_merge_ends(const AlignEnd* rec, int nrec, int* score, int* ei, int* ej);
+// progress words (4 B an item, a whole number of 16 bytes) and end-cell records of a locate launch
+long long align_progress_bytes(long long items);
+long long align_end_bytes(long long items);
+// The window of one pair in one round: the strips [strip - g + 1, strip] that are filled at once.
+//   strip_bytes   one strip's trace of the pair at full height (align_strip_trace_bytes(m))
+//   live_bytes    the sum of that over every pair still walking in this round (the pair included)
+//   long_window   option "long_window": 0 automatic, else the window asked for
+// Automatic: g = floor(trace_budget / live_bytes), so that the round's windows fit one launch when its
+// pairs would have; forced: long_window, cut to what fits the budget for this pair alone.  Either way
+// 1 <= g <= min(ALIGN_WINDOW_MAX, strip + 1), and g * strip_bytes <= trace_budget whenever strip_bytes is.
+int align_window(long long strip_bytes, long long live_bytes, long long trace_budget, int long_window, int strip);
+// align_long_plan (the same refusals, the same messages) and what the cooperative path adds
+int align_long_coop_plan(int n, int m, long long trace_budget, long long ckpt_budget, int long_window, const char* what,
+                         int idx, sw_align_coop_plan* out);
 }  // namespace swmi

@@ -162,11 +162,15 @@ class Database:
         _check(lib().sw_db_search_db(self._h, queries._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
         return out
 
-    def align(self, query, indices, matrix, gap_init: int, gap_ext: int, long: bool = False, mode: str = "local") -> list:
+    def align(self, query, indices, matrix, gap_init: int, gap_ext: int, long: bool = False, mode: str = "local",
+              coop: bool = False) -> list:
         """An :class:`Alignment` of ``query`` (seq1) with each record of ``indices``, out of the
         database's device arena (sw_db_align_matrix): only the query is uploaded.  ``long=True``: the
         same alignments by checkpointed traceback (sw_db_align_matrix_long), for records whose whole
-        trace does not fit option ``trace_mb`` (local only).  ``mode`` as in :meth:`search`."""
+        trace does not fit option ``trace_mb`` (local only); with ``coop=True`` as well, on many waves
+        (sw_db_align_matrix_long_coop: ``align_matrix_long(..., coop=True)``).  ``mode`` as in :meth:`search`."""
+        if coop and not long:
+            raise ValueError("coop=True is not built without long=True (it is the checkpointed traceback on many waves)")
         am = self._amode(mode, matrix, "long=True (checkpointed traceback)" if long else None)
         q = _u8(query)
         idx = [int(i) for i in indices]
@@ -178,7 +182,7 @@ class Database:
             return _align_call(lambda out, cig, cap, used: lib().sw_db_align_matrix_mode(
                 self._h, matrix._handle(), _ptr(q), len(q), IDX, n, int(gap_init), int(gap_ext), am, out, cig, cap, used), n,
                 16 * n)
-        f = lib().sw_db_align_matrix_long if long else lib().sw_db_align_matrix
+        f = lib().sw_db_align_matrix_long_coop if coop else lib().sw_db_align_matrix_long if long else lib().sw_db_align_matrix
         return _align_call(lambda out, cig, cap, used: f(
             self._h, matrix._handle(), _ptr(q), len(q), IDX, n, int(gap_init), int(gap_ext), out, cig, cap, used), n,
             max(16 * n, _LONG_CIGAR_CAP if long else 0))

@@ -526,6 +526,58 @@ int  sw_score_matrix_batch_coop(const sw_matrix*, const unsigned char* const* a,
                                 int gap_init, int gap_ext, int mode, int* scores_out);
 int  sw_matrix_coop_plan(int n, int m, int mode, sw_coop_plan* out);
 
+/* ---- long pairs on many waves: cooperative locate, a window of strips a round ----
+ *
+ * sw_align_matrix_long runs the locate pass of a pair on one wave and fills one strip of it a round.
+ * sw_align_matrix_long_coop, sw_db_align_matrix_long_coop: the arguments, checks, refusals, messages and
+ *   cigar protocol of their _long namesakes, and bit for bit the same alignments.  Local alignment only;
+ *   opt-in: no other call takes this path.  Two things differ:
+ *   LOCATE ON MANY WAVES.  A work item is one strip (512 seq1 positions) of one pair, claimed in order;
+ *   the wave of strip s + 1 follows the wave of strip s down the pair through checkpoint column s, by the
+ *   hand-off of sw_score_matrix_batch_coop (a progress word an item, a bounded poll: option "timeout",
+ *   after which the call returns -1 and sw_last_error names the item, its pair and its strip).  The
+ *   checkpoints are the ones sw_align_matrix_long keeps, same bytes, same layout.  Every item reports the
+ *   end cell of its strip in a 16-byte record and the host merges a pair's records by the end-cell rule
+ *   above.  Beyond the checkpoints: 4 bytes of progress word and 16 bytes of record a strip.
+ *   A WINDOW OF STRIPS A ROUND.  The walk's seq2 position never grows as it moves left, so the position j
+ *   at which it enters strip s bounds the rows of every strip further left: a round fills the G strips
+ *   [s - G + 1, s] of a pair at once, each over seq2 positions [0, j] from the checkpoint on its own left,
+ *   on G waves, and the walk runs on through all of them.  Rounds fall from the strips a walk covers to
+ *   ceil(that / G).  Option "long_window" (0 .. 64, default 0; set and read with sw_set_option /
+ *   sw_get_option, read by these two calls and sw_align_long_coop_plan only):
+ *     0        automatic: in every round each pair still walking gets
+ *              G = max(1, min(64, floor(trace_mb bytes / sum over those pairs of one strip's trace)))
+ *     1 .. 64  that G, cut to what fits trace_mb for the pair alone; 1 takes the rounds of
+ *              sw_align_matrix_long
+ *   and either is cut to the strips that are left (s + 1).  A strip is budgeted at its full height, a
+ *   launch never holds more than trace_mb of trace, and a round that does not fit runs as several
+ *   launches as before.  Option "coop_poison" = 1 fills the checkpoint columns with 0x3F bytes before
+ *   the locate launch.
+ *   sw_last_stats: mode 12, W 8, C 64, items = the strips of all pairs (the items of the locate launches),
+ *   variant = strip-fill launches, boundary_bytes = the most device bytes of checkpoints, progress words,
+ *   end records and window traces held at once, kernel_ms = locate plus strip fills;
+ *   sw_last_align_long_ms and sw_last_align_ms as after sw_align_matrix_long.
+ * sw_align_long_coop_plan: no GPU call.  For one n x m pair under the current trace_mb, SWMI_ALIGN_CKPT_MB
+ *   and long_window: strips, checkpoint bytes, the bytes of progress words and of end records, the window
+ *   the pair would get alone in its first round if its walk began in the last strip, and that window's
+ *   trace bytes.  Refuses exactly as sw_align_long_plan refuses. */
+typedef struct {
+    int strips;                     /* = items of the locate launch */
+    long long ckpt_bytes;           /* as sw_align_plan */
+    long long progress_bytes;       /* a 4-byte word a strip, a whole number of 16 bytes */
+    long long end_bytes;            /* a 16-byte end-cell record a strip */
+    int window;                     /* strips a round fills at once */
+    long long window_trace_bytes;   /* window * one strip's trace */
+} sw_align_coop_plan;
+int  sw_align_matrix_long_coop(const sw_matrix*, const unsigned char* const* a, const int* alen,
+                               const unsigned char* const* b, const int* blen, int npairs,
+                               int gap_init, int gap_ext, sw_alignment* out,
+                               unsigned* cigar, long long cigar_cap, long long* cigar_used);
+int  sw_db_align_matrix_long_coop(sw_db*, const sw_matrix*, const unsigned char* query, int qlen,
+                                  const int* record_idx, int nidx, int gap_init, int gap_ext,
+                                  sw_alignment* out, unsigned* cigar, long long cigar_cap, long long* cigar_used);
+int  sw_align_long_coop_plan(int n, int m, sw_align_coop_plan* out);
+
 /* Tuning knobs (process-wide).  Keys:
  *   "W"        columns per lane: 0 = auto, 1, 2, 4, 8
  *   "C"        rows per strip hand-off chunk: 0 = auto, 16, 32, 64

@@ -15,10 +15,22 @@ Without --n: the whole series, N = 8192, 16384, 32768, both kinds, every step a 
 time limit of its own; the first step that fails or runs out of time ends the series (nothing more is started
 on the GPU after it).  Lines are appended to --out (default profiles/align_long.jsonl).
 
+--coop runs sw_align_matrix_long_coop instead (the locate pass on many waves, a window of strips a round;
+DESIGN.md section 17), --window G with option long_window = G (0: automatic).  --reps R (default 1) times R
+calls after the warm-up: the line then carries the median of every device time and, as *_min / *_max, their
+range.  Every line carries a digest of the alignment, so that runs can be compared.
+
+--series-coop: the series of DESIGN.md section 17: N = 8192, 16384, 32768, both kinds, each as the baseline
+(align_matrix_long), --coop automatic and --coop --window 1, 4, 16, five timed calls each, a fresh child
+process a step as above; the series fails when a digest differs from its baseline's.  Lines are appended to
+--out (default then profiles/align_long_coop.jsonl).
+
     python tools/bench_align_long.py [--out FILE] [--limit SECONDS]
-    python tools/bench_align_long.py --n 8192 --kind crossing [--check]
+    python tools/bench_align_long.py --n 8192 --kind crossing [--check] [--coop [--window G]] [--reps R]
+    python tools/bench_align_long.py --series-coop [--out FILE] [--limit SECONDS]
 """
 import argparse
+import hashlib
 import json
 import os
 import subprocess
@@ -56,22 +68,42 @@ def table():
     return t.astype(np.int8)
 
 
-def step(n, kind, check):
+def step(n, kind, check, coop=False, window=0, reps=1):
     import concurrentproject_amd as sw
     a, b = make_pair(n, kind)
-    rec = {"what": "align_long", "n": n, "m": len(b), "kind": kind, "gaps": [12, 1], "stamp": sw.source_stamp()[:12]}
+    rec = {"what": "align_long_coop" if coop else "align_long", "n": n, "m": len(b), "kind": kind, "gaps": [12, 1],
+           "stamp": sw.source_stamp()[:12]}
     with sw.Matrix(SYMBOLS, table()) as mx:
-        rec["plan"] = sw.align_long_plan(n, len(b))
-        sw.align_matrix_long([(a[:600], b[:600])], mx, 12, 1)          # loads the kernels, allocates the context
-        t0 = time.perf_counter()
-        x = sw.align_matrix_long([(a, b)], mx, 12, 1)[0]
-        rec["call_ms"] = round((time.perf_counter() - t0) * 1e3, 3)
+        if coop:
+            sw.set_option("long_window", window)
+            rec.update(long_window=window, plan=sw.align_long_coop_plan(n, len(b)))
+        else:
+            rec["plan"] = sw.align_long_plan(n, len(b))
+        sw.align_matrix_long([(a[:600], b[:600])], mx, 12, 1, coop=coop)   # loads the kernels, allocates the context
+        if reps > 1:
+            sw.align_matrix_long([(a, b)], mx, 12, 1, coop=coop)           # the warm-up call of a timed series
+        runs = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            x = sw.align_matrix_long([(a, b)], mx, 12, 1, coop=coop)[0]
+            ms = dict(sw.last_align_long_ms(), call_ms=(time.perf_counter() - t0) * 1e3)
+            ms["device_ms"] = ms["locate_ms"] + ms["strip_ms"] + ms["walk_ms"]
+            runs.append(ms)
         st = sw.last_stats()
-        ms = sw.last_align_long_ms()
-        rec.update(locate_ms=round(ms["locate_ms"], 3), strip_ms=round(ms["strip_ms"], 3), walk_ms=round(ms["walk_ms"], 3),
-                   rounds=ms["rounds"], strip_launches=st["variant"], boundary_bytes=st["boundary_bytes"], mode=st["mode"],
+        for key in ("call_ms", "locate_ms", "strip_ms", "walk_ms", "device_ms"):
+            v = sorted(r[key] for r in runs)
+            rec[key] = round(float(np.median(v)), 3)
+            if reps > 1:
+                rec[key + "_min"], rec[key + "_max"] = round(v[0], 3), round(v[-1], 3)
+        ms = runs[-1]
+        rec.update(reps=reps, rounds=ms["rounds"], strip_launches=st["variant"], boundary_bytes=st["boundary_bytes"],
+                   mode=st["mode"], items=st["items"],
                    score=x.score, beg1=x.beg1, end1=x.end1, beg2=x.beg2, end2=x.end2, cigar_entries=len(x.ops),
-                   locate_gcups=round(n * len(b) / max(ms["locate_ms"], 1e-9) / 1e6, 3))
+                   digest=hashlib.sha1(repr(x).encode()).hexdigest()[:16],
+                   locate_gcups=round(n * len(b) / max(rec["locate_ms"], 1e-9) / 1e6, 3))
+        if reps > 1:      # a timed series: the device times only
+            print(json.dumps(rec), flush=True)
+            return 0
         sw.score_matrix(a[:600], b[:600], mx, 12, 1)
         t0 = time.perf_counter()
         s = sw.score_matrix(a, b, mx, 12, 1)
@@ -115,15 +147,54 @@ def series(out, limit):
     return 0
 
 
+def series_coop(out, limit):
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    for n in (8192, 16384, 32768):
+        for kind in ("crossing", "random"):
+            base = None
+            for extra in ([], ["--coop"], ["--coop", "--window", "1"], ["--coop", "--window", "4"], ["--coop", "--window", "16"]):
+                cmd = [sys.executable, os.path.abspath(__file__), "--n", str(n), "--kind", kind, "--reps", "5"] + extra
+                try:
+                    r = subprocess.run(cmd, capture_output=True, text=True, timeout=limit)
+                except subprocess.TimeoutExpired:
+                    print("bench_align_long: %d %s %s ran past %d s; stopping" % (n, kind, extra, limit), file=sys.stderr)
+                    return 124
+                sys.stderr.write(r.stderr[-2000:])
+                if r.returncode != 0:
+                    print("bench_align_long: %d %s %s failed (%d); stopping" % (n, kind, extra, r.returncode), file=sys.stderr)
+                    return r.returncode
+                line = r.stdout.strip().split("\n")[-1]
+                print(line, flush=True)
+                with open(out, "a") as f:
+                    f.write(line + "\n")
+                digest = json.loads(line)["digest"]
+                base = base or digest
+                if digest != base:
+                    print("bench_align_long: %d %s %s: another alignment than the baseline's; stopping" % (n, kind, extra),
+                          file=sys.stderr)
+                    return 4
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=0)
     ap.add_argument("--kind", default="crossing", choices=("crossing", "random"))
     ap.add_argument("--check", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "align_long.jsonl"))
+    ap.add_argument("--coop", action="store_true", help="sw_align_matrix_long_coop")
+    ap.add_argument("--window", type=int, default=0, help="with --coop: option long_window (0: automatic)")
+    ap.add_argument("--reps", type=int, default=1, help="timed calls after a warm-up call: medians and ranges")
+    ap.add_argument("--series-coop", action="store_true", help="baseline against --coop, DESIGN.md section 17")
+    ap.add_argument("--out", default=None)
     ap.add_argument("--limit", type=int, default=150, help="seconds a step of the series may take")
     a = ap.parse_args()
-    return step(a.n, a.kind, a.check) if a.n else series(a.out, a.limit)
+    if a.window and not a.coop:
+        ap.error("--window goes with --coop")
+    if a.n:
+        return step(a.n, a.kind, a.check, a.coop, a.window, a.reps)
+    if a.series_coop:
+        return series_coop(a.out or os.path.join(ROOT, "profiles", "align_long_coop.jsonl"), a.limit)
+    return series(a.out or os.path.join(ROOT, "profiles", "align_long.jsonl"), a.limit)
 
 
 if __name__ == "__main__":
