@@ -278,6 +278,15 @@ def lib() -> ctypes.CDLL:
         L.sw_db_align_matrix_long_coop.restype = i
         L.sw_align_long_coop_plan.argtypes = [i, i, ctypes.POINTER(_AlignCoopPlan)]
         L.sw_align_long_coop_plan.restype = i
+    if hasattr(L, "sw_align_matrix_long_mode"):   # the long path, global and semi-global (include/algoGPU.h)
+        for name in ("sw_align_matrix_long_mode", "sw_align_matrix_long_coop_mode"):
+            f = getattr(L, name)
+            f.argtypes = L.sw_align_matrix_batch_mode.argtypes
+            f.restype = i
+        for name in ("sw_db_align_matrix_long_mode", "sw_db_align_matrix_long_coop_mode"):
+            f = getattr(L, name)
+            f.argtypes = L.sw_db_align_matrix_mode.argtypes
+            f.restype = i
     _lib = L
     return L
 
@@ -781,7 +790,7 @@ def align_matrix_batch(pairs: Iterable[Sequence], matrix: Matrix, gap_init: int,
     the library's plain full-matrix aligner on the host (sw_align_matrix_cpu), which gives the same
     result.  Which alignment is reported when several reach the score is fixed (include/algoGPU.h).
     ``mode``: "local", "global" (both sequences end to end) or "semiglobal" (seq1 end to end inside
-    seq2); ``long=True`` is :func:`align_matrix_long`, which is local only.
+    seq2); ``long=True`` is :func:`align_matrix_long` in local mode only (that function takes ``mode=`` itself).
     ``band=B`` (any mode, not with ``long=True``): the alignment within the band of
     :func:`score_matrix_batch`, from the band kernels (sw_align_matrix_batch_band), which hold only the
     band's trace (:func:`band_plan`), or with ``cpu=True`` from the host aligner restricted to it.
@@ -799,7 +808,8 @@ def align_matrix_batch(pairs: Iterable[Sequence], matrix: Matrix, gap_init: int,
         return _align_pairs(f, pairs, matrix, gap_init, gap_ext, mode=am, band=_band(band))
     if long:
         if am != SW_MODE_LOCAL:
-            raise ValueError("mode=%r is not built for long=True (checkpointed traceback): it is local only" % mode)
+            raise ValueError("mode=%r is not built for long=True (checkpointed traceback): it is local only; "
+                             "align_matrix_long(..., mode=%r) aligns long pairs in that mode" % (mode, mode))
         if cpu:
             raise ValueError("long=True is a GPU path: not with cpu=True")
         return align_matrix_long(pairs, matrix, gap_init, gap_ext, coop=coop)
@@ -809,14 +819,22 @@ def align_matrix_batch(pairs: Iterable[Sequence], matrix: Matrix, gap_init: int,
     return _align_pairs(lib().sw_align_matrix_cpu if cpu else lib().sw_align_matrix_batch, pairs, matrix, gap_init, gap_ext)
 
 
-def align_matrix_long(pairs: Iterable[Sequence], matrix: Matrix, gap_init: int, gap_ext: int, coop: bool = False) -> list:
+def align_matrix_long(pairs: Iterable[Sequence], matrix: Matrix, gap_init: int, gap_ext: int, coop: bool = False,
+                      mode: str = "local") -> list:
     """:func:`align_matrix_batch` for pairs whose whole trace does not fit option ``trace_mb``: the same
     alignments, bit for bit, by checkpointed traceback (sw_align_matrix_long): a locate pass keeps the
     right-edge column of every strip of 512 seq1 positions, then the strips are filled again and
     walked one at a time, right to left.  Memory: :func:`align_long_plan`.
     ``coop=True`` (sw_align_matrix_long_coop): the same alignments with the locate pass of a pair on as
     many waves as it has strips and a window of strips filled a round (option ``long_window``), for one or
-    a few long pairs.  Memory: :func:`align_long_coop_plan`."""
+    a few long pairs.  Memory: :func:`align_long_coop_plan`.
+    ``mode`` "global" or "semiglobal" (sw_align_matrix_long_mode, sw_align_matrix_long_coop_mode): the
+    alignments of ``align_matrix_batch(..., mode=mode)``, bit for bit, by the same two paths; the plans do
+    not depend on the mode."""
+    am = _mode(mode)
+    if am != SW_MODE_LOCAL:
+        f = lib().sw_align_matrix_long_coop_mode if coop else lib().sw_align_matrix_long_mode
+        return _align_pairs(f, pairs, matrix, gap_init, gap_ext, _LONG_CIGAR_CAP, mode=am)
     f = lib().sw_align_matrix_long_coop if coop else lib().sw_align_matrix_long
     return _align_pairs(f, pairs, matrix, gap_init, gap_ext, _LONG_CIGAR_CAP)
 

@@ -57,7 +57,8 @@ def main(argv=None) -> int:
     if a.mode != "local" and a.matrix is None:
         ap.error("--mode %s requires --matrix (and --gaps)" % a.mode)
     if a.mode != "local" and a.long:
-        ap.error("--long is local only: not with --mode %s" % a.mode)
+        ap.error("--long is local only: not with --mode %s (Database.align_long(..., mode=...) aligns long records in a mode)"
+                 % a.mode)
     if (a.matrix is None) != (a.gaps is None):
         ap.error("--matrix and --gaps go together")
     matrix, gaps = None, (None, None)

@@ -272,6 +272,31 @@ void align_mode_empty(AlignSink& sink, int k, int alen, int blen, int gap_init, 
     sink.set(k, score, 0, seq1 ? L : 0, 0, seq1 ? 0 : L, ops.data(), L);
 }
 
+// ---- long pairs in a mode: the end record, the end cell and the refusals (sw_matrix_host.h) ----
+
+void align_mode_end(const AlignEnd* rec, int nrec, int* score, int* ei, int* ej) {
+    const AlignEnd none{0, 0, 0, 0};
+    const AlignEnd& r = nrec > 0 ? rec[nrec - 1] : none;   // only the last strip holds column n - 1
+    *score = r.t;
+    *ei = r.d;
+    *ej = r.j;
+}
+
+bool align_long_end_ok(int n, int m, int mode, int ei, int ej) {
+    if (ei < 0 || ei >= n || ej < 0 || ej >= m) return false;
+    if (mode == SW_MODE_LOCAL) return true;
+    return ei == n - 1 && (mode != SW_MODE_GLOBAL || ej == m - 1);
+}
+
+int align_long_mode_check(const char* fn, int mode, const int* alen, const int* blen, const int* name_idx, int npairs,
+                          int gap_init, int gap_ext, const char* what) {
+    if (!mode_ok(fn, mode)) return -1;
+    if (mode == SW_MODE_LOCAL) return 0;
+    for (int k = 0; k < npairs; ++k)
+        if (!mode_range_ok(alen[k], blen[k], gap_init, gap_ext, what, name_idx ? name_idx[k] : k)) return -1;
+    return 0;
+}
+
 // ---- banded alignment: the arithmetic of a band (sw_matrix_host.h) ----
 
 bool band_ok(const char* fn, int band) {

@@ -270,33 +270,38 @@ int search_matrix(sw_db* db, const sw_matrix* mx, const unsigned char* query, in
 }
 
 // the query (seq1, across the lanes) aligned with the chosen records, out of the device arena;
-// long_pairs: by checkpointed traceback (sw_db_align_matrix_long); coop: on many waves (sw_db_align_matrix_long_coop)
+// long_pairs: by checkpointed traceback (sw_db_align_matrix_long); coop: on many waves (sw_db_align_matrix_long_coop);
+// both in amode through the _mode entry points, whose range refusal comes before any device work
 int align_matrix(sw_db* db, const sw_matrix* mx, const unsigned char* query, int qlen, const int* record_idx, int nidx,
                  int gap_init, int gap_ext, AlignSink& sink, bool long_pairs, int amode = SW_MODE_LOCAL, bool coop = false) {
     const int nrec = (int)db->len.size();
     for (int k = 0; k < nidx; ++k)
         if (record_idx[k] < 0 || record_idx[k] >= nrec) {
-            char m[120];
-            std::snprintf(m, sizeof m, "sw_db_align_matrix%s: record index %d (entry %d) is outside [0, %d)",
-                          coop ? "_long_coop" : long_pairs ? "_long" : "", record_idx[k], k, nrec);
+            char m[160];
+            std::snprintf(m, sizeof m, "sw_db_align_matrix%s%s: record index %d (entry %d) is outside [0, %d)",
+                          coop ? "_long_coop" : long_pairs ? "_long" : "", long_pairs && amode != SW_MODE_LOCAL ? "_mode" : "",
+                          record_idx[k], k, nrec);
             report_error(m);
             return -1;
         }
     if (nidx == 0) return 0;
     if (check_records(db, mx) || check_query(db, mx, query, qlen, 0)) return -1;
-    sw_db::Dev* v = nullptr;
-    if (device_arena(db, qlen, &v)) return -1;
     const int64_t qoff = (int64_t)db->res.size();
-    if (qlen > 0) DBCHK(hipMemcpy(v->arena + qoff, query, (size_t)qlen, hipMemcpyHostToDevice));
     std::vector<int64_t> a_off((size_t)nidx, qoff), b_off((size_t)nidx);
     std::vector<int> alen((size_t)nidx, qlen), blen((size_t)nidx);
     for (int k = 0; k < nidx; ++k) {
         b_off[(size_t)k] = db->off[(size_t)record_idx[k]];
         blen[(size_t)k] = db->len[(size_t)record_idx[k]];
     }
+    if (long_pairs && align_long_mode_check(coop ? "sw_db_align_matrix_long_coop_mode" : "sw_db_align_matrix_long_mode", amode,
+                                            alen.data(), blen.data(), record_idx, nidx, gap_init, gap_ext, "record"))
+        return -1;
+    sw_db::Dev* v = nullptr;
+    if (device_arena(db, qlen, &v)) return -1;
+    if (qlen > 0) DBCHK(hipMemcpy(v->arena + qoff, query, (size_t)qlen, hipMemcpyHostToDevice));
     if (long_pairs)
         return matrix_align_long_device(mx, v->arena, a_off.data(), alen.data(), b_off.data(), blen.data(), record_idx, nidx,
-                                        gap_init, gap_ext, "record", sink, coop);
+                                        gap_init, gap_ext, "record", sink, coop, amode);
     return matrix_align_device(mx, v->arena, a_off.data(), alen.data(), b_off.data(), blen.data(), record_idx, nidx, gap_init,
                                gap_ext, "record", sink, amode);
 }
@@ -402,6 +407,41 @@ int sw_db_align_matrix_long_coop(sw_db* db, const sw_matrix* mx, const unsigned 
     AlignSink sink{out, {}};
     if (align_matrix(db, mx, query, qlen, record_idx, nidx, gap_init, gap_ext, sink, true, SW_MODE_LOCAL, true)) return -1;
     return sink.finish(cigar, cigar_cap, cigar_used);
+}
+
+// the long path in a mode; local mode through them is the calls above
+static int db_align_long_mode(const char* fn, bool coop, sw_db* db, const sw_matrix* mx, const unsigned char* query, int qlen,
+                              const int* record_idx, int nidx, int gap_init, int gap_ext, int mode, sw_alignment* out,
+                              unsigned* cigar, long long cigar_cap, long long* cigar_used) {
+    if (!mode_ok(fn, mode)) return -1;
+    if (mode == SW_MODE_LOCAL)
+        return (coop ? sw_db_align_matrix_long_coop : sw_db_align_matrix_long)(db, mx, query, qlen, record_idx, nidx, gap_init,
+                                                                               gap_ext, out, cigar, cigar_cap, cigar_used);
+    if (!db || !mx || qlen < 0 || (qlen > 0 && !query) || nidx < 0 || cigar_cap < 0 || !cigar_used ||
+        (cigar_cap > 0 && !cigar) || (nidx > 0 && (!record_idx || !out))) {
+        char m[96];
+        std::snprintf(m, sizeof m, "%s: invalid arguments", fn);
+        report_error(m);
+        return -1;
+    }
+    std::lock_guard<std::mutex> g(db->mu);
+    AlignSink sink{out, {}};
+    if (align_matrix(db, mx, query, qlen, record_idx, nidx, gap_init, gap_ext, sink, true, mode, coop)) return -1;
+    return sink.finish(cigar, cigar_cap, cigar_used);
+}
+
+int sw_db_align_matrix_long_mode(sw_db* db, const sw_matrix* mx, const unsigned char* query, int qlen, const int* record_idx,
+                                 int nidx, int gap_init, int gap_ext, int mode, sw_alignment* out, unsigned* cigar,
+                                 long long cigar_cap, long long* cigar_used) {
+    return db_align_long_mode("sw_db_align_matrix_long_mode", false, db, mx, query, qlen, record_idx, nidx, gap_init, gap_ext,
+                              mode, out, cigar, cigar_cap, cigar_used);
+}
+
+int sw_db_align_matrix_long_coop_mode(sw_db* db, const sw_matrix* mx, const unsigned char* query, int qlen,
+                                      const int* record_idx, int nidx, int gap_init, int gap_ext, int mode, sw_alignment* out,
+                                      unsigned* cigar, long long cigar_cap, long long* cigar_used) {
+    return db_align_long_mode("sw_db_align_matrix_long_coop_mode", true, db, mx, query, qlen, record_idx, nidx, gap_init,
+                              gap_ext, mode, out, cigar, cigar_cap, cigar_used);
 }
 
 int sw_db_search(sw_db* db, const unsigned char* query, int qlen, int* scores_out) {

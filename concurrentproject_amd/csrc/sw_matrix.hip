@@ -43,7 +43,7 @@
 // ALIGNMENT MODES.  Everything above is local alignment.  Global and semi-global alignment
 // (include/algoGPU.h SW_MODE_*) are a third template parameter of the same
 // step, pair loop and kernel (AM, below): no clamp, borders made by the set-up and the inflow, the
-// end read from one column.  The long path is local only.
+// end read from one column.  The long path takes them too (LONG PAIRS IN A MODE below).
 //
 // BANDED ALIGNMENT (include/algoGPU.h sw_*_band) is a fourth template parameter
 // (BAND, below) of the step, the pair loop and the kernel: a strip runs only the chunks that hold
@@ -60,7 +60,7 @@
 //
 // LONG PAIRS ON MANY WAVES (include/algoGPU.h sw_align_matrix_long_coop) puts the locate pass of
 // the long path on that hand-off -- the edge columns are the checkpoint columns -- and lets a round fill a window of
-// consecutive strips of a pair, which do not depend on one another.  Opt-in, local only; the same alignments.
+// consecutive strips of a pair, which do not depend on one another.  Opt-in, every mode; the same alignments.
 #include "sw_device.h"
 #include "sw_matrix_host.h"
 #include "../../include/algoGPU.h"
@@ -192,7 +192,6 @@ constexpr int MAT_NEG = -(1 << 30);
 template <int W, int MODE, int AM = AM_LOCAL, bool BAND = false>
 struct MStrip {
     static_assert(MODE == M_SCORE || W == TRACE_W, "a traced step stores one dword a lane");
-    static_assert(AM == AM_LOCAL || MODE != M_LOCATE, "the long path is local only");
     static_assert(!BAND || MODE != M_LOCATE, "the long path has no band");
     int cb[W], tb[W];                       // LDS offset of the column's table row / bias
     int hgA[W], hgB[W], eh[W], r[W], fh[W]; // DP state, as Strip (sw_kernels.hip)
@@ -816,6 +815,13 @@ __global__ void __launch_bounds__(64) sw_matrix_walk_kernel(WalkArgs w) {
 // until the walk ends or leaves the strip on the left.  The host runs the rounds (below).  As in the
 // kernels above no wave waits for another and every loop is bounded: chunks of the strip, n + m
 // operations.
+//
+// LONG PAIRS IN A MODE (sw_align_matrix_long_mode).  The three fill kernels of this path
+// -- locate, strip fill and, further down, the cooperative locate -- are templates on AM as every other fill
+// kernel is, and the two resumable walks take the mode at run time, as sw_matrix_walk_kernel does.  Global and
+// semi-global: the end is read from column n - 1, so it lies in the last strip and there is no merge of strips;
+// a strip is filled again under AM's borders; every pair walks, whatever its score; and a walk may end in any
+// strip by leaving the matrix at j < 0, its leading I run covering the strips still to the left.
 
 struct LongPair {           // locate: per item, beside its MatPair
     uint64_t ckpt_off;      // bytes, from LongArgs::ckpt: checkpoint column 0 of the pair
@@ -844,8 +850,11 @@ struct LongArgs {
     unsigned char* trace;
 };
 
-// The locate pass: sw_matrix_kernel<8, true> without the trace, every strip's right edge kept.
-// a.res[out_idx] receives score, ei, ej (the first half of a TraceRes).
+// The locate pass: sw_matrix_kernel<8, true, AM> without the trace, every strip's right edge kept.
+// a.res[out_idx] receives score, ei, ej (the first half of a TraceRes).  AM != AM_LOCAL: matrix_pair's own
+// mode code -- AM's setup(), the left border as strip 0's inflow, the strict end update on column n - 1 --
+// so ei = n - 1, and there is no merge of strips: the end cell is in the last one.
+template <int AM>
 __global__ void __launch_bounds__(256) sw_matrix_locate_kernel(MatArgs a, LongArgs x) {
     const MatLds s = matrix_stage(a);
     const int lane = threadIdx.x & 63;
@@ -858,7 +867,7 @@ __global__ void __launch_bounds__(256) sw_matrix_locate_kernel(MatArgs a, LongAr
         const LongPair lraw = x.lp[item];
         unsigned char* ckpt = x.ckpt + uniform64(lraw.ckpt_off);
         const unsigned stride = __builtin_amdgcn_readfirstlane(lraw.ckpt_stride);
-        matrix_pair<TRACE_W, M_LOCATE>(a, pd, wp, lane, nullptr, s.tab, s.code, ckpt, stride);
+        matrix_pair<TRACE_W, M_LOCATE, AM>(a, pd, wp, lane, nullptr, s.tab, s.code, ckpt, stride);
     }
 }
 
@@ -866,6 +875,10 @@ __global__ void __launch_bounds__(256) sw_matrix_locate_kernel(MatArgs a, LongAr
 // (the border for strip 0), no outflow, no end cell.  Every store of a step is inside the item's
 // buffer by construction (align_strip_trace_bytes(rows) <= trace_bytes); the resource drops
 // whatever is not.
+// AM != AM_LOCAL: AM's setup() builds the top border H[512 * strip][-1] from the strip index, strip 0 takes
+// the left border H[-1][j] as its inflow chunk by chunk (as matrix_pair does), and the step's bookkeeping
+// of column n - 1 runs on a pair of `rows` rows and is dropped: the locate pass has the end.
+template <int AM>
 __device__ void matrix_strip_fill(const MatArgs& a, const LongArgs& x, const StripItem& it, const int lane,
                                   const signed char* s_tab, const unsigned char* s_code) {
     constexpr int W = TRACE_W, SW = 64 * W, C = MAT_C;
@@ -888,11 +901,16 @@ __device__ void matrix_strip_fill(const MatArgs& a, const LongArgs& x, const Str
         __builtin_amdgcn_make_buffer_rsrc(x.trace + it.trace_off, 0, (int)it.trace_bytes, RSRC_FLAGS);
     const int nchunks = (m + SW - 1 + C - 1) / C;
     unsigned toff = (unsigned)lane * 4u;
-    MStrip<W, M_TRACE> S;
+    MStrip<W, M_TRACE, AM> S;
     S.setup(a, pd, it.strip, lane, s_code);
-    S.M = 0;
-    S.Mkp = 0;
-    S.kp8 = 0;
+    if constexpr (AM == AM_LOCAL) {
+        S.M = 0;
+        S.Mkp = 0;
+        S.kp8 = 0;
+    } else {
+        S.M = MAT_NEG;
+        S.Mj = 0;
+    }
     unsigned raw_nxt = mat_fetch_raw(row_rsrc, 0, lane, m);
     u32x2 g_nxt = has_in ? mat_fetch_edge(in_rsrc, 0, lane, m) : u32x2{0u, 0u};
     for (int c = 0; c < nchunks; ++c) {
@@ -903,12 +921,19 @@ __device__ void matrix_strip_fill(const MatArgs& a, const LongArgs& x, const Str
         if (has_in) g_nxt = mat_fetch_edge(in_rsrc, k0 + C, lane, m);
         const bool live = k0 + lane < m;
         S.IOR = live ? (int)s_code[raw & 0xFFu] : a.k;
-        S.IOH = has_in && live ? (int)g.x : -go;
-        S.IOE = has_in && live ? (int)g.y : -ge;
+        if constexpr (AM == AM_LOCAL) {
+            S.IOH = has_in && live ? (int)g.x : -go;
+            S.IOE = has_in && live ? (int)g.y : -ge;
+        } else {   // strip 0: the left border H[-1][j], and no E to extend out of it
+            const int lb = AM == AM_GLOBAL ? -(go + (k0 + lane) * min(go, ge)) - go : -go;
+            S.IOH = has_in && live ? (int)g.x : lb;
+            S.IOE = has_in && live ? (int)g.y : MAT_NEG;
+        }
         S.run(l63, go, ge, s_tab, trc, toff);
     }
 }
 
+template <int AM>
 __global__ void __launch_bounds__(256) sw_matrix_strip_kernel(MatArgs a, LongArgs x) {
     const MatLds s = matrix_stage(a);
     const int lane = threadIdx.x & 63;
@@ -924,22 +949,26 @@ __global__ void __launch_bounds__(256) sw_matrix_strip_kernel(MatArgs a, LongArg
         it.strip = __builtin_amdgcn_readfirstlane(raw.strip);
         it.rows = __builtin_amdgcn_readfirstlane(raw.rows);
         it.trace_bytes = __builtin_amdgcn_readfirstlane(raw.trace_bytes);
-        matrix_strip_fill(a, x, it, lane, s.tab, s.code);
+        matrix_strip_fill<AM>(a, x, it, lane, s.tab, s.code);
     }
 }
 
 // The resumable walk: matrix_walk from the pair's WalkState, while the cell is in the item's strip;
 // the cell at column i - 512 * strip of the one-strip buffer (StripTrace with strip0 = strip, so the
 // steps of a strip multiply 0).  Operations are
-// appended at the running offset nops.  done: a cell with H = 0 met in state H, or i < 0, or j < 0.
+// appended at the running offset nops.  done: a cell with H = 0 met in state H (local), or i < 0, or j < 0.
 // Otherwise the walk left the strip through its left side, in state H (after an M) or E (after an
 // I): the state the last cell's extend bit decided, exactly as inside a strip.
+// amode != SW_MODE_LOCAL: done also says that the walk has left the matrix and matrix_walk has written the
+// leading run and set i or j to -1.  A leading I run may cover every strip still to the left: it is
+// i + 1 <= n operations into the pair's n + m bytes, and no further round reads a trace for it.
 struct WalkStripArgs {
     const StripItem* items;
     const unsigned char* trace;
     unsigned char* ops;
     WalkState* st;
     int nitems;
+    int amode;   // SW_MODE_*
 };
 
 __global__ void __launch_bounds__(64) sw_matrix_walk_strip_kernel(WalkStripArgs w) {
@@ -954,7 +983,7 @@ __global__ void __launch_bounds__(64) sw_matrix_walk_strip_kernel(WalkStripArgs 
         s.err = WALK_RANGE;   // (matrix_walk checks the cell against the pair)
     else
         matrix_walk(StripTrace{it.strip, 0, it.trace_bytes}, w.trace + it.trace_off, w.ops + it.ops_off, it.n, it.m,
-                    SW_MODE_LOCAL, s);
+                    w.amode, s);
     *static_cast<Walk*>(st) = s;
 }
 
@@ -1014,10 +1043,13 @@ __device__ __noinline__ int coop_await(__amdgpu_buffer_rsrc_t prog_rsrc, __amdgp
 }
 
 // One strip of one pair.  false: the launch has failed (coop_await) and the wave leaves.
-// MODE: M_SCORE, the score path; M_LOCATE (local, W = TRACE_W, seq1 across the lanes), the cooperative
+// MODE: M_SCORE, the score path; M_LOCATE (W = TRACE_W, seq1 across the lanes), the cooperative
 // locate pass of LONG PAIRS ON MANY WAVES below: the same consumer and producer on the pair's checkpoint
 // columns, the end-cell bookkeeping of matrix_pair for this one strip, and an end-cell record an item
 // instead of the atomicMax.  The score instantiations are the code they were.
+// M_LOCATE in a mode (AM != AM_LOCAL): only the last strip holds column n - 1, so only its item has an end:
+// it reduces (M, Mj) over its lanes as matrix_pair does and stores {score, n - 1, ej} as its record; every
+// other item's store is out of range, and the host reads the last strip's record (align_mode_end).
 template <int W, int AM, int MODE = M_SCORE>
 __device__ __forceinline__ bool matrix_coop_strip(const MatArgs& a, const CoopArgs& x, const MatPair& pd, const CoopPair& cp,
                                                   const unsigned item, const int strip, const int lane,
@@ -1047,6 +1079,7 @@ __device__ __forceinline__ bool matrix_coop_strip(const MatArgs& a, const CoopAr
     if constexpr (MODE == M_LOCATE) {   // as matrix_pair starts every strip
         S.Mkp = 0;
         S.kp8 = 0;
+        if constexpr (AM != AM_LOCAL) S.Mj = 0;
     }
     // THE CONSUMER.  `seen` rows of the left edge are known to be stored (strip 0 has no left edge).
     // Before the fetch of rows [k, k + 64) the word of item - 1 -- strip - 1 of this pair: items are
@@ -1103,6 +1136,22 @@ __device__ __forceinline__ bool matrix_coop_strip(const MatArgs& a, const CoopAr
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __builtin_amdgcn_raw_buffer_store_b32((unsigned)pub, prog_rsrc, lane == 0 ? item * 4u : OOR, 0, AUX_SC1);
         }
+    }
+    if constexpr (MODE == M_LOCATE && AM != AM_LOCAL) {   // one lane of the last strip holds the end; M is H - G_INIT
+        int M = S.M, J = S.Mj;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const int oM = __shfl_xor(M, off), oJ = __shfl_xor(J, off);
+            J = oM > M ? oJ : J;
+            M = max(M, oM);
+        }
+        // lane 0's store without a branch on the lane (the comment at matrix_pair's score store)
+        const int jlo = AM == AM_GLOBAL ? m - 1 : 0;
+        const __amdgpu_buffer_rsrc_t end_rsrc =
+            __builtin_amdgcn_make_buffer_rsrc(x.ends, 0, (int)((unsigned)a.npairs * (unsigned)sizeof(AlignEnd)), RSRC_FLAGS);
+        __builtin_amdgcn_raw_buffer_store_b128(u32x4{(unsigned)(M + go), (unsigned)(pd.n - 1), (unsigned)(J + jlo), 0u}, end_rsrc,
+                                               lane == 0 && !has_out ? item * (unsigned)sizeof(AlignEnd) : OOR, 0, 0);
+        return true;
     }
     if constexpr (MODE == M_LOCATE) {
         // The item's end cell: the lane's cell of this strip (column lane * W + p, reached at step k), the
@@ -1180,6 +1229,10 @@ __global__ void __launch_bounds__(256) sw_matrix_coop_kernel(MatArgs a, CoopArgs
 // edge, and an end-cell record an item.  The hand-off and the progress argument are the ones above,
 // unchanged: items are claimed in the same order and an item waits for the same one item.  It writes
 // exactly what sw_matrix_locate_kernel writes, so sw_matrix_strip_kernel reads it as it is.
+// In a mode (AM != AM_LOCAL) the progress argument above holds word for word: the claim order, the one item
+// an item waits for, what it polls and what it publishes are the shared code, and none of them depends on
+// AM.  What AM changes is the arithmetic of a step and which item stores an end record.
+template <int AM>
 __global__ void __launch_bounds__(256) sw_matrix_locate_coop_kernel(MatArgs a, CoopArgs x) {
     const MatLds s = matrix_stage(a);
     const int lane = threadIdx.x & 63;
@@ -1197,7 +1250,7 @@ __global__ void __launch_bounds__(256) sw_matrix_locate_coop_kernel(MatArgs a, C
         cp.edge_off = uniform64(craw.edge_off);
         cp.stride = __builtin_amdgcn_readfirstlane(craw.stride);
         cp.strips = __builtin_amdgcn_readfirstlane(craw.strips);
-        if (!matrix_coop_strip<TRACE_W, AM_LOCAL, M_LOCATE>(a, x, pd, cp, item, strip, lane, s.tab, s.code)) return;
+        if (!matrix_coop_strip<TRACE_W, AM, M_LOCATE>(a, x, pd, cp, item, strip, lane, s.tab, s.code)) return;
     }
 }
 
@@ -1223,6 +1276,7 @@ struct WalkWindowArgs {
     unsigned char* ops;
     WalkState* st;
     int nitems;
+    int amode;   // SW_MODE_*
 };
 
 // sw_matrix_walk_strip_kernel for a window; a window of one strip walks what that kernel walks.
@@ -1238,7 +1292,7 @@ __global__ void __launch_bounds__(64) sw_matrix_walk_window_kernel(WalkWindowArg
         s.err = WALK_RANGE;   // (matrix_walk checks the cell against the pair and the window's bytes)
     else
         matrix_walk(StripTrace{it.strip0, it.steps, it.trace_bytes}, w.trace + it.trace_off, w.ops + it.ops_off, it.n, it.m,
-                    SW_MODE_LOCAL, s);
+                    w.amode, s);
     *static_cast<Walk*>(st) = s;
 }
 
@@ -1280,6 +1334,13 @@ void name_coop_kernels(FillKernel (&row)[4]) {   // the cooperative score kernel
     row[3].fn = (const void*)sw_matrix_coop_kernel<8, AM>;
 }
 
+template <int AM>
+void name_long_kernels(FillKernel& locate, FillKernel& locate_coop, FillKernel& strip) {   // the long path's fills
+    locate.fn = (const void*)sw_matrix_locate_kernel<AM>;
+    locate_coop.fn = (const void*)sw_matrix_locate_coop_kernel<AM>;
+    strip.fn = (const void*)sw_matrix_strip_kernel<AM>;
+}
+
 // device memory and a stream per (thread, device), as the engine's own context (sw_engine.hip)
 enum {
     B_PAIRS = 0, B_CTRL, B_SCRATCH, B_ARENA, B_SCORES,   // every launch
@@ -1296,10 +1357,13 @@ struct MatCtx {
     void* buf[B_COUNT] = {};
     size_t cap[B_COUNT] = {};
     FillKernel fill[2][3][5];   // [band][SW_MODE_*][index into W_OF, or WI_TRACED]
-    FillKernel locate{(const void*)sw_matrix_locate_kernel}, strip{(const void*)sw_matrix_strip_kernel};
+    FillKernel locate[3], strip[3];   // [SW_MODE_*]: the long path
     FillKernel coop[3][4];      // [SW_MODE_*][index into W_OF]
-    FillKernel locate_coop{(const void*)sw_matrix_locate_coop_kernel};
+    FillKernel locate_coop[3];  // [SW_MODE_*]
     MatCtx() {
+        name_long_kernels<AM_LOCAL>(locate[AM_LOCAL], locate_coop[AM_LOCAL], strip[AM_LOCAL]);
+        name_long_kernels<AM_GLOBAL>(locate[AM_GLOBAL], locate_coop[AM_GLOBAL], strip[AM_GLOBAL]);
+        name_long_kernels<AM_SEMI>(locate[AM_SEMI], locate_coop[AM_SEMI], strip[AM_SEMI]);
         name_coop_kernels<AM_LOCAL>(coop[AM_LOCAL]);
         name_coop_kernels<AM_GLOBAL>(coop[AM_GLOBAL]);
         name_coop_kernels<AM_SEMI>(coop[AM_SEMI]);
@@ -1932,11 +1996,14 @@ constexpr int MODE_MATRIX_LONG_COOP = 12;   // sw_align_matrix_long_coop: cooper
 // The cooperative locate launch of one group (LONG PAIRS ON MANY WAVES above): the items are the strips of
 // its pairs, pair-major and strip-minor, the pairs longest first (pairs[k], with the checkpoint column 0 of
 // pairs[k] at byte ckpt_off[pairs[k].out_idx] of B_CKPT).  o.res[slot] receives score, ei, ej of every pair,
-// merged on the host from the records of its strips.  a: the launch's arguments, which the strip fills go on
-// using.  *extra: the bytes of progress words and end records.
+// merged on the host from the records of its strips (local), or read from the record of its last strip (a mode:
+// align_mode_end).  a: the launch's arguments, which the strip fills go on using.  *extra: the bytes of
+// progress words and end records.
 int locate_coop(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, const std::vector<MatPair>& pairs,
                 const std::vector<uint64_t>& ckpt_off, uint64_t ckpt_total, int gap_init, int gap_ext, const char* fn,
-                const char* what, const std::vector<int>& name_of, MatArgs& a, sw_stats& st, LongOut& o, long long* extra) {
+                const char* what, const std::vector<int>& name_of, MatArgs& a, sw_stats& st, LongOut& o, long long* extra,
+                int amode) {
+    FillKernel& kern = c->locate_coop[amode];
     const size_t np = pairs.size();
     std::vector<CoopPair> cp(np);
     std::vector<CoopItem> items;
@@ -1950,7 +2017,7 @@ int locate_coop(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, co
     const size_t ni = items.size();
     const size_t prog_bytes = (size_t)align_progress_bytes((long long)ni), end_bytes = (size_t)align_end_bytes((long long)ni);
     long long blocks = 0;
-    if (fill_blocks(c, c->locate_coop, ni, 0, &blocks) || fill_args(c, mx, d_arena, pairs, (int)np, gap_init, gap_ext, 0, blocks, a) ||
+    if (fill_blocks(c, kern, ni, 0, &blocks) || fill_args(c, mx, d_arena, pairs, (int)np, gap_init, gap_ext, 0, blocks, a) ||
         ensure(c, B_CPAIRS, np * sizeof(CoopPair)) || ensure(c, B_CITEMS, ni * sizeof(CoopItem)) ||
         ensure(c, B_PROGRESS, prog_bytes) || ensure(c, B_ENDS, end_bytes))
         return -1;
@@ -1970,7 +2037,7 @@ int locate_coop(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, co
     x.ends = (AlignEnd*)c->buf[B_ENDS];
     void* kargs[] = {&a, &x};
     MCHK(hipEventRecord(c->ev0, c->stream));
-    MCHK(hipLaunchKernel(c->locate_coop.fn, dim3((unsigned)blocks), dim3(256), kargs, 0, c->stream));
+    MCHK(hipLaunchKernel(kern.fn, dim3((unsigned)blocks), dim3(256), kargs, 0, c->stream));
     MCHK(hipGetLastError());
     MCHK(hipEventRecord(c->ev1, c->stream));
     Ctrl ctrl{};
@@ -1984,7 +2051,7 @@ int locate_coop(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, co
     t_locate_ms += ms;
     st.items += (int)ni;
     st.blocks = (int)blocks;
-    st.waves_per_cu = 4 * c->locate_coop.wgs;
+    st.waves_per_cu = 4 * kern.wgs;
     *extra = (long long)(prog_bytes + end_bytes);
     if (ctrl.error != 0) {
         const unsigned it = std::min<unsigned>(ctrl.err_item, (unsigned)ni - 1);
@@ -2000,7 +2067,8 @@ int locate_coop(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, co
     o.res.assign(np, TraceRes{});
     for (size_t k = 0; k < np; ++k) {
         TraceRes& r = o.res[(size_t)pairs[k].out_idx];
-        align_merge_ends(ends.data() + first[k], cp[k].strips, &r.score, &r.ei, &r.ej);
+        if (amode == AM_LOCAL) align_merge_ends(ends.data() + first[k], cp[k].strips, &r.score, &r.ei, &r.ej);
+        else align_mode_end(ends.data() + first[k], cp[k].strips, &r.score, &r.ei, &r.ej);
     }
     return 0;
 }
@@ -2008,9 +2076,13 @@ int locate_coop(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, co
 // coop: the cooperative locate launch instead of the one-wave one, and rounds that fill a window of strips
 // a pair (align_window) and walk it with sw_matrix_walk_window_kernel; else a window is one strip and the
 // launches are the ones they were.
+// amode != AM_LOCAL (LONG PAIRS IN A MODE): the kernels of that mode, and every pair walks,
+// whatever its score, from (n - 1, ej) in state H.
 int long_group(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, const std::vector<DevSeq>& act, int gap_init,
                int gap_ext, long long trace_budget, const char* what, const int* name_idx, sw_stats& st, LongOut& o,
-               bool coop = false) {
+               bool coop, int amode) {
+    FillKernel& k_locate = c->locate[amode];
+    FillKernel& k_strip = c->strip[amode];
     const size_t np = act.size();
     const std::vector<int> order = longest_first(act);
     std::vector<uint64_t> ckpt_off(np);
@@ -2043,12 +2115,13 @@ int long_group(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, con
         for (size_t s = 0; s < np; ++s) name_of[s] = name_idx ? name_idx[act[s].idx] : act[s].idx;
         long long extra = 0;
         if (locate_coop(c, mx, d_arena, pairs, ckpt_off, ckpt_total, gap_init, gap_ext,
-                        name_idx ? "sw_db_align_matrix_long_coop" : "sw_align_matrix_long_coop", what, name_of, a, st, o, &extra))
+                        name_idx ? "sw_db_align_matrix_long_coop" : "sw_align_matrix_long_coop", what, name_of, a, st, o, &extra,
+                        amode))
             return -1;
         held += extra;
         x.ckpt = (unsigned char*)c->buf[B_CKPT];
     } else {
-        if (fill_blocks(c, c->locate, np, 0, &blocks) || fill_args(c, mx, d_arena, pairs, (int)np, gap_init, gap_ext, 0, blocks, a) ||
+        if (fill_blocks(c, k_locate, np, 0, &blocks) || fill_args(c, mx, d_arena, pairs, (int)np, gap_init, gap_ext, 0, blocks, a) ||
             ensure(c, B_LONG, np * sizeof(LongPair)) || ensure(c, B_RES, np * sizeof(TraceRes)))
             return -1;
         MCHK(hipMemcpyAsync(c->buf[B_LONG], lp.data(), np * sizeof(LongPair), hipMemcpyHostToDevice, c->stream));
@@ -2058,7 +2131,7 @@ int long_group(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, con
         x.ckpt = (unsigned char*)c->buf[B_CKPT];
 
         MCHK(hipEventRecord(c->ev0, c->stream));
-        MCHK(hipLaunchKernel(c->locate.fn, dim3((unsigned)blocks), dim3(256), kargs, 0, c->stream));
+        MCHK(hipLaunchKernel(k_locate.fn, dim3((unsigned)blocks), dim3(256), kargs, 0, c->stream));
         MCHK(hipGetLastError());
         MCHK(hipEventRecord(c->ev1, c->stream));
         o.res.resize(np);
@@ -2069,19 +2142,21 @@ int long_group(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, con
         t_fill_ms += ms;
         t_locate_ms += ms;
         st.blocks = (int)blocks;
-        st.waves_per_cu = 4 * c->locate.wgs;
+        st.waves_per_cu = 4 * k_locate.wgs;
     }
     st.boundary_bytes = std::max(st.boundary_bytes, held);
 
-    // every walk starts at its end cell in state H; a pair without an alignment never walks
+    // every walk starts at its end cell in state H; a local pair without an alignment never walks, and in a
+    // mode every pair walks, from column n - 1 (global: from the corner), whatever its score
     o.ws.assign(np, WalkState{});
     for (size_t s = 0; s < np; ++s) {
         const TraceRes& r = o.res[s];
-        if (r.score > 0 && (r.ei < 0 || r.ei >= act[s].alen || r.ej < 0 || r.ej >= act[s].blen))
+        const bool walks = amode != AM_LOCAL || r.score > 0;
+        if (walks && !align_long_end_ok(act[s].alen, act[s].blen, amode, r.ei, r.ej))
             return walk_failed(what, name_idx ? name_idx[act[s].idx] : act[s].idx, WALK_RANGE);
         o.ws[s].i = r.ei;
         o.ws[s].j = r.ej;
-        o.ws[s].done = r.score > 0 ? 0 : 1;
+        o.ws[s].done = walks ? 0 : 1;
     }
     MCHK(hipMemcpyAsync(c->buf[B_STATE], o.ws.data(), np * sizeof(WalkState), hipMemcpyHostToDevice, c->stream));
 
@@ -2156,7 +2231,7 @@ int long_group(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, con
             }
             std::stable_sort(items.begin(), items.end(), [](const StripItem& p, const StripItem& q) { return p.rows > q.rows; });
             const size_t ni = items.size(), nw = windows.size();
-            if (fill_blocks(c, c->strip, ni, 0, &blocks)) return -1;
+            if (fill_blocks(c, k_strip, ni, 0, &blocks)) return -1;
             if (ensure(c, B_ITEMS, ni * sizeof(StripItem)) || ensure(c, B_TRACE, (size_t)trace_total)) return -1;
             if (coop && ensure(c, B_WINDOWS, nw * sizeof(WindowItem))) return -1;
             MCHK(hipMemcpyAsync(c->buf[B_ITEMS], items.data(), ni * sizeof(StripItem), hipMemcpyHostToDevice, c->stream));
@@ -2168,15 +2243,15 @@ int long_group(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, con
             x.items = (const StripItem*)c->buf[B_ITEMS];
             x.trace = (unsigned char*)c->buf[B_TRACE];
             MCHK(hipEventRecord(c->ev0, c->stream));
-            MCHK(hipLaunchKernel(c->strip.fn, dim3((unsigned)blocks), dim3(256), kargs, 0, c->stream));
+            MCHK(hipLaunchKernel(k_strip.fn, dim3((unsigned)blocks), dim3(256), kargs, 0, c->stream));
             MCHK(hipGetLastError());
             MCHK(hipEventRecord(c->ev1, c->stream));
             if (coop) {
                 WalkWindowArgs w{(const WindowItem*)c->buf[B_WINDOWS], x.trace, (unsigned char*)c->buf[B_OPS],
-                                 (WalkState*)c->buf[B_STATE], (int)nw};
+                                 (WalkState*)c->buf[B_STATE], (int)nw, amode};
                 hipLaunchKernelGGL(sw_matrix_walk_window_kernel, dim3((unsigned)((nw + 63) / 64)), dim3(64), 0, c->stream, w);
             } else {
-                WalkStripArgs w{x.items, x.trace, (unsigned char*)c->buf[B_OPS], (WalkState*)c->buf[B_STATE], (int)ni};
+                WalkStripArgs w{x.items, x.trace, (unsigned char*)c->buf[B_OPS], (WalkState*)c->buf[B_STATE], (int)ni, amode};
                 hipLaunchKernelGGL(sw_matrix_walk_strip_kernel, dim3((unsigned)((ni + 63) / 64)), dim3(64), 0, c->stream, w);
             }
             MCHK(hipGetLastError());
@@ -2190,7 +2265,7 @@ int long_group(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, con
             t_walk_ms += wk;
             st.variant += 1;
             st.blocks = (int)blocks;
-            st.waves_per_cu = 4 * c->strip.wgs;
+            st.waves_per_cu = 4 * k_strip.wgs;
             st.boundary_bytes = std::max(st.boundary_bytes, held + (long long)trace_total);
             for (const WindowItem& it : windows) {   // an error stops the call; a walk that goes on stands in the strip left of the window
                 const WalkState& s = o.ws[(size_t)it.slot];
@@ -2212,7 +2287,7 @@ int long_group(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, con
 
 int matrix_align_long_device(const sw_matrix* mx, const unsigned char* d_arena, const int64_t* a_off, const int* alen,
                              const int64_t* b_off, const int* blen, const int* name_idx, int npairs, int gap_init,
-                             int gap_ext, const char* what, AlignSink& sink, bool coop) {
+                             int gap_ext, const char* what, AlignSink& sink, bool coop, int amode) {
     const auto t0 = std::chrono::steady_clock::now();
     if (!gaps_ok(gap_init, gap_ext)) return -1;
     const long long trace_budget = sw_get_option("trace_mb") << 20;
@@ -2220,6 +2295,8 @@ int matrix_align_long_device(const sw_matrix* mx, const unsigned char* d_arena, 
     if (align_ckpt_budget(&ckpt_budget)) return -1;
     std::vector<long long> need((size_t)npairs, 0);
     for (int k = 0; k < npairs; ++k) {   // refused before anything is launched
+        if (amode != AM_LOCAL && !mode_range_ok(alen[k], blen[k], gap_init, gap_ext, what, name_idx ? name_idx[k] : k))
+            return -1;
         sw_align_plan p;
         if (align_long_plan(alen[k], blen[k], trace_budget, ckpt_budget, what, name_idx ? name_idx[k] : k, &p)) return -1;
         need[(size_t)k] = p.ckpt_bytes;
@@ -2245,21 +2322,24 @@ int matrix_align_long_device(const sw_matrix* mx, const unsigned char* d_arena, 
                 act.push_back(DevSeq{a_off[k], b_off[k], alen[k], blen[k], k});
                 st.cells += (long long)alen[k] * blen[k];
             }
-        if (!act.empty() && long_group(c, mx, d_arena, act, gap_init, gap_ext, trace_budget, what, name_idx, st, o, coop)) return -1;
+        if (!act.empty() && long_group(c, mx, d_arena, act, gap_init, gap_ext, trace_budget, what, name_idx, st, o, coop, amode))
+            return -1;
         size_t s = 0;
         for (int k = lo; k < hi; ++k) {
             if (alen[k] == 0 || blen[k] == 0) {
-                sink.set_empty(k);
+                if (amode != AM_LOCAL) align_mode_empty(sink, k, alen[k], blen[k], gap_init, gap_ext, amode);
+                else sink.set_empty(k);
                 continue;
             }
             const TraceRes& r = o.res[s];
             const WalkState& w = o.ws[s];
-            if (r.score <= 0) sink.set_empty(k);
+            if (amode == AM_LOCAL && r.score <= 0) sink.set_empty(k);
             else sink.set(k, r.score, w.i + 1, r.ei + 1, w.j + 1, r.ej + 1, o.ops.data() + o.ops_off[s], w.nops);
             ++s;
         }
         lo = hi;
     }
+    st.variant |= amode << 28;   // bits 28-29: the alignment mode (SW_MODE_*), as the traced launches report it
     st.kernel_ms = t_fill_ms;
     st.total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     report_stats(st);
@@ -2292,7 +2372,7 @@ int matrix_align_device(const sw_matrix* mx, const unsigned char* d_arena, const
         if (alen[k] == 0 || blen[k] == 0) continue;
         const long long need = pair_trace(alen[k], blen[k]);
         if (need > budget) {
-            char m[320];
+            char m[400];
             if (banded)
                 std::snprintf(m, sizeof m,
                               "%s %d: a %d x %d alignment in a band of %d needs %lld bytes of trace memory, more than option "
@@ -2301,8 +2381,8 @@ int matrix_align_device(const sw_matrix* mx, const unsigned char* d_arena, const
             else if (amode != AM_LOCAL)
                 std::snprintf(m, sizeof m,
                               "%s %d: a %d x %d alignment needs %lld bytes of trace memory, more than option trace_mb = %lld "
-                              "MiB, and the checkpointed traceback of long pairs is local only: no global or semi-global "
-                              "alignment of this pair",
+                              "MiB, and the long=True routing of this call is local only (sw_align_matrix_long_mode / "
+                              "sw_db_align_matrix_long_mode align such pairs in a mode, a strip at a time)",
                               what, name_idx ? name_idx[k] : k, alen[k], blen[k], need, budget >> 20);
             else
                 std::snprintf(m, sizeof m,
@@ -2421,6 +2501,8 @@ static int align_host(const char* fn, int long_pairs, const sw_matrix* mx, const
     if (align_check(fn, mx, a, alen, b, blen, npairs, gap_init, gap_ext, out, cigar, cigar_cap, cigar_used)) return -1;
     AlignSink sink{out, {}};
     if (npairs == 0) return sink.finish(cigar, cigar_cap, cigar_used);
+    // the long path in a mode: the range refusal before any device work
+    if (long_pairs && align_long_mode_check(fn, amode, alen, blen, nullptr, npairs, gap_init, gap_ext, "pair")) return -1;
     MatCtx* c = get_mctx();
     if (!c) return -1;
     // the sequences of the pairs with both lengths > 0, as score_host lays them out
@@ -2443,7 +2525,7 @@ static int align_host(const char* fn, int long_pairs, const sw_matrix* mx, const
     // (synchronous: a refusal below returns before anything is launched or waited for)
     if (total) MCHK(hipMemcpy(c->buf[B_ARENA], arena.data(), total, hipMemcpyHostToDevice));
     if (long_pairs ? matrix_align_long_device(mx, (const unsigned char*)c->buf[B_ARENA], a_off.data(), alen, b_off.data(), blen,
-                                              nullptr, npairs, gap_init, gap_ext, "pair", sink, long_pairs == 2)
+                                              nullptr, npairs, gap_init, gap_ext, "pair", sink, long_pairs == 2, amode)
                    : matrix_align_device(mx, (const unsigned char*)c->buf[B_ARENA], a_off.data(), alen, b_off.data(), blen,
                                          nullptr, npairs, gap_init, gap_ext, "pair", sink, amode, band))
         return -1;
@@ -2545,6 +2627,27 @@ int sw_align_matrix_long_coop(const sw_matrix* mx, const unsigned char* const* a
                               sw_alignment* out, unsigned* cigar, long long cigar_cap, long long* cigar_used) {
     return align_host("sw_align_matrix_long_coop", 2, mx, a, alen, b, blen, npairs, gap_init, gap_ext, out, cigar, cigar_cap,
                       cigar_used);
+}
+
+// the long path in a mode; local mode through them is the calls above
+int sw_align_matrix_long_mode(const sw_matrix* mx, const unsigned char* const* a, const int* alen,
+                              const unsigned char* const* b, const int* blen, int npairs, int gap_init, int gap_ext,
+                              int mode, sw_alignment* out, unsigned* cigar, long long cigar_cap, long long* cigar_used) {
+    if (!mode_ok("sw_align_matrix_long_mode", mode)) return -1;
+    if (mode == SW_MODE_LOCAL)
+        return sw_align_matrix_long(mx, a, alen, b, blen, npairs, gap_init, gap_ext, out, cigar, cigar_cap, cigar_used);
+    return align_host("sw_align_matrix_long_mode", 1, mx, a, alen, b, blen, npairs, gap_init, gap_ext, out, cigar, cigar_cap,
+                      cigar_used, mode);
+}
+
+int sw_align_matrix_long_coop_mode(const sw_matrix* mx, const unsigned char* const* a, const int* alen,
+                                   const unsigned char* const* b, const int* blen, int npairs, int gap_init, int gap_ext,
+                                   int mode, sw_alignment* out, unsigned* cigar, long long cigar_cap, long long* cigar_used) {
+    if (!mode_ok("sw_align_matrix_long_coop_mode", mode)) return -1;
+    if (mode == SW_MODE_LOCAL)
+        return sw_align_matrix_long_coop(mx, a, alen, b, blen, npairs, gap_init, gap_ext, out, cigar, cigar_cap, cigar_used);
+    return align_host("sw_align_matrix_long_coop_mode", 2, mx, a, alen, b, blen, npairs, gap_init, gap_ext, out, cigar,
+                      cigar_cap, cigar_used, mode);
 }
 
 int sw_align_long_coop_plan(int n, int m, sw_align_coop_plan* out) {

@@ -138,9 +138,10 @@ void align_pack(const long long* need, int n, long long budget, std::vector<int>
 
 // as matrix_align_device, by checkpointed traceback: pairs of any length that the two budgets admit.
 // coop: the locate pass on many waves and rounds that trace a window of strips (below); the same alignments.
+// amode: SW_MODE_*; global and semi-global pairs (below) are checked with mode_range_ok here.
 int matrix_align_long_device(const sw_matrix* m, const unsigned char* d_arena, const int64_t* a_off, const int* alen,
                              const int64_t* b_off, const int* blen, const int* name_idx, int npairs, int gap_init,
-                             int gap_ext, const char* what, AlignSink& sink, bool coop = false);
+                             int gap_ext, const char* what, AlignSink& sink, bool coop = false, int amode = SW_MODE_LOCAL);
 
 // ---- long pairs on many waves (include/algoGPU.h sw_align_matrix_long_coop) ----
 // The arithmetic is host only (sw_align_host.cpp); the kernels, the launch and the rounds are in sw_matrix.hip.
@@ -169,4 +170,18 @@ int align_window(long long strip_bytes, long long live_bytes, long long trace_bu
 // align_long_plan (the same refusals, the same messages) and what the cooperative path adds
 int align_long_coop_plan(int n, int m, long long trace_budget, long long ckpt_budget, int long_window, const char* what,
                          int idx, sw_align_coop_plan* out);
+
+// ---- long pairs in a mode (include/algoGPU.h sw_align_matrix_long_mode) ----
+// The plans above do not depend on the mode.  What does is host only (sw_align_host.cpp):
+// The end of a global or semi-global pair from the records of the cooperative locate pass: column n - 1 lies
+// in the last strip, so its item alone stores a record, {score, n - 1, ej} in AlignEnd's {t, d, j}; the
+// other items leave theirs zeroed and are not read.  (nrec = 0: zeros.)
+void align_mode_end(const AlignEnd* rec, int nrec, int* score, int* ei, int* ej);
+// An end cell a walk may start from: inside the pair; in a mode on column n - 1, and global at row m - 1.
+bool align_long_end_ok(int n, int m, int mode, int ei, int ej);
+// What the _long_mode entry points refuse before any device work beyond align_long_plan's refusals: an
+// unknown mode (the message names fn) and, in a mode, a pair over mode_range_ok's bound (`what`
+// name_idx[k], or `what` k when name_idx is null).  0 or -1.
+int align_long_mode_check(const char* fn, int mode, const int* alen, const int* blen, const int* name_idx, int npairs,
+                          int gap_init, int gap_ext, const char* what);
 }  // namespace swmi

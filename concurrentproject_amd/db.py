@@ -121,7 +121,9 @@ class Database:
         """SW_MODE_* of ``mode``; a non-local mode needs a matrix and is not built for ``what``."""
         am = _mode(mode)
         if am != 0 and what:
-            raise ValueError("mode=%r is not built for %s: it is local only" % (mode, what))
+            raise ValueError("mode=%r is not built for %s: it is local only%s" % (
+                mode, what, "; Database.align_long(..., mode=%r) aligns long records in that mode" % (mode,)
+                if what.startswith("long=True") else ""))
         if am != 0 and matrix is None:
             raise ValueError("mode=%r needs matrix= (Matrix.equality gives the table of an equality scoring)" % (mode,))
         return am
@@ -167,7 +169,7 @@ class Database:
         """An :class:`Alignment` of ``query`` (seq1) with each record of ``indices``, out of the
         database's device arena (sw_db_align_matrix): only the query is uploaded.  ``long=True``: the
         same alignments by checkpointed traceback (sw_db_align_matrix_long), for records whose whole
-        trace does not fit option ``trace_mb`` (local only); with ``coop=True`` as well, on many waves
+        trace does not fit option ``trace_mb`` (local only: :meth:`align_long` takes a mode); with ``coop=True`` as well, on many waves
         (sw_db_align_matrix_long_coop: ``align_matrix_long(..., coop=True)``).  ``mode`` as in :meth:`search`."""
         if coop and not long:
             raise ValueError("coop=True is not built without long=True (it is the checkpointed traceback on many waves)")
@@ -186,6 +188,26 @@ class Database:
         return _align_call(lambda out, cig, cap, used: f(
             self._h, matrix._handle(), _ptr(q), len(q), IDX, n, int(gap_init), int(gap_ext), out, cig, cap, used), n,
             max(16 * n, _LONG_CIGAR_CAP if long else 0))
+
+    def align_long(self, query, indices, matrix, gap_init: int, gap_ext: int, mode: str = "local", coop: bool = False) -> list:
+        """:meth:`align` with ``long=True`` in any ``mode``: checkpointed traceback of ``query`` (seq1) with each
+        record of ``indices`` (sw_db_align_matrix_long_mode; with ``coop=True`` on many waves,
+        sw_db_align_matrix_long_coop_mode).  Global and semi-global alignments are those of
+        ``align(..., mode=mode)``, bit for bit, for records whose whole trace does not fit option ``trace_mb``;
+        ``mode="local"`` is ``align(..., long=True, coop=coop)``."""
+        am = self._amode(mode, matrix)
+        if am == 0:
+            return self.align(query, indices, matrix, gap_init, gap_ext, long=True, coop=coop)
+        q = _u8(query)
+        idx = [int(i) for i in indices]
+        n = len(idx)
+        if n == 0:
+            return []
+        IDX = (ctypes.c_int * n)(*idx)
+        f = lib().sw_db_align_matrix_long_coop_mode if coop else lib().sw_db_align_matrix_long_mode
+        return _align_call(lambda out, cig, cap, used: f(
+            self._h, matrix._handle(), _ptr(q), len(q), IDX, n, int(gap_init), int(gap_ext), am, out, cig, cap, used), n,
+            max(16 * n, _LONG_CIGAR_CAP))
 
     def top(self, query, k: int = 10, matrix=None, gap_init=None, gap_ext=None, alignments: bool = False,
             mode: str = "local") -> list:

@@ -404,12 +404,13 @@ void sw_last_align_long_ms(float* locate_ms, float* strip_ms, float* walk_ms, in
  * sw_align_matrix_batch_mode: as sw_align_matrix_batch (trace memory, packing, cigar protocol).
  *   sw_last_stats: mode 7; variant = launches as before in bits 0-27, the alignment mode in
  *   bits 28-29.  A pair whose trace does not fit option "trace_mb" alone is refused with a
- *   message that says so: the checkpointed traceback (sw_align_matrix_long) is local only.
+ *   message that says so and names sw_align_matrix_long_mode (below), which aligns such pairs in a
+ *   mode; this call never takes that path by itself.
  * sw_align_matrix_cpu_mode: the plain full-matrix host aligner with the same end rule and walk.
  * sw_db_search_matrix_mode, sw_db_align_matrix_mode: as sw_db_search_matrix / sw_db_align_matrix;
  *   the query is seq1, so semi-global finds the whole query inside a record.
- * An unknown mode returns -1 with a message.  Not built in the new modes: the long path and
- * sw_db_search_db_matrix. */
+ * An unknown mode returns -1 with a message.  Not built in the new modes: sw_db_search_db_matrix.
+ * The long path in a mode has entry points of its own (sw_align_matrix_long_mode, below). */
 #define SW_MODE_LOCAL      0
 #define SW_MODE_GLOBAL     1
 #define SW_MODE_SEMIGLOBAL 2
@@ -530,8 +531,8 @@ int  sw_matrix_coop_plan(int n, int m, int mode, sw_coop_plan* out);
  *
  * sw_align_matrix_long runs the locate pass of a pair on one wave and fills one strip of it a round.
  * sw_align_matrix_long_coop, sw_db_align_matrix_long_coop: the arguments, checks, refusals, messages and
- *   cigar protocol of their _long namesakes, and bit for bit the same alignments.  Local alignment only;
- *   opt-in: no other call takes this path.  Two things differ:
+ *   cigar protocol of their _long namesakes, and bit for bit the same alignments.  Local alignment (the
+ *   other modes: sw_align_matrix_long_coop_mode, below); opt-in: no other call takes this path.  Two things differ:
  *   LOCATE ON MANY WAVES.  A work item is one strip (512 seq1 positions) of one pair, claimed in order;
  *   the wave of strip s + 1 follows the wave of strip s down the pair through checkpoint column s, by the
  *   hand-off of sw_score_matrix_batch_coop (a progress word an item, a bounded poll: option "timeout",
@@ -577,6 +578,47 @@ int  sw_db_align_matrix_long_coop(sw_db*, const sw_matrix*, const unsigned char*
                                   const int* record_idx, int nidx, int gap_init, int gap_ext,
                                   sw_alignment* out, unsigned* cigar, long long cigar_cap, long long* cigar_used);
 int  sw_align_long_coop_plan(int n, int m, sw_align_coop_plan* out);
+
+/* ---- long pairs in a mode: checkpointed traceback, global and semi-global ----
+ *
+ * sw_align_matrix_long_mode, sw_db_align_matrix_long_mode: sw_align_matrix_long / sw_db_align_matrix_long
+ *   with an alignment mode (SW_MODE_*) before `out`; sw_align_matrix_long_coop_mode,
+ *   sw_db_align_matrix_long_coop_mode: the same for the _long_coop calls.  SW_MODE_LOCAL through them is a
+ *   call of the entry point without _mode.  In SW_MODE_GLOBAL and SW_MODE_SEMIGLOBAL the result equals,
+ *   bit for bit, what sw_align_matrix_cpu_mode and sw_align_matrix_batch_mode return for the pair: score,
+ *   the four coordinates and the operations; the end-cell rule and the walk priorities are the ones above,
+ *   run on the same 4 bits a cell.  What differs from the local long path:
+ *     the locate pass reads the end from column n - 1 (global: the corner), so the end is always in the last
+ *       strip; on many waves only that strip's item stores an end record, and the host reads that one;
+ *     every pair with two non-empty sequences walks, whatever its score (scores may be negative or 0); a pair
+ *       with an empty sequence is answered on the host as under sw_align_matrix_batch_mode;
+ *     a strip is filled again under the mode's borders: the top border H[512 s][-1] from the strip index, and
+ *       for strip 0 the left border H[-1][j] as its inflow;
+ *     the walk may leave the matrix at j < 0 in any strip: the leading I run then covers every strip still to
+ *       the left and no further round is run for the pair (global: likewise the leading D run at i < 0).
+ *   Refused before any device work: an unknown mode (-1, the message names the entry point); a pair over the
+ *   SCORE RANGE bound above (the message names the pair or the record) -- the bound holds for a strip filled
+ *   on its own over seq2 positions [0, j] as it does for the whole pair, which has no fewer steps; and
+ *   whatever sw_align_long_plan refuses, with its text.  sw_align_long_plan and sw_align_long_coop_plan do
+ *   not depend on the mode: the checkpoints, a strip's trace, the progress words, the records and the
+ *   window are the same bytes in every mode.
+ *   sw_last_stats: mode 8 (mode 12 for the _coop calls) as before, and the alignment mode in bits 28-29 of
+ *   variant, the strip-fill launches below them, as mode 7 reports it; a local call reports what it did.
+ *   Options trace_mb, long_window, blocks, timeout, coop_poison and SWMI_ALIGN_CKPT_MB as for the local calls. */
+int  sw_align_matrix_long_mode(const sw_matrix*, const unsigned char* const* a, const int* alen,
+                               const unsigned char* const* b, const int* blen, int npairs,
+                               int gap_init, int gap_ext, int mode, sw_alignment* out,
+                               unsigned* cigar, long long cigar_cap, long long* cigar_used);
+int  sw_align_matrix_long_coop_mode(const sw_matrix*, const unsigned char* const* a, const int* alen,
+                                    const unsigned char* const* b, const int* blen, int npairs,
+                                    int gap_init, int gap_ext, int mode, sw_alignment* out,
+                                    unsigned* cigar, long long cigar_cap, long long* cigar_used);
+int  sw_db_align_matrix_long_mode(sw_db*, const sw_matrix*, const unsigned char* query, int qlen,
+                                  const int* record_idx, int nidx, int gap_init, int gap_ext, int mode,
+                                  sw_alignment* out, unsigned* cigar, long long cigar_cap, long long* cigar_used);
+int  sw_db_align_matrix_long_coop_mode(sw_db*, const sw_matrix*, const unsigned char* query, int qlen,
+                                       const int* record_idx, int nidx, int gap_init, int gap_ext, int mode,
+                                       sw_alignment* out, unsigned* cigar, long long cigar_cap, long long* cigar_used);
 
 /* Tuning knobs (process-wide).  Keys:
  *   "W"        columns per lane: 0 = auto, 1, 2, 4, 8

@@ -5,7 +5,10 @@ the shared strip step left the existing instantiations alone (DESIGN.md sections
     python tools/asm_diff_matrix.py OLD.s NEW.s
 
 Prints, per kernel of OLD, its instruction count in both files and "same" or "DIFFERENT", then the
-kernels only NEW has.  Exit 1 if a kernel of OLD is missing from NEW or differs."""
+kernels only NEW has.  Exit 1 if a kernel of OLD is missing from NEW or differs.
+
+A kernel of OLD that NEW has made a template on the alignment mode is compared
+with NEW's instantiation at 0, local -- the symbol with "ILi0EEEv" after the name -- and its line says so."""
 import re
 import sys
 
@@ -36,20 +39,35 @@ def kernels(path):
     return out
 
 
+def local_instance(name, new):
+    """The symbol in `new` of kernel `name` made a template on one int and instantiated at 0, or None."""
+    m = re.match(r"^(_ZN?(?:\d+[A-Za-z_]\w*?)*?\d+sw_matrix\w*?kernel)(E?)(.*)$", name)
+    if not m:
+        return None
+    cand = m.group(1) + "ILi0EE" + m.group(2) + "v" + m.group(3)
+    return cand if cand in new else None
+
+
 def main(old, new):
     a, b = kernels(old), kernels(new)
     bad = 0
+    paired = set()
     for k in sorted(a):
         n_old = sum(1 for x in a[k] if x != "LABEL:")
+        kn, note = k, ""
         if k not in b:
-            print("%-60s %5d  MISSING" % (k, n_old))
-            bad = 1
-            continue
-        n_new = sum(1 for x in b[k] if x != "LABEL:")
-        same = a[k] == b[k]
+            kn = local_instance(k, b)
+            if kn is None:
+                print("%-60s %5d  MISSING" % (k, n_old))
+                bad = 1
+                continue
+            paired.add(kn)
+            note = "  (now a template: its instantiation at 0)"
+        n_new = sum(1 for x in b[kn] if x != "LABEL:")
+        same = a[k] == b[kn]
         bad |= not same
-        print("%-60s %5d %5d  %s" % (k, n_old, n_new, "same" if same else "DIFFERENT"))
-    for k in sorted(set(b) - set(a)):
+        print("%-60s %5d %5d  %s%s" % (k, n_old, n_new, "same" if same else "DIFFERENT", note))
+    for k in sorted(set(b) - set(a) - paired):
         print("%-60s     - %5d  new" % (k, sum(1 for x in b[k] if x != "LABEL:")))
     return bad
 
