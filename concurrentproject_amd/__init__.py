@@ -26,6 +26,7 @@ __all__ = [
     "ipc_open", "ipc_close", "score_slab_device", "Database", "Matrix", "score_matrix", "score_matrix_batch",
     "SW_MATRIX_FOLD_CASE", "Alignment", "align_matrix", "align_matrix_batch", "last_align_ms",
     "align_matrix_long", "align_long_plan", "last_align_long_ms", "coop_plan", "align_long_coop_plan",
+    "Profile", "score_profile", "score_profile_batch", "align_profile", "align_profile_batch",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -287,6 +288,37 @@ def lib() -> ctypes.CDLL:
             f = getattr(L, name)
             f.argtypes = L.sw_db_align_matrix_mode.argtypes
             f.restype = i
+    if hasattr(L, "sw_profile_create"):   # position-specific scoring (include/algoGPU.h sw_profile_*)
+        L.sw_profile_create.argtypes = [u8p, i, i8p, i, i, i]
+        L.sw_profile_create.restype = vp
+        L.sw_profile_from_matrix.argtypes = [vp, u8p, i]
+        L.sw_profile_from_matrix.restype = vp
+        L.sw_profile_parse.argtypes = [ctypes.c_char_p, ctypes.c_longlong]
+        L.sw_profile_parse.restype = vp
+        L.sw_profile_open.argtypes = [ctypes.c_char_p]
+        L.sw_profile_open.restype = vp
+        for name in ("sw_profile_length", "sw_profile_size"):
+            f = getattr(L, name)
+            f.argtypes = [vp]
+            f.restype = i
+        L.sw_profile_symbols.argtypes = [vp, u8p]
+        L.sw_profile_symbols.restype = i
+        L.sw_profile_score.argtypes = [vp, i, ctypes.c_ubyte, ctypes.POINTER(i)]
+        L.sw_profile_score.restype = i
+        L.sw_profile_free.argtypes = [vp]
+        L.sw_profile_free.restype = None
+        L.sw_score_profile_batch.argtypes = [vp, ctypes.POINTER(u8p), ctypes.POINTER(i), i, i, i, i, ctypes.POINTER(i)]
+        L.sw_score_profile_batch.restype = i
+        for name in ("sw_align_profile_batch", "sw_align_profile_cpu"):
+            f = getattr(L, name)
+            f.argtypes = [vp, ctypes.POINTER(u8p), ctypes.POINTER(i), i, i, i, i, ctypes.POINTER(_Alignment),
+                          ctypes.POINTER(ctypes.c_uint), ll, ctypes.POINTER(ll)]
+            f.restype = i
+        L.sw_db_search_profile.argtypes = [vp, vp, i, i, i, ctypes.POINTER(i)]
+        L.sw_db_search_profile.restype = i
+        L.sw_db_align_profile.argtypes = [vp, vp, ctypes.POINTER(i), i, i, i, i, ctypes.POINTER(_Alignment),
+                                          ctypes.POINTER(ctypes.c_uint), ll, ctypes.POINTER(ll)]
+        L.sw_db_align_profile.restype = i
     _lib = L
     return L
 
@@ -885,6 +917,136 @@ def coop_plan(n: int, m: int, mode: str = "local") -> dict:
     p = _CoopPlan()
     _check(lib().sw_matrix_coop_plan(int(n), int(m), _mode(mode), ctypes.byref(p)))
     return {"W": p.W, "strips": p.strips, "swap": p.swap, "edge_bytes": p.edge_bytes, "items": p.items}
+
+
+# ---- position-specific scoring (include/algoGPU.h sw_profile_*) --------------------------------------
+
+class Profile:
+    """A profile: n >= 1 positions over K <= 32 distinct byte symbols, ``scores[i][c]`` what symbol c of the
+    sequence scores at position i (a PSSM, a family profile, a query with masked or up-weighted positions).
+    ``other`` and ``fold_case`` as for :class:`Matrix`.  The profile is seq1 of every call that takes one: an
+    "I" consumes a profile position, ``beg1`` / ``end1`` are profile positions, and in "semiglobal" mode the
+    profile is what is covered end to end.  Immutable; usable from any thread."""
+
+    def __init__(self, symbols=None, scores=None, other: int = -1, fold_case: bool = False, _handle=None):
+        if _handle is None:
+            sym = _u8(symbols)
+            tab = np.ascontiguousarray(scores, dtype=np.int64)
+            k = len(sym)
+            if k == 0 or tab.size % k != 0 or (tab.ndim == 2 and tab.shape[1] != k):
+                raise SwError("profile: the table is not n x %d" % k)
+            n = tab.size // k
+            if tab.size and (tab.min() < -127 or tab.max() > 127):
+                raise SwError("profile: an entry is outside [-127, 127]")
+            t8 = tab.reshape(-1).astype(np.int8)
+            _handle = lib().sw_profile_create(_ptr(sym), k, t8.ctypes.data_as(ctypes.POINTER(ctypes.c_byte)), n,
+                                              int(other), SW_MATRIX_FOLD_CASE if fold_case else 0)
+        if not _handle:
+            raise SwError(lib().sw_last_error().decode(errors="replace"))
+        self._h = ctypes.c_void_p(_handle)
+
+    @classmethod
+    def parse(cls, text) -> "Profile":
+        """From the library's own text format: '#' comment lines, a header line of K symbols, then a row a
+        position: a one-byte label (the consensus residue, ignored) and K integers."""
+        if isinstance(text, str):
+            text = text.encode("latin-1")
+        return cls(_handle=lib().sw_profile_parse(text, len(text)) or 0)
+
+    @classmethod
+    def open(cls, path) -> "Profile":
+        return cls(_handle=lib().sw_profile_open(os.fsencode(path)) or 0)
+
+    @classmethod
+    def from_matrix(cls, matrix: Matrix, query) -> "Profile":
+        """Row i is ``matrix``'s row of query byte i: the profile calls then give what the matrix calls give
+        with ``query`` as seq1."""
+        q = _u8(query)
+        return cls(_handle=lib().sw_profile_from_matrix(matrix._handle(), _ptr(q), len(q)) or 0)
+
+    def _handle(self):
+        if self._h is None:
+            raise SwError("profile is closed")
+        return self._h
+
+    def __len__(self) -> int:
+        return lib().sw_profile_length(self._handle())
+
+    @property
+    def symbols(self) -> bytes:
+        k = lib().sw_profile_size(self._handle())
+        out = np.zeros(max(k, 1), dtype=np.uint8)
+        _check(lib().sw_profile_symbols(self._handle(), _ptr(out)))
+        return out[:k].tobytes()
+
+    def score(self, pos: int, byte) -> int:
+        """The entry of position ``pos`` for ``byte``, through the byte-to-code map the kernel uses."""
+        out = ctypes.c_int()
+        _check(lib().sw_profile_score(self._handle(), int(pos), int(_u8(byte)[0]), ctypes.byref(out)))
+        return out.value
+
+    def close(self) -> None:
+        if self._h is not None and self._h.value:
+            lib().sw_profile_free(self._h)
+        self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _seq_arrays(seqs):
+    arrs = [_u8(x) for x in seqs]
+    n = len(arrs)
+    u8p = ctypes.POINTER(ctypes.c_ubyte)
+    return arrs, (u8p * n)(*[_ptr(x) for x in arrs]), (ctypes.c_int * n)(*[len(x) for x in arrs])
+
+
+def score_profile_batch(profile: Profile, seqs: Iterable, gap_init: int, gap_ext: int, mode: str = "local") -> list:
+    """The score of ``profile`` (seq1) against every sequence of ``seqs`` in one launch
+    (sw_score_profile_batch): the recurrence of :func:`score_matrix_batch` in ``mode``, with the score of a
+    cell read from the profile's row of its position.  No ``band=``, ``coop=`` or long path with a profile."""
+    am = _mode(mode)
+    arrs, S, SL = _seq_arrays(seqs)
+    n = len(arrs)
+    if n == 0:
+        return []
+    out = (ctypes.c_int * n)()
+    _check(lib().sw_score_profile_batch(profile._handle(), S, SL, n, int(gap_init), int(gap_ext), am, out))
+    return list(out)
+
+
+def score_profile(profile: Profile, seq, gap_init: int, gap_ext: int, mode: str = "local") -> int:
+    """One sequence (see :func:`score_profile_batch`)."""
+    return score_profile_batch(profile, [seq], gap_init, gap_ext, mode=mode)[0]
+
+
+def align_profile_batch(profile: Profile, seqs: Iterable, gap_init: int, gap_ext: int, cpu: bool = False,
+                        mode: str = "local") -> list:
+    """An :class:`Alignment` of ``profile`` (seq1) with every sequence of ``seqs``, on the GPU
+    (sw_align_profile_batch) or, with ``cpu=True``, from the library's host aligner (sw_align_profile_cpu),
+    which gives the same result bit for bit.  End cell, walk and modes as :func:`align_matrix_batch`."""
+    am = _mode(mode)
+    arrs, S, SL = _seq_arrays(seqs)
+    n = len(arrs)
+    if n == 0:
+        return []
+    f = lib().sw_align_profile_cpu if cpu else lib().sw_align_profile_batch
+    return _align_call(lambda out, cig, cap, used: f(profile._handle(), S, SL, n, int(gap_init), int(gap_ext), am, out, cig,
+                                                     cap, used), n, 16 * n)
+
+
+def align_profile(profile: Profile, seq, gap_init: int, gap_ext: int, cpu: bool = False, mode: str = "local") -> Alignment:
+    """One sequence (see :func:`align_profile_batch`)."""
+    return align_profile_batch(profile, [seq], gap_init, gap_ext, cpu=cpu, mode=mode)[0]
 
 
 def last_align_ms() -> tuple:

@@ -13,6 +13,8 @@
 // the answers for empty sequences, and sw_align_matrix_cpu_mode, the same plain aligner for those modes.
 // And banded alignment (sw_*_band): the band's arithmetic (range, cells, the strips' chunks, trace bytes),
 // sw_band_plan, and sw_align_matrix_cpu_band, the plain aligner restricted to a band, every mode.
+// And position-specific scoring (sw_*_profile_*): the entry points' checks, and sw_align_profile_cpu: the local and
+// the mode aligner are templates on where a cell's score comes from, a table row by residue or a profile row by position.
 #include "sw_matrix_host.h"
 #include "../../include/algoGPU.h"
 
@@ -124,6 +126,57 @@ int AlignSink::finish(unsigned* cigar, long long cigar_cap, long long* cigar_use
     }
     if (!cig.empty()) std::memcpy(cigar, cig.data(), cig.size() * sizeof(unsigned));
     return 0;
+}
+
+// ---- position-specific scoring: the checks of the sw_*_profile_* entry points (sw_matrix_host.h) ----
+
+bool profile_range_ok(const sw_profile* pf, int len, int gap_init, int gap_ext, int amode, const char* what, int idx) {
+    if (amode != SW_MODE_LOCAL && !mode_range_ok(pf->n, len, gap_init, gap_ext, what, idx)) return false;
+    return len == 0 || align_range_ok(&pf->alpha, pf->n, len, what, idx);
+}
+
+int profile_check(const char* fn, const sw_profile* pf, const unsigned char* const* seqs, const int* lens, int nseq,
+                  int gap_init, int gap_ext, int mode) {
+    char m[200];
+    if (!pf || nseq < 0 || (nseq > 0 && (!seqs || !lens))) {
+        std::snprintf(m, sizeof m, "%s: invalid arguments", fn);
+        report_error(m);
+        return -1;
+    }
+    if (!mode_ok(fn, mode)) return -1;
+    if (gap_init < 0 || gap_ext < 0 || gap_init > (1 << 20) || gap_ext > (1 << 20)) {
+        std::snprintf(m, sizeof m, "unsupported gap penalties (%d, %d): need 0 <= G_INIT, G_EXT <= 2^20", gap_init, gap_ext);
+        report_error(m);
+        return -1;
+    }
+    for (int k = 0; k < nseq; ++k) {
+        if (lens[k] < 0 || (lens[k] > 0 && !seqs[k]) || lens[k] > ALIGN_MAX_SEQ) {
+            std::snprintf(m, sizeof m, "sequence %d: invalid sequence pointer or length", k);
+            report_error(m);
+            return -1;
+        }
+        if (!profile_range_ok(pf, lens[k], gap_init, gap_ext, mode, "sequence", k)) return -1;
+        const long long bad = matrix_first_bad(&pf->alpha, seqs[k], lens[k]);
+        if (bad >= 0) {
+            std::snprintf(m, sizeof m, "sequence %d: position %lld: byte 0x%02x is outside the profile alphabet", k, bad,
+                          seqs[k][bad]);
+            report_error(m);
+            return -1;
+        }
+    }
+    return 0;
+}
+
+int profile_align_check(const char* fn, const sw_profile* pf, const unsigned char* const* seqs, const int* lens, int nseq,
+                        int gap_init, int gap_ext, int mode, const sw_alignment* out, const unsigned* cigar,
+                        long long cigar_cap, const long long* cigar_used) {
+    if (cigar_cap < 0 || !cigar_used || (cigar_cap > 0 && !cigar) || (nseq > 0 && !out)) {
+        char m[200];
+        std::snprintf(m, sizeof m, "%s: invalid arguments", fn);
+        report_error(m);
+        return -1;
+    }
+    return profile_check(fn, pf, seqs, lens, nseq, gap_init, gap_ext, mode);
 }
 
 // ---- long pairs: the plan of a checkpointed traceback (sw_matrix_host.h) ----
@@ -447,10 +500,24 @@ void align_pair_band(const sw_matrix* mx, const unsigned char* a, int n, const u
     sink.set(k, best, i + 1, bi + 1, j + 1, bj + 1, ops.data(), nops);
 }
 
+// The score of a cell, the one thing align_pair_mode and align_pair do not know: s(i, cb), i a position of seq1
+// and cb the code of seq2's residue.  Under a matrix it is the table row of seq1's residue; under a profile
+// (sw_align_profile_cpu) the row of position i itself.
+struct MatrixScore {
+    const sw_matrix* mx;
+    const unsigned char* a;
+    int operator()(int i, int cb) const { return mx->sc[mx->code[a[i]] * mx->k + cb]; }
+};
+struct ProfileScore {
+    const sw_profile* pf;
+    int operator()(int i, int cb) const { return pf->sc[(size_t)i * (size_t)pf->alpha.k + (size_t)cb]; }
+};
+
 // Global and semi-global (include/algoGPU.h): one pair, both lengths > 0, three full rows of state
 // and a byte a cell as align_pair below, the unclamped recurrence with its borders, the end rule and
 // the walk with its border exits.
-void align_pair_mode(const sw_matrix* mx, const unsigned char* a, int n, const unsigned char* b, int m, int go, int ge,
+template <class SCORE>
+void align_pair_mode(const SCORE& s, const unsigned char* code, int n, const unsigned char* b, int m, int go, int ge,
                      int mode, std::vector<unsigned char>& cell, std::vector<int>& hup, std::vector<int>& fup,
                      std::vector<unsigned char>& ops, int k, AlignSink& sink) {
     const int gx = std::min(go, ge);
@@ -460,7 +527,7 @@ void align_pair_mode(const sw_matrix* mx, const unsigned char* a, int n, const u
     for (int i = 0; i < n; ++i) hup[(size_t)i] = -(go + i * gx);   // H[i][-1]
     int best = CPU_NEG, bj = 0;
     for (int j = 0; j < m; ++j) {
-        const int cb = mx->code[b[j]];
+        const int cb = code[b[j]];
         // H[-1][j] and H[-1][j-1]; E[-1][j] is minus infinity
         int hleft = mode == SW_MODE_GLOBAL ? -(go + j * gx) : 0;
         int hdiag = j == 0 || mode != SW_MODE_GLOBAL ? 0 : -(go + (j - 1) * gx);
@@ -471,7 +538,7 @@ void align_pair_mode(const sw_matrix* mx, const unsigned char* a, int n, const u
             const int fo = hup[(size_t)i] - go, fe = fup[(size_t)i] - ge;
             const int E = std::max(eo, ee);
             const int F = std::max(fo, fe);
-            const int t = hdiag + mx->sc[mx->code[a[i]] * mx->k + cb];
+            const int t = hdiag + s(i, cb);
             const int H = std::max(t, std::max(E, F));
             row[i] = (unsigned char)((t == H ? 1 : E == H ? 2 : 3) | (ee > eo ? 4 : 0) | (fe > fo ? 8 : 0));
             hdiag = hup[(size_t)i];
@@ -525,7 +592,8 @@ void align_pair_mode(const sw_matrix* mx, const unsigned char* a, int n, const u
 // 2 E, 3 F), bit 2 E extended a gap (else opened one), bit 3 the same for F; E runs along seq1
 // (operation I), F along seq2 (operation D).  The clamped form of the kernel: E and F are kept as
 // max(E, 0), max(F, 0), which changes no H and no decision at a cell the walk can visit.
-void align_pair(const sw_matrix* mx, const unsigned char* a, int n, const unsigned char* b, int m, int go, int ge,
+template <class SCORE>
+void align_pair(const SCORE& s, const unsigned char* code, int n, const unsigned char* b, int m, int go, int ge,
                 std::vector<unsigned char>& cell, std::vector<int>& hup, std::vector<int>& fup,
                 std::vector<unsigned char>& ops, int k, AlignSink& sink) {
     cell.assign((size_t)n * (size_t)m, 0);
@@ -533,7 +601,7 @@ void align_pair(const sw_matrix* mx, const unsigned char* a, int n, const unsign
     fup.assign((size_t)n, 0);
     int best = 0, bi = 0, bj = 0;
     for (int j = 0; j < m; ++j) {
-        const int cb = mx->code[b[j]];
+        const int cb = code[b[j]];
         int hleft = 0, eleft = 0, hdiag = 0;
         unsigned char* row = cell.data() + (size_t)j * (size_t)n;
         for (int i = 0; i < n; ++i) {
@@ -541,7 +609,7 @@ void align_pair(const sw_matrix* mx, const unsigned char* a, int n, const unsign
             const int fo = hup[(size_t)i] - go, fe = fup[(size_t)i] - ge;
             const int E = std::max(std::max(eo, ee), 0);
             const int F = std::max(std::max(fo, fe), 0);
-            const int t = hdiag + mx->sc[mx->code[a[i]] * mx->k + cb];
+            const int t = hdiag + s(i, cb);
             const int H = std::max(t, std::max(E, F));
             row[i] = (unsigned char)((H == 0 ? 0 : t == H ? 1 : E == H ? 2 : 3) | (ee > eo ? 4 : 0) | (fe > fo ? 8 : 0));
             // the end cell: largest t, then smallest i + j, then smallest j
@@ -615,7 +683,7 @@ int sw_align_matrix_cpu(const sw_matrix* mx, const unsigned char* const* a, cons
     std::vector<int> hup, fup;
     for (int k = 0; k < npairs; ++k) {
         if (alen[k] == 0 || blen[k] == 0) sink.set_empty(k);
-        else align_pair(mx, a[k], alen[k], b[k], blen[k], gap_init, gap_ext, cell, hup, fup, ops, k, sink);
+        else align_pair(MatrixScore{mx, a[k]}, mx->code, alen[k], b[k], blen[k], gap_init, gap_ext, cell, hup, fup, ops, k, sink);
     }
     return sink.finish(cigar, cigar_cap, cigar_used);
 }
@@ -644,7 +712,8 @@ int sw_align_matrix_cpu_mode(const sw_matrix* mx, const unsigned char* const* a,
     std::vector<int> hup, fup;
     for (int k = 0; k < npairs; ++k) {
         if (alen[k] == 0 || blen[k] == 0) align_mode_empty(sink, k, alen[k], blen[k], gap_init, gap_ext, mode);
-        else align_pair_mode(mx, a[k], alen[k], b[k], blen[k], gap_init, gap_ext, mode, cell, hup, fup, ops, k, sink);
+        else align_pair_mode(MatrixScore{mx, a[k]}, mx->code, alen[k], b[k], blen[k], gap_init, gap_ext, mode, cell, hup, fup, ops, k,
+                             sink);
     }
     return sink.finish(cigar, cigar_cap, cigar_used);
 }
@@ -678,6 +747,36 @@ int sw_align_matrix_cpu_band(const sw_matrix* mx, const unsigned char* const* a,
         int dlo, dhi;
         band_range(alen[k], blen[k], band, &dlo, &dhi);
         align_pair_band(mx, a[k], alen[k], b[k], blen[k], gap_init, gap_ext, mode, dlo, dhi, cell, hup, fup, ops, k, sink);
+    }
+    return sink.finish(cigar, cigar_cap, cigar_used);
+}
+
+int sw_align_profile_cpu(const sw_profile* pf, const unsigned char* const* seqs, const int* lens, int nseq, int gap_init,
+                         int gap_ext, int mode, sw_alignment* out, unsigned* cigar, long long cigar_cap, long long* cigar_used) {
+    if (profile_align_check("sw_align_profile_cpu", pf, seqs, lens, nseq, gap_init, gap_ext, mode, out, cigar, cigar_cap,
+                            cigar_used))
+        return -1;
+    for (int k = 0; k < nseq; ++k)
+        if ((long long)pf->n * lens[k] > CPU_MAX_CELLS) {
+            char m[160];
+            std::snprintf(m, sizeof m, "sequence %d: %lld cells are more than the CPU aligner's full matrix holds (2^32)", k,
+                          (long long)pf->n * lens[k]);
+            report_error(m);
+            return -1;
+        }
+    AlignSink sink{out, {}};
+    std::vector<unsigned char> cell, ops;
+    std::vector<int> hup, fup;
+    const ProfileScore s{pf};
+    for (int k = 0; k < nseq; ++k) {
+        if (lens[k] == 0) {
+            if (mode != SW_MODE_LOCAL) align_mode_empty(sink, k, pf->n, 0, gap_init, gap_ext, mode);
+            else sink.set_empty(k);
+        } else if (mode == SW_MODE_LOCAL) {
+            align_pair(s, pf->alpha.code, pf->n, seqs[k], lens[k], gap_init, gap_ext, cell, hup, fup, ops, k, sink);
+        } else {
+            align_pair_mode(s, pf->alpha.code, pf->n, seqs[k], lens[k], gap_init, gap_ext, mode, cell, hup, fup, ops, k, sink);
+        }
     }
     return sink.finish(cigar, cigar_cap, cigar_used);
 }

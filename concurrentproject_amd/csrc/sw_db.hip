@@ -201,8 +201,9 @@ int search_many(sw_db* db, const sw_db* queries, int* scores_out) {
 
 // ---- substitution-matrix searches (sw_matrix.hip's kernel over the same arena and query slot) ----
 
-// every residue of the database has a code in mx: checked once per (database, matrix)
-int check_records(sw_db* db, const sw_matrix* mx) {
+// every residue of the database has a code in mx: checked once per (database, matrix); a profile's alphabet is
+// a matrix object with an id of its own, so once per (database, profile) too (`alphabet` words the message)
+int check_records(sw_db* db, const sw_matrix* mx, const char* alphabet = "matrix") {
     if (db->matrix_ok.count(mx->id)) return 0;
     const long long bad = matrix_first_bad(mx, db->res.data(), (long long)db->res.size());
     if (bad >= 0) {
@@ -211,8 +212,8 @@ int check_records(sw_db* db, const sw_matrix* mx) {
         for (size_t r = 0; r < db->len.size(); ++r)
             if (db->len[r] > 0 && db->off[r] <= bad && bad < db->off[r] + db->len[r]) rec = (int)r;
         char m[160];
-        std::snprintf(m, sizeof m, "record %d: position %lld: byte 0x%02x is outside the matrix alphabet", rec,
-                      bad - (long long)db->off[rec], db->res[(size_t)bad]);
+        std::snprintf(m, sizeof m, "record %d: position %lld: byte 0x%02x is outside the %s alphabet", rec,
+                      bad - (long long)db->off[rec], db->res[(size_t)bad], alphabet);
         report_error(m);
         return -1;
     }
@@ -306,12 +307,86 @@ int align_matrix(sw_db* db, const sw_matrix* mx, const unsigned char* query, int
                                gap_ext, "record", sink, amode);
 }
 
+// ---- profile searches (include/algoGPU.h sw_db_*_profile): the profile in the query's place, nothing of it in the arena ----
+
+// the profile (seq1, across the lanes) against every record, longest first; scores in record order
+int search_profile(sw_db* db, const sw_profile* pf, int gap_init, int gap_ext, int amode, int* scores_out) {
+    const int nrec = (int)db->len.size();
+    if (nrec == 0) return 0;
+    if (check_records(db, &pf->alpha, "profile")) return -1;
+    for (int r = 0; r < nrec; ++r)
+        if (!profile_range_ok(pf, db->len[(size_t)r], gap_init, gap_ext, amode, "record", r)) return -1;
+    sw_db::Dev* v = nullptr;
+    if (device_arena(db, 0, &v)) return -1;
+    std::vector<int64_t> b_off;
+    std::vector<int> blen;
+    record_order(db, b_off, blen);
+    if (profile_score_device(pf, v->arena, b_off.data(), blen.data(), nrec, gap_init, gap_ext, v->scores, amode)) return -1;
+    std::vector<int> got((size_t)nrec);
+    DBCHK(hipMemcpy(got.data(), v->scores, (size_t)nrec * sizeof(int), hipMemcpyDeviceToHost));
+    if (amode != SW_MODE_LOCAL)   // an empty record is answered on the host
+        for (int k = 0; k < nrec; ++k)
+            if (blen[(size_t)k] == 0) got[(size_t)k] = mode_empty_score(pf->n, 0, gap_init, gap_ext, amode);
+    for (int k = 0; k < nrec; ++k) scores_out[db->order[k]] = got[k];
+    return 0;
+}
+
+// the profile aligned with the chosen records, out of the device arena
+int align_profile(sw_db* db, const sw_profile* pf, const int* record_idx, int nidx, int gap_init, int gap_ext, int amode,
+                  AlignSink& sink) {
+    const int nrec = (int)db->len.size();
+    for (int k = 0; k < nidx; ++k)
+        if (record_idx[k] < 0 || record_idx[k] >= nrec) {
+            char m[160];
+            std::snprintf(m, sizeof m, "sw_db_align_profile: record index %d (entry %d) is outside [0, %d)", record_idx[k], k, nrec);
+            report_error(m);
+            return -1;
+        }
+    if (nidx == 0) return 0;
+    if (check_records(db, &pf->alpha, "profile")) return -1;
+    std::vector<int64_t> b_off((size_t)nidx);
+    std::vector<int> blen((size_t)nidx);
+    for (int k = 0; k < nidx; ++k) {
+        b_off[(size_t)k] = db->off[(size_t)record_idx[k]];
+        blen[(size_t)k] = db->len[(size_t)record_idx[k]];
+        if (!profile_range_ok(pf, blen[(size_t)k], gap_init, gap_ext, amode, "record", record_idx[k])) return -1;
+    }
+    sw_db::Dev* v = nullptr;
+    if (device_arena(db, 0, &v)) return -1;
+    return profile_align_device(pf, v->arena, b_off.data(), blen.data(), record_idx, nidx, gap_init, gap_ext, "record", sink,
+                                amode);
+}
+
 }  // namespace
 }  // namespace swmi
 
 using namespace swmi;
 
 extern "C" {
+
+int sw_db_search_profile(sw_db* db, const sw_profile* pf, int gap_init, int gap_ext, int mode, int* scores_out) {
+    if (!db || !pf || (!db->len.empty() && !scores_out)) {
+        report_error("sw_db_search_profile: invalid arguments");
+        return -1;
+    }
+    if (!mode_ok("sw_db_search_profile", mode)) return -1;
+    std::lock_guard<std::mutex> g(db->mu);
+    return search_profile(db, pf, gap_init, gap_ext, mode, scores_out);
+}
+
+int sw_db_align_profile(sw_db* db, const sw_profile* pf, const int* record_idx, int nidx, int gap_init, int gap_ext, int mode,
+                        sw_alignment* out, unsigned* cigar, long long cigar_cap, long long* cigar_used) {
+    if (!db || !pf || nidx < 0 || cigar_cap < 0 || !cigar_used || (cigar_cap > 0 && !cigar) ||
+        (nidx > 0 && (!record_idx || !out))) {
+        report_error("sw_db_align_profile: invalid arguments");
+        return -1;
+    }
+    if (!mode_ok("sw_db_align_profile", mode)) return -1;
+    std::lock_guard<std::mutex> g(db->mu);
+    AlignSink sink{out, {}};
+    if (align_profile(db, pf, record_idx, nidx, gap_init, gap_ext, mode, sink)) return -1;
+    return sink.finish(cigar, cigar_cap, cigar_used);
+}
 
 int sw_db_search_matrix(sw_db* db, const sw_matrix* mx, const unsigned char* query, int qlen, int gap_init,
                         int gap_ext, int* scores_out) {

@@ -89,7 +89,10 @@ constexpr int MODE_MATRIX_TRACE = 7;                 // the traced launches (ali
 constexpr int MODE_MATRIX_LONG = 8;                  // checkpointed traceback of long pairs (sw_align_matrix_long)
 constexpr int MODE_MATRIX_BAND = 9;                  // the band launches, score-only (sw_score_matrix_batch_band)
 constexpr int MODE_MATRIX_BAND_TRACE = 10;           // and traced (sw_align_matrix_batch_band)
+constexpr int MODE_MATRIX_PROFILE = 13;              // the profile launches, score-only (sw_score_profile_batch)
+constexpr int MODE_MATRIX_PROFILE_TRACE = 14;        // and traced (sw_align_profile_batch)
 constexpr int TRACE_W = 8;                           // the traced variant's columns per lane: a step is a dword a lane
+static_assert(SW_PROFILE_STRIDE == MAT_STRIDE && SW_PROFILE_SENT == MAT_SENT, "the profile image is rows of the table");
 
 struct MatPair {
     uint64_t col_off;   // the sequence across the lanes
@@ -145,6 +148,8 @@ struct MatArgs {
     const WalkPair* walk;     // per item
     unsigned char* trace;
     TraceRes* res;            // nscores entries
+    // profile launches only (PROFILE below): the device image, pd.n + 1 rows of MAT_STRIDE bytes
+    const unsigned char* prof;
 };
 static_assert(sizeof(MatArgs) <= 4096, "kernel arguments");
 static_assert(MAT_TAB_BYTES % 4 == 0, "table words");
@@ -189,10 +194,23 @@ constexpr int MAT_NEG = -(1 << 30);
 //     bound where it was.  The lane's other cells of that step are either in rows >= 0 on diagonals
 //     >= dlo + 1 (columns before it: unaffected) or in rows <= -2 (columns after it: never read by a
 //     cell of the matrix).
-template <int W, int MODE, int AM = AM_LOCAL, bool BAND = false>
+//
+// PROFILE: position-specific scoring (include/algoGPU.h sw_*_profile_*), a fifth
+// compile-time parameter: the columns are the positions of a profile, and column c reads its scores from a
+// table row that is its own, P[c][.], instead of the row of its residue in a table the workgroup shares.  The
+// step is the same step: cb[p] is still "the LDS offset of this column's table row".  The rows live in a slab
+// that belongs to the wave, W * 64 slots of MAT_STRIDE bytes laid out [p][lane] (a lane's slots are 9 dwords from
+// its neighbour's: odd, so a step's 64 byte reads at one row code fall in 64 different banks), and before each
+// strip lane l copies the rows of its W columns there from the device image (stage_rows).  A lane reads only
+// the slots it wrote itself, and a wave's LDS operations complete in order: no barrier, and nothing shared
+// with the other waves of the workgroup.  LDS does not grow with the profile's length.  Row pd.n of the image is
+// the dead row, for the columns past the end.  seq1 is always the profile: there is no swap, no band, no
+// cooperative and no long instantiation.
+template <int W, int MODE, int AM = AM_LOCAL, bool BAND = false, bool PROFILE = false>
 struct MStrip {
     static_assert(MODE == M_SCORE || W == TRACE_W, "a traced step stores one dword a lane");
     static_assert(!BAND || MODE != M_LOCATE, "the long path has no band");
+    static_assert(!PROFILE || (!BAND && MODE != M_LOCATE), "a profile has neither a band nor a long path");
     int cb[W], tb[W];                       // LDS offset of the column's table row / bias
     int hgA[W], hgB[W], eh[W], r[W], fh[W]; // DP state, as Strip (sw_kernels.hip)
     int L0, M, IOH, IOE, IOR;
@@ -205,17 +223,25 @@ struct MStrip {
                                           const unsigned char* s_code) {
         constexpr int SW = 64 * W;
         const int go = a.gap_init, ge = a.gap_ext;
-        const unsigned char* colseq = a.seq + pd.col_off;
-        const int tbase = pd.swap_or_band ? MAT_TAB_BYTES : 0;   // (a band launch's claim loop has taken B out)
+        if constexpr (PROFILE) {   // the lane's own slots of the wave's slab (stage_rows fills them)
 #pragma unroll
-        for (int p = 0; p < W; ++p) {
-            const int c = strip * SW + lane * W + p;
-            if (c < pd.n) {
-                cb[p] = tbase + (int)s_code[colseq[c]] * MAT_STRIDE;
-                tb[p] = go;
-            } else {
-                cb[p] = tbase + a.k * MAT_STRIDE;
-                tb[p] = -DEAD;
+            for (int p = 0; p < W; ++p) {
+                cb[p] = (p * 64 + lane) * MAT_STRIDE;
+                tb[p] = strip * SW + lane * W + p < pd.n ? go : -DEAD;
+            }
+        } else {
+            const unsigned char* colseq = a.seq + pd.col_off;
+            const int tbase = pd.swap_or_band ? MAT_TAB_BYTES : 0;   // (a band launch's claim loop has taken B out)
+#pragma unroll
+            for (int p = 0; p < W; ++p) {
+                const int c = strip * SW + lane * W + p;
+                if (c < pd.n) {
+                    cb[p] = tbase + (int)s_code[colseq[c]] * MAT_STRIDE;
+                    tb[p] = go;
+                } else {
+                    cb[p] = tbase + a.k * MAT_STRIDE;
+                    tb[p] = -DEAD;
+                }
             }
         }
 #pragma unroll
@@ -239,6 +265,22 @@ struct MStrip {
             pstar = cl & (W - 1);
             jrow = cl >= 0 && cl < SW && cl / W == lane ? -cl - jlo : MAT_NEG;
             wl = pd.m - jlo;
+        }
+    }
+
+    // PROFILE, before the strip's first step: rows min(c, pd.n) of the image, c the lane's W columns, into the
+    // lane's slots of the wave's slab.  Every row read is inside the image (pd.n + 1 rows) and every slot written
+    // inside the slab (W * 64 slots).  The strip's reads of these slots come after these writes in the wave's own
+    // LDS order, and the previous strip's reads before them: only the compiler's wait for the writes is needed.
+    __device__ __forceinline__ void stage_rows(const MatArgs& a, const MatPair& pd, int strip, int lane, unsigned* slab) {
+        constexpr int SW = 64 * W, RW = MAT_STRIDE / 4;
+        const unsigned* img = reinterpret_cast<const unsigned*>(a.prof);
+#pragma unroll
+        for (int p = 0; p < W; ++p) {
+            const unsigned* src = img + (size_t)min(strip * SW + lane * W + p, pd.n) * RW;
+            unsigned* dst = slab + (p * 64 + lane) * RW;
+#pragma unroll
+            for (int q = 0; q < RW; ++q) dst[q] = src[q];
         }
     }
 
@@ -418,7 +460,9 @@ __device__ __forceinline__ int band_nch(int i0, int SW, int m, int dlo, int dhi)
 // still used in place: a chunk at k0 stores rows <= k0 + 64 - SW <= k0, a row r is read by the chunk
 // that holds it, k0' <= r, and that read is complete before chunk k0' runs, so before any store of
 // chunk k0 >= k0'; which rows a strip skips changes nothing in that.
-template <int W, int MODE, int AM = AM_LOCAL, bool BAND = false>
+// PROFILE: the columns are the positions of a profile; s_tab is the wave's slab (MStrip above), filled again
+// before every strip.
+template <int W, int MODE, int AM = AM_LOCAL, bool BAND = false, bool PROFILE = false>
 __device__ void matrix_pair(const MatArgs& a, const MatPair& pd, const WalkPair& wp, const int lane, uint2* scr,
                             const signed char* s_tab, const unsigned char* s_code, unsigned char* ckpt = nullptr,
                             unsigned ckpt_stride = 0, const BandPair bp = BandPair{0, 0}) {
@@ -441,11 +485,12 @@ __device__ void matrix_pair(const MatArgs& a, const MatPair& pd, const WalkPair&
                         : scr_rsrc;
     unsigned toff = (unsigned)lane * 4u;
     int bM = 0, bD = 0, bJ = 0;   // TRACE: the best of the strips so far: t, i + j, j
-    MStrip<W, MODE, AM, BAND> S;
+    MStrip<W, MODE, AM, BAND, PROFILE> S;
     S.M = AM == AM_LOCAL ? 0 : MAT_NEG;
     if constexpr (AM != AM_LOCAL) S.Mj = 0;
     for (int strip = 0; strip < strips; ++strip) {
         S.setup(a, pd, strip, lane, s_code);
+        if constexpr (PROFILE) S.stage_rows(a, pd, strip, lane, reinterpret_cast<unsigned*>(const_cast<signed char*>(s_tab)));
         if constexpr (TRACE && AM == AM_LOCAL) {
             S.M = 0;
             S.Mkp = 0;
@@ -612,6 +657,19 @@ __device__ __forceinline__ MatLds matrix_stage(const MatArgs& a) {
     __syncthreads();
     return MatLds{reinterpret_cast<const signed char*>(s_tabw), reinterpret_cast<const unsigned char*>(s_codew)};
 }
+// PROFILE: the byte-to-code map alone is staged; the table is the wave's slab in the dynamic LDS, W * 64 slots
+// of MAT_STRIDE bytes a wave (MStrip above), which the launch sizes (profile_slab_bytes)
+constexpr int profile_slab_bytes(int W) { return 4 * W * 64 * MAT_STRIDE; }
+template <int W>
+__device__ __forceinline__ MatLds profile_stage(const MatArgs& a) {
+    __shared__ unsigned s_codew[64];
+    extern __shared__ unsigned s_slabw[];
+    if (threadIdx.x < 64) s_codew[threadIdx.x] = a.code[threadIdx.x];
+    __syncthreads();
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    return MatLds{reinterpret_cast<const signed char*>(s_slabw + wave * (W * 64 * MAT_STRIDE / 4)),
+                  reinterpret_cast<const unsigned char*>(s_codew)};
+}
 // the wave's next item; false: none is left
 __device__ __forceinline__ bool matrix_claim(const MatArgs& a, const int lane, unsigned& item) {
     item = 0;
@@ -640,9 +698,12 @@ __device__ __forceinline__ void matrix_claimed_pair(const MatArgs& a, const unsi
 }
 
 // BAND: the pair's diagonal range beside it; seq1 is across the lanes (table 0) in local mode too.
-template <int W, bool TRACE = false, int AM = AM_LOCAL, bool BAND = false>
+// PROFILE: seq1 is the profile of the launch (MatArgs::prof), pd.n its length for every item.
+template <int W, bool TRACE = false, int AM = AM_LOCAL, bool BAND = false, bool PROFILE = false>
 __global__ void __launch_bounds__(256) sw_matrix_kernel(MatArgs a) {
-    const MatLds s = matrix_stage(a);
+    MatLds s;
+    if constexpr (PROFILE) s = profile_stage<W>(a);
+    else s = matrix_stage(a);
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
     uint2* scr = a.scratch + (uint64_t)wave * (uint64_t)a.scratch_rows;
@@ -656,7 +717,7 @@ __global__ void __launch_bounds__(256) sw_matrix_kernel(MatArgs a) {
             bp = band_of(pd.n, pd.m, pd.swap_or_band);
             pd.swap_or_band = 0;
         }
-        matrix_pair<W, TRACE ? M_TRACE : M_SCORE, AM, BAND>(a, pd, wp, lane, scr, s.tab, s.code, nullptr, 0, bp);
+        matrix_pair<W, TRACE ? M_TRACE : M_SCORE, AM, BAND, PROFILE>(a, pd, wp, lane, scr, s.tab, s.code, nullptr, 0, bp);
     }
 }
 
@@ -1314,6 +1375,7 @@ __global__ void __launch_bounds__(64) sw_matrix_walk_window_kernel(WalkWindowArg
 struct FillKernel {
     const void* fn = nullptr;
     int wgs = 0;
+    int dyn = 0;   // dynamic LDS bytes of a workgroup (the profile kernels' slabs): they count in wgs
 };
 constexpr int W_OF[4] = {1, 2, 4, 8};
 constexpr int WI_TRACED = 4;   // a row of the table: the score-only kernels at W_OF, then the traced one
@@ -1324,6 +1386,16 @@ void name_fill_kernels(FillKernel (&row)[5]) {
     row[2].fn = (const void*)sw_matrix_kernel<4, false, AM, BAND>;
     row[3].fn = (const void*)sw_matrix_kernel<8, false, AM, BAND>;
     row[WI_TRACED].fn = (const void*)sw_matrix_kernel<TRACE_W, true, AM, BAND>;
+}
+
+template <int AM>
+void name_profile_kernels(FillKernel (&row)[5]) {   // as name_fill_kernels; a workgroup's slabs are dynamic LDS
+    row[0].fn = (const void*)sw_matrix_kernel<1, false, AM, false, true>;
+    row[1].fn = (const void*)sw_matrix_kernel<2, false, AM, false, true>;
+    row[2].fn = (const void*)sw_matrix_kernel<4, false, AM, false, true>;
+    row[3].fn = (const void*)sw_matrix_kernel<8, false, AM, false, true>;
+    row[WI_TRACED].fn = (const void*)sw_matrix_kernel<TRACE_W, true, AM, false, true>;
+    for (int k = 0; k < 5; ++k) row[k].dyn = profile_slab_bytes(k == WI_TRACED ? TRACE_W : W_OF[k]);
 }
 
 template <int AM>
@@ -1348,6 +1420,7 @@ enum {
     B_LONG, B_CKPT, B_ITEMS, B_STATE,                    // long pairs: locate items, checkpoints, strip items, walk states
     B_CPAIRS, B_CITEMS, B_EDGE, B_PROGRESS,              // cooperative score: pairs, items, edge columns, progress words
     B_ENDS, B_WINDOWS,                                   // long pairs on many waves: end-cell records, a round's windows
+    B_PROFILE,                                           // profile launches: the profile's device image
     B_COUNT
 };
 struct MatCtx {
@@ -1360,7 +1433,11 @@ struct MatCtx {
     FillKernel locate[3], strip[3];   // [SW_MODE_*]: the long path
     FillKernel coop[3][4];      // [SW_MODE_*][index into W_OF]
     FillKernel locate_coop[3];  // [SW_MODE_*]
+    FillKernel pfill[3][5];     // [SW_MODE_*][index into W_OF, or WI_TRACED]: the profile kernels
     MatCtx() {
+        name_profile_kernels<AM_LOCAL>(pfill[AM_LOCAL]);
+        name_profile_kernels<AM_GLOBAL>(pfill[AM_GLOBAL]);
+        name_profile_kernels<AM_SEMI>(pfill[AM_SEMI]);
         name_long_kernels<AM_LOCAL>(locate[AM_LOCAL], locate_coop[AM_LOCAL], strip[AM_LOCAL]);
         name_long_kernels<AM_GLOBAL>(locate[AM_GLOBAL], locate_coop[AM_GLOBAL], strip[AM_GLOBAL]);
         name_long_kernels<AM_SEMI>(locate[AM_SEMI], locate_coop[AM_SEMI], strip[AM_SEMI]);
@@ -1509,7 +1586,8 @@ MatPair make_pair(const DevSeq& p, int out_idx, bool swap, int band, WalkPair* w
 int fill_blocks(MatCtx* c, FillKernel& k, size_t items, long long scratch_rows, long long* out) {
     if (k.wgs == 0) {
         int nb = 0;
-        MCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k.fn, 256, 0));
+        if (k.dyn > 64 * 1024) MCHK(raise_dyn_lds(k.fn, k.dyn));   // past the default limit of a launch's dynamic LDS
+        MCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k.fn, 256, (size_t)k.dyn));
         k.wgs = std::max(1, std::min(nb, 8));
     }
     long long blocks = sw_get_option("blocks");
@@ -1523,8 +1601,9 @@ int fill_blocks(MatCtx* c, FillKernel& k, size_t items, long long scratch_rows, 
 // The pairs uploaded, the claim counter zeroed, the scratch sized (a right-edge column of scratch_rows
 // entries per wave of `blocks` workgroups), and the MatArgs fields every fill kernel reads.  long_group
 // passes scratch_rows = 0; its kernels never touch the scratch pointer, whatever it holds.
+// pf: a profile launch: mx is its alphabet, and its image goes up into a buffer of its own.
 int fill_args(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, const std::vector<MatPair>& pairs, int nscores,
-              int gap_init, int gap_ext, long long scratch_rows, long long blocks, MatArgs& a) {
+              int gap_init, int gap_ext, long long scratch_rows, long long blocks, MatArgs& a, const sw_profile* pf = nullptr) {
     if (ensure(c, B_PAIRS, pairs.size() * sizeof(MatPair)) || ensure(c, B_CTRL, sizeof(Ctrl)) ||
         ensure(c, B_SCRATCH, (size_t)scratch_rows * 8 * 4 * (size_t)blocks))
         return -1;
@@ -1540,6 +1619,11 @@ int fill_args(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, cons
     a.gap_init = gap_init;
     a.gap_ext = gap_ext;
     stage_matrix(a, mx);
+    if (pf) {
+        if (ensure(c, B_PROFILE, pf->image.size())) return -1;
+        MCHK(hipMemcpyAsync(c->buf[B_PROFILE], pf->image.data(), pf->image.size(), hipMemcpyHostToDevice, c->stream));
+        a.prof = (const unsigned char*)c->buf[B_PROFILE];
+    }
     return 0;
 }
 // the scratch column of a launch: the rows of its widest pair of more than one strip, in whole chunks
@@ -1553,13 +1637,15 @@ long long scratch_rows_of(const std::vector<MatPair>& pairs, int SW) {
 // act: the pairs to launch (both lengths > 0); d_scores[idx] receives each score, every other
 // entry of d_scores[0, nscores) is zeroed.  amode != SW_MODE_LOCAL: seq1 always across the lanes.
 // band >= 0: the band launches (seq1 across the lanes in every mode); -1: none.
+// pf: the profile launches: seq1 of every pair is the profile (alen = pf->n, a_off not read), always across the
+// lanes, and mx its alphabet.
 int launch(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, std::vector<DevSeq>& act, int gap_init,
-           int gap_ext, int* d_scores, int nscores, bool a_on_lanes, int amode, int band = -1) {
+           int gap_ext, int* d_scores, int nscores, bool a_on_lanes, int amode, int band = -1, const sw_profile* pf = nullptr) {
     const auto t0 = std::chrono::steady_clock::now();
     const bool banded = band >= 0;
-    if (amode != AM_LOCAL || banded) a_on_lanes = true;
+    if (amode != AM_LOCAL || banded || pf) a_on_lanes = true;
     sw_stats st{};
-    st.mode = banded ? MODE_MATRIX_BAND : MODE_MATRIX;
+    st.mode = pf ? MODE_MATRIX_PROFILE : banded ? MODE_MATRIX_BAND : MODE_MATRIX;
     st.variant = amode;   // free on score-only matrix launches: the alignment mode (SW_MODE_*)
     st.C = MAT_C;
     st.items = nscores;
@@ -1609,18 +1695,18 @@ int launch(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, std::ve
             cells += (long long)d.n * d.m;
         }
     }
-    FillKernel& kern = c->fill[banded][amode][wi];
+    FillKernel& kern = pf ? c->pfill[amode][wi] : c->fill[banded][amode][wi];
     const long long scratch_rows = scratch_rows_of(pairs, 64 * W);
     long long blocks = 0;
     MatArgs a{};
     if (fill_blocks(c, kern, pairs.size(), scratch_rows, &blocks) ||
-        fill_args(c, mx, d_arena, pairs, nscores, gap_init, gap_ext, scratch_rows, blocks, a))
+        fill_args(c, mx, d_arena, pairs, nscores, gap_init, gap_ext, scratch_rows, blocks, a, pf))
         return -1;
     a.scores = d_scores;
 
     MCHK(hipEventRecord(c->ev0, c->stream));
     void* kargs[] = {&a};
-    MCHK(hipLaunchKernel(kern.fn, dim3((unsigned)blocks), dim3(256), kargs, 0, c->stream));
+    MCHK(hipLaunchKernel(kern.fn, dim3((unsigned)blocks), dim3(256), kargs, (size_t)kern.dyn, c->stream));
     MCHK(hipGetLastError());
     MCHK(hipEventRecord(c->ev1, c->stream));
     MCHK(hipStreamSynchronize(c->stream));
@@ -1909,9 +1995,9 @@ struct TracedOut {
     int blocks = 0;
 };
 int launch_traced(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, const std::vector<DevSeq>& act,
-                  int gap_init, int gap_ext, TracedOut& o, int amode, int band = -1) {
+                  int gap_init, int gap_ext, TracedOut& o, int amode, int band = -1, const sw_profile* pf = nullptr) {
     const bool banded = band >= 0;
-    FillKernel& kern = c->fill[banded][amode][WI_TRACED];
+    FillKernel& kern = pf ? c->pfill[amode][WI_TRACED] : c->fill[banded][amode][WI_TRACED];
     const size_t np = act.size();
     const std::vector<int> order = longest_first(act);
     std::vector<MatPair> pairs(np);
@@ -1934,7 +2020,7 @@ int launch_traced(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, 
     long long blocks = 0;
     MatArgs a{};
     if (fill_blocks(c, kern, np, scratch_rows, &blocks) ||
-        fill_args(c, mx, d_arena, pairs, (int)np, gap_init, gap_ext, scratch_rows, blocks, a) ||
+        fill_args(c, mx, d_arena, pairs, (int)np, gap_init, gap_ext, scratch_rows, blocks, a, pf) ||
         ensure(c, B_WALK, np * sizeof(WalkPair)) || ensure(c, B_TRACE, (size_t)trace_total) ||
         ensure(c, B_RES, np * sizeof(TraceRes)) || ensure(c, B_OPS, (size_t)ops_total))
         return -1;
@@ -1947,7 +2033,7 @@ int launch_traced(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, 
 
     MCHK(hipEventRecord(c->ev0, c->stream));
     void* kargs[] = {&a};
-    MCHK(hipLaunchKernel(kern.fn, dim3((unsigned)blocks), dim3(256), kargs, 0, c->stream));
+    MCHK(hipLaunchKernel(kern.fn, dim3((unsigned)blocks), dim3(256), kargs, (size_t)kern.dyn, c->stream));
     MCHK(hipGetLastError());
     MCHK(hipEventRecord(c->ev1, c->stream));
     if (banded) hipLaunchKernelGGL(sw_matrix_walk_kernel<true>, dim3((unsigned)((np + 63) / 64)), dim3(64), 0, c->stream, w);
@@ -2348,7 +2434,7 @@ int matrix_align_long_device(const sw_matrix* mx, const unsigned char* d_arena, 
 
 int matrix_align_device(const sw_matrix* mx, const unsigned char* d_arena, const int64_t* a_off, const int* alen,
                         const int64_t* b_off, const int* blen, const int* name_idx, int npairs, int gap_init,
-                        int gap_ext, const char* what, AlignSink& sink, int amode, int band) {
+                        int gap_ext, const char* what, AlignSink& sink, int amode, int band, const sw_profile* pf) {
     const auto t0 = std::chrono::steady_clock::now();
     if (!gaps_ok(gap_init, gap_ext)) return -1;
     const long long budget = sw_get_option("trace_mb") << 20;
@@ -2373,7 +2459,12 @@ int matrix_align_device(const sw_matrix* mx, const unsigned char* d_arena, const
         const long long need = pair_trace(alen[k], blen[k]);
         if (need > budget) {
             char m[400];
-            if (banded)
+            if (pf)
+                std::snprintf(m, sizeof m,
+                              "%s %d: a %d x %d alignment needs %lld bytes of trace memory, more than option trace_mb = %lld "
+                              "MiB, and there is no long path with a profile",
+                              what, name_idx ? name_idx[k] : k, alen[k], blen[k], need, budget >> 20);
+            else if (banded)
                 std::snprintf(m, sizeof m,
                               "%s %d: a %d x %d alignment in a band of %d needs %lld bytes of trace memory, more than option "
                               "trace_mb = %lld MiB: a narrower band or a larger trace_mb aligns this pair",
@@ -2398,7 +2489,7 @@ int matrix_align_device(const sw_matrix* mx, const unsigned char* d_arena, const
     t_fill_ms = t_walk_ms = t_locate_ms = 0.f;
     t_rounds = 0;
     sw_stats st{};
-    st.mode = banded ? MODE_MATRIX_BAND_TRACE : MODE_MATRIX_TRACE;
+    st.mode = pf ? MODE_MATRIX_PROFILE_TRACE : banded ? MODE_MATRIX_BAND_TRACE : MODE_MATRIX_TRACE;
     st.W = TRACE_W;
     st.C = MAT_C;
     st.items = npairs;
@@ -2418,10 +2509,10 @@ int matrix_align_device(const sw_matrix* mx, const unsigned char* d_arena, const
             st.cells += pair_cells(alen[hi], blen[hi]);
         }
         if (!act.empty()) {
-            if (launch_traced(c, mx, d_arena, act, gap_init, gap_ext, o, amode, band)) return -1;
+            if (launch_traced(c, mx, d_arena, act, gap_init, gap_ext, o, amode, band, pf)) return -1;
             st.variant += 1;
             st.blocks = o.blocks;
-            st.waves_per_cu = 4 * c->fill[banded][amode][WI_TRACED].wgs;
+            st.waves_per_cu = 4 * (pf ? c->pfill[amode][WI_TRACED] : c->fill[banded][amode][WI_TRACED]).wgs;
             st.boundary_bytes = std::max(st.boundary_bytes, o.trace_total);
         }
         size_t s = 0;
@@ -2462,6 +2553,26 @@ int matrix_score_device(const sw_matrix* mx, const unsigned char* d_arena, const
     for (int k = 0; k < npairs; ++k)
         if (alen[k] > 0 && blen[k] > 0) act.push_back(DevSeq{a_off[k], b_off[k], alen[k], blen[k], k});
     return launch(c, mx, d_arena, act, gap_init, gap_ext, d_scores, npairs, a_on_lanes, amode);
+}
+
+int profile_score_device(const sw_profile* pf, const unsigned char* d_arena, const int64_t* b_off, const int* blen, int nseq,
+                         int gap_init, int gap_ext, int* d_scores, int amode) {
+    if (!gaps_ok(gap_init, gap_ext)) return -1;
+    MatCtx* c = get_mctx();
+    if (!c) return -1;
+    std::vector<DevSeq> act;
+    for (int k = 0; k < nseq; ++k)
+        if (blen[k] > 0) act.push_back(DevSeq{0, b_off[k], pf->n, blen[k], k});
+    return launch(c, &pf->alpha, d_arena, act, gap_init, gap_ext, d_scores, nseq, true, amode, -1, pf);
+}
+
+int profile_align_device(const sw_profile* pf, const unsigned char* d_arena, const int64_t* b_off, const int* blen,
+                         const int* name_idx, int nseq, int gap_init, int gap_ext, const char* what, AlignSink& sink,
+                         int amode) {
+    const std::vector<int64_t> a_off((size_t)nseq, 0);
+    const std::vector<int> alen((size_t)nseq, pf->n);
+    return matrix_align_device(&pf->alpha, d_arena, a_off.data(), alen.data(), b_off, blen, name_idx, nseq, gap_init, gap_ext,
+                               what, sink, amode, -1, pf);
 }
 
 }  // namespace swmi
@@ -2669,6 +2780,62 @@ int sw_align_long_plan(int n, int m, sw_align_plan* out) {
     long long ckpt_budget = 0;
     if (align_ckpt_budget(&ckpt_budget)) return -1;
     return align_long_plan(n, m, sw_get_option("trace_mb") << 20, ckpt_budget, "pair", 0, out);
+}
+
+// The sequences of a profile call in one arena, as score_host lays seq2 out (the profile has no bytes there).
+static int profile_upload(MatCtx* c, const unsigned char* const* seqs, const int* lens, int nseq, std::vector<int64_t>& b_off) {
+    b_off.assign((size_t)nseq, 0);
+    size_t total = 0;
+    for (int k = 0; k < nseq; ++k) {
+        b_off[(size_t)k] = (int64_t)total;
+        total += ((size_t)lens[k] + 15) / 16 * 16;
+    }
+    std::vector<unsigned char> arena(total);
+    for (int k = 0; k < nseq; ++k)
+        if (lens[k] > 0) std::memcpy(arena.data() + b_off[(size_t)k], seqs[k], (size_t)lens[k]);
+    if (ensure(c, B_ARENA, total)) return -1;
+    if (total) MCHK(hipMemcpy(c->buf[B_ARENA], arena.data(), total, hipMemcpyHostToDevice));
+    return 0;
+}
+
+int sw_score_profile_batch(const sw_profile* pf, const unsigned char* const* seqs, const int* lens, int nseq, int gap_init,
+                           int gap_ext, int mode, int* scores_out) {
+    if (profile_check("sw_score_profile_batch", pf, seqs, lens, nseq, gap_init, gap_ext, mode)) return -1;
+    if (nseq > 0 && !scores_out) {
+        report_error("sw_score_profile_batch: invalid arguments");
+        return -1;
+    }
+    if (nseq == 0) return 0;
+    MatCtx* c = get_mctx();
+    if (!c) return -1;
+    std::vector<int64_t> b_off;
+    if (profile_upload(c, seqs, lens, nseq, b_off) || ensure(c, B_SCORES, (size_t)nseq * sizeof(int))) return -1;
+    if (profile_score_device(pf, (const unsigned char*)c->buf[B_ARENA], b_off.data(), lens, nseq, gap_init, gap_ext,
+                             (int*)c->buf[B_SCORES], mode))
+        return -1;
+    MCHK(hipMemcpy(scores_out, c->buf[B_SCORES], (size_t)nseq * sizeof(int), hipMemcpyDeviceToHost));
+    if (mode != SW_MODE_LOCAL)   // empty sequences are answered on the host
+        for (int k = 0; k < nseq; ++k)
+            if (lens[k] == 0) scores_out[k] = mode_empty_score(pf->n, 0, gap_init, gap_ext, mode);
+    return 0;
+}
+
+int sw_align_profile_batch(const sw_profile* pf, const unsigned char* const* seqs, const int* lens, int nseq, int gap_init,
+                           int gap_ext, int mode, sw_alignment* out, unsigned* cigar, long long cigar_cap,
+                           long long* cigar_used) {
+    if (profile_align_check("sw_align_profile_batch", pf, seqs, lens, nseq, gap_init, gap_ext, mode, out, cigar, cigar_cap,
+                            cigar_used))
+        return -1;
+    AlignSink sink{out, {}};
+    if (nseq == 0) return sink.finish(cigar, cigar_cap, cigar_used);
+    MatCtx* c = get_mctx();
+    if (!c) return -1;
+    std::vector<int64_t> b_off;
+    if (profile_upload(c, seqs, lens, nseq, b_off)) return -1;
+    if (profile_align_device(pf, (const unsigned char*)c->buf[B_ARENA], b_off.data(), lens, nullptr, nseq, gap_init, gap_ext,
+                             "sequence", sink, mode))
+        return -1;
+    return sink.finish(cigar, cigar_cap, cigar_used);
 }
 
 void sw_last_align_ms(float* fill_ms, float* walk_ms) {

@@ -1,6 +1,7 @@
 // sw_matrix_host.cpp -- substitution matrices, host only (no HIP): creation from a table, the
 // NCBI text format, the byte-to-code map the kernel uses (sw_matrix.hip stages this very array)
 // and the accessors of include/algoGPU.h.  No named matrix is compiled in: users pass a file.
+// And profiles (sw_profile_*): n positions over a matrix object's alphabet, their text format and the device image.
 #include "sw_matrix_host.h"
 #include "../../include/algoGPU.h"
 
@@ -121,6 +122,92 @@ sw_matrix* parse(const char* text, size_t nbytes) {
     return make(sym, k, sc, other, 0);
 }
 
+// ---- profiles: n positions over a matrix object's alphabet ----
+
+sw_profile* pfail(const char* fmt, long long a = 0, long long b = 0) {
+    fail(fmt, a, b);
+    return nullptr;
+}
+
+// scores: n * k entries, row-major by position (long long: the parser's values, checked here)
+template <class T>
+sw_profile* make_profile(const unsigned char* symbols, int k, const T* scores, long long n, int other, int flags) {
+    if (k < 1 || k > SW_MATRIX_MAX_K) return pfail("profile: %lld symbols (need 1 to 32)", k);
+    if (n < 1) return pfail("profile: %lld positions (need at least 1)", n);
+    if (n > SW_PROFILE_MAX_N) return pfail("profile: %lld positions are more than SW_PROFILE_MAX_LENGTH = %lld", n, SW_PROFILE_MAX_N);
+    if (!symbols || !scores) return pfail("profile: null table");
+    for (long long i = 0; i < n * k; ++i)
+        if (scores[i] < -127 || scores[i] > 127)
+            return pfail("profile: position %lld: entry %lld is outside [-127, 127]", i / k, (long long)scores[i]);
+    // the alphabet is a matrix object's: its checks (duplicates, other, flags), its byte-to-code map, an id
+    const signed char none[SW_MATRIX_MAX_K * SW_MATRIX_MAX_K] = {};
+    sw_matrix* al = make(symbols, k, none, other, flags);
+    if (!al) return nullptr;
+    sw_profile* p = new sw_profile();
+    p->alpha = *al;
+    delete al;
+    p->n = (int)n;
+    p->sc.resize((size_t)n * (size_t)k);
+    p->image.assign(((size_t)n + 1) * SW_PROFILE_STRIDE, 0);
+    for (long long i = 0; i <= n; ++i) {
+        signed char* row = p->image.data() + (size_t)i * SW_PROFILE_STRIDE;
+        for (int c = 0; c < k && i < n; ++c) {
+            const signed char v = (signed char)scores[i * k + c];
+            p->sc[(size_t)(i * k + c)] = v;
+            row[c] = v;
+            p->alpha.max_entry = v > p->alpha.max_entry ? v : p->alpha.max_entry;
+        }
+        row[k] = (signed char)SW_PROFILE_SENT;
+    }
+    return p;
+}
+
+// The profile text format (include/algoGPU.h): '#' comment lines, a header line of K symbols, then one row
+// a position: a one-byte label (the consensus residue, not read) and K integers.
+sw_profile* parse_profile(const char* text, size_t nbytes) {
+    std::vector<std::string> tok;
+    unsigned char sym[SW_MATRIX_MAX_K];
+    std::vector<long long> sc;
+    int k = 0, other = -1, line_no = 0;
+    long long rows = 0;
+    const char* p = text;
+    const char* const end = text + nbytes;
+    while (p < end) {
+        const char* e = (const char*)std::memchr(p, '\n', (size_t)(end - p));
+        if (!e) e = end;
+        ++line_no;
+        split(p, e, tok);
+        p = e < end ? e + 1 : end;
+        if (tok.empty() || tok[0][0] == '#') continue;   // (so '#' cannot label a row)
+        if (k == 0) {   // the header: one symbol per token
+            if (tok.size() > (size_t)SW_MATRIX_MAX_K) return pfail("profile file: %lld symbols (at most 32)", (long long)tok.size());
+            for (const std::string& t : tok) {
+                if (t.size() != 1) return pfail("profile file line %lld: a symbol must be one byte", line_no);
+                for (int i = 0; i < k; ++i)
+                    if (sym[i] == (unsigned char)t[0]) return pfail("profile file: duplicate symbol 0x%02llx", (unsigned char)t[0]);
+                if (t[0] == '*') other = k;
+                sym[k++] = (unsigned char)t[0];
+            }
+            continue;
+        }
+        if (rows >= SW_PROFILE_MAX_N)
+            return pfail("profile file line %lld: more than SW_PROFILE_MAX_LENGTH = %lld positions", line_no, SW_PROFILE_MAX_N);
+        if (tok[0].size() != 1) return pfail("profile file line %lld: the row label must be one byte", line_no);
+        if (tok.size() != (size_t)k + 1)
+            return pfail("profile file line %lld: %lld entries in the row, not one a symbol", line_no, (long long)tok.size() - 1);
+        for (int j = 0; j < k; ++j) {
+            long long v = 0;
+            if (!to_int(tok[(size_t)j + 1], &v)) return pfail("profile file line %lld: entry %lld is not an integer", line_no, j);
+            if (v < -127 || v > 127) return pfail("profile file line %lld: entry %lld is outside [-127, 127]", line_no, v);
+            sc.push_back(v);
+        }
+        ++rows;
+    }
+    if (k == 0) return pfail("profile file: no header line and no rows");
+    if (rows == 0) return pfail("profile file: no rows at all");
+    return make_profile(sym, k, sc.data(), rows, other, 0);
+}
+
 }  // namespace
 
 long long matrix_first_bad(const sw_matrix* m, const unsigned char* p, long long len) {
@@ -193,5 +280,84 @@ int sw_matrix_score(const sw_matrix* m, unsigned char a, unsigned char b, int* o
 }
 
 void sw_matrix_free(sw_matrix* m) { delete m; }
+
+sw_profile* sw_profile_create(const unsigned char* symbols, int k, const signed char* scores, int n, int other, int flags) {
+    return make_profile(symbols, k, scores, n, other, flags);
+}
+
+sw_profile* sw_profile_from_matrix(const sw_matrix* mx, const unsigned char* query, int qlen) {
+    if (!mx || qlen < 0 || (qlen > 0 && !query)) return pfail("sw_profile_from_matrix: invalid arguments");
+    if (qlen < 1) return pfail("profile: %lld positions (need at least 1)", qlen);
+    if (qlen > SW_PROFILE_MAX_N) return pfail("profile: %lld positions are more than SW_PROFILE_MAX_LENGTH = %lld", qlen, SW_PROFILE_MAX_N);
+    std::vector<signed char> sc((size_t)qlen * (size_t)mx->k);
+    for (int i = 0; i < qlen; ++i) {
+        const int c = mx->code[query[i]];
+        if (c == SW_MATRIX_NOCODE) return pfail("query position %lld: byte 0x%02llx is outside the matrix alphabet", i, query[i]);
+        std::memcpy(sc.data() + (size_t)i * (size_t)mx->k, mx->sc + c * mx->k, (size_t)mx->k);
+    }
+    return make_profile(mx->sym, mx->k, sc.data(), qlen, mx->other, mx->flags);
+}
+
+sw_profile* sw_profile_parse(const char* text, long long nbytes) {
+    if (nbytes < 0 || (nbytes > 0 && !text)) return pfail("sw_profile_parse: invalid arguments");
+    return parse_profile(text, (size_t)nbytes);
+}
+
+sw_profile* sw_profile_open(const char* path) {
+    if (!path) return pfail("sw_profile_open: null path");
+    std::FILE* f = std::fopen(path, "rb");
+    if (!f) {
+        const std::string msg = std::string("cannot open profile file ") + path;
+        report_error(msg.c_str());
+        return nullptr;
+    }
+    constexpr size_t LIMIT = (size_t)1 << 30;   // SW_PROFILE_MAX_LENGTH rows of 32 entries fit; anything larger is refused
+    std::vector<char> buf;
+    char chunk[65536];
+    size_t got = 0;
+    while ((got = std::fread(chunk, 1, sizeof chunk, f)) > 0) {
+        buf.insert(buf.end(), chunk, chunk + got);
+        if (buf.size() > LIMIT) break;
+    }
+    std::fclose(f);
+    if (buf.size() > LIMIT) return pfail("profile file: larger than 1 GiB");
+    return parse_profile(buf.data(), buf.size());
+}
+
+int sw_profile_length(const sw_profile* p) { return p ? p->n : -1; }
+
+int sw_profile_size(const sw_profile* p) { return p ? p->alpha.k : -1; }
+
+int sw_profile_symbols(const sw_profile* p, unsigned char* out) {
+    if (!p || !out) {
+        report_error("sw_profile_symbols: invalid arguments");
+        return -1;
+    }
+    std::memcpy(out, p->alpha.sym, (size_t)p->alpha.k);
+    return p->alpha.k;
+}
+
+int sw_profile_score(const sw_profile* p, int pos, unsigned char byte, int* out) {
+    if (!p || !out) {
+        report_error("sw_profile_score: invalid arguments");
+        return -1;
+    }
+    char msg[96];
+    if (pos < 0 || pos >= p->n) {
+        std::snprintf(msg, sizeof msg, "position %d is outside the profile's [0, %d)", pos, p->n);
+        report_error(msg);
+        return -1;
+    }
+    const int c = p->alpha.code[byte];
+    if (c == SW_MATRIX_NOCODE) {
+        std::snprintf(msg, sizeof msg, "byte 0x%02x is outside the profile alphabet", byte);
+        report_error(msg);
+        return -1;
+    }
+    *out = p->sc[(size_t)pos * (size_t)p->alpha.k + (size_t)c];
+    return 0;
+}
+
+void sw_profile_free(sw_profile* p) { delete p; }
 
 }  // extern "C"

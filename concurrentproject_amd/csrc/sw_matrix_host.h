@@ -26,6 +26,22 @@ struct sw_matrix {
                                                           // a database's "records checked" cache
 };
 
+// ---- position-specific scoring (include/algoGPU.h sw_profile_*) ----
+constexpr int SW_PROFILE_MAX_N = 1 << 22;   // positions of a profile (include/algoGPU.h SW_PROFILE_MAX_LENGTH)
+constexpr int SW_PROFILE_STRIDE = 36;       // bytes a row of the device image: sw_matrix.hip's MAT_STRIDE
+constexpr int SW_PROFILE_SENT = -127;       // column K of a row, the "no row" code: sw_matrix.hip's MAT_SENT
+
+// n positions over the alphabet of a matrix object: P[i][c] scores symbol c of the sequence at position i.
+// Immutable after creation: any thread may read it at once.
+struct sw_profile {
+    sw_matrix alpha;                  // the alphabet: k, sym, other, flags, code, and an id of its own; max_entry is the
+                                      // profile's (max(0, largest entry)); its table sc is not used
+    int n = 0;                        // positions
+    std::vector<signed char> sc;      // sc[i * k + c]
+    std::vector<signed char> image;   // what the kernels read: n + 1 rows of SW_PROFILE_STRIDE bytes, row i = P[i][0..k)
+                                      // and SW_PROFILE_SENT at column k; row n, for the columns past the end, zeros
+};
+
 namespace swmi {
 // sets the calling thread's sw_last_error() text (sw_engine.hip)
 void report_error(const char* msg);
@@ -92,7 +108,28 @@ void align_mode_empty(AlignSink& sink, int k, int alen, int blen, int gap_init, 
 // band >= 0: the band launches (below), whose trace is the band's; -1: the whole matrix.
 int matrix_align_device(const sw_matrix* m, const unsigned char* d_arena, const int64_t* a_off, const int* alen,
                         const int64_t* b_off, const int* blen, const int* name_idx, int npairs, int gap_init,
-                        int gap_ext, const char* what, AlignSink& sink, int amode, int band = -1);
+                        int gap_ext, const char* what, AlignSink& sink, int amode, int band = -1,
+                        const sw_profile* pf = nullptr);
+
+// ---- position-specific scoring: the profile launches (sw_matrix.hip PROFILE) ----
+// As matrix_score_device / matrix_align_device with the profile as seq1 (across the lanes, never swapped, no
+// bytes in the arena) and d_arena[b_off[k], +blen[k]) as seq2, checked against pf->alpha by the caller, who
+// also answers for the range refusals (profile_check) and, for the scores, the empty sequences.
+int profile_score_device(const sw_profile* pf, const unsigned char* d_arena, const int64_t* b_off, const int* blen,
+                         int nseq, int gap_init, int gap_ext, int* d_scores, int amode);
+int profile_align_device(const sw_profile* pf, const unsigned char* d_arena, const int64_t* b_off, const int* blen,
+                         const int* name_idx, int nseq, int gap_init, int gap_ext, const char* what, AlignSink& sink,
+                         int amode);
+// the argument, mode, gap, length, range and alphabet checks of the sw_*_profile_* entry points (fn names the
+// entry point; a sequence is named "sequence k"); the align calls' output arguments as well.  0 or -1.
+int profile_check(const char* fn, const sw_profile* pf, const unsigned char* const* seqs, const int* lens, int nseq,
+                  int gap_init, int gap_ext, int mode);
+int profile_align_check(const char* fn, const sw_profile* pf, const unsigned char* const* seqs, const int* lens, int nseq,
+                        int gap_init, int gap_ext, int mode, const sw_alignment* out, const unsigned* cigar,
+                        long long cigar_cap, const long long* cigar_used);
+// the refusals of one sequence of length len against pf, before any device work: mode_range_ok in a mode, and
+// the int32 score range (min(n, len) * largest entry < 2^28); the message names `what idx`
+bool profile_range_ok(const sw_profile* pf, int len, int gap_init, int gap_ext, int amode, const char* what, int idx);
 
 // ---- banded alignment (include/algoGPU.h sw_*_band) ----
 // The arithmetic is host only (sw_align_host.cpp); sw_matrix.hip's kernels compute the same per strip.

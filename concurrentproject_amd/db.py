@@ -209,6 +209,39 @@ class Database:
             self._h, matrix._handle(), _ptr(q), len(q), IDX, n, int(gap_init), int(gap_ext), am, out, cig, cap, used), n,
             max(16 * n, _LONG_CIGAR_CAP))
 
+    # ---- profiles (position-specific scoring: concurrentproject_amd.Profile) ----------------------
+    def search_profile(self, profile, gap_init: int, gap_ext: int, mode: str = "local") -> np.ndarray:
+        """int32 score of ``profile`` (seq1) against every record, in record order (sw_db_search_profile);
+        ``mode`` as in :meth:`search`.  The records are checked against the profile's alphabet once."""
+        out = np.zeros(len(self), dtype=np.int32)
+        _check(lib().sw_db_search_profile(self._h, profile._handle(), int(gap_init), int(gap_ext), _mode(mode),
+                                          out.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+        return out
+
+    def align_profile(self, profile, indices, gap_init: int, gap_ext: int, mode: str = "local") -> list:
+        """An :class:`Alignment` of ``profile`` (seq1) with each record of ``indices``, out of the database's
+        device arena (sw_db_align_profile)."""
+        am = _mode(mode)
+        idx = [int(i) for i in indices]
+        n = len(idx)
+        if n == 0:
+            return []
+        IDX = (ctypes.c_int * n)(*idx)
+        return _align_call(lambda out, cig, cap, used: lib().sw_db_align_profile(
+            self._h, profile._handle(), IDX, n, int(gap_init), int(gap_ext), am, out, cig, cap, used), n, 16 * n)
+
+    def top_profile(self, profile, k: int = 10, gap_init: int = 0, gap_ext: int = 0, alignments: bool = False,
+                    mode: str = "local") -> list:
+        """:meth:`top` for a profile: the k best records as [(score, index, header)], score descending, index
+        ascending on ties; with ``alignments=True`` each tuple ends with the hit's :class:`Alignment`."""
+        sc = self.search_profile(profile, gap_init, gap_ext, mode=mode)
+        idx = np.lexsort((np.arange(len(sc)), -sc.astype(np.int64)))[:k]
+        hits = [(int(sc[i]), int(i), self.header(int(i))) for i in idx]
+        if not alignments:
+            return hits
+        al = self.align_profile(profile, [h[1] for h in hits], gap_init, gap_ext, mode=mode)
+        return [h + (x,) for h, x in zip(hits, al)]
+
     def top(self, query, k: int = 10, matrix=None, gap_init=None, gap_ext=None, alignments: bool = False,
             mode: str = "local") -> list:
         """The k best records: [(score, index, header)], score descending, index ascending on ties.

@@ -620,6 +620,80 @@ int  sw_db_align_matrix_long_coop_mode(sw_db*, const sw_matrix*, const unsigned 
                                        const int* record_idx, int nidx, int gap_init, int gap_ext, int mode,
                                        sw_alignment* out, unsigned* cigar, long long cigar_cap, long long* cigar_used);
 
+/* ---- position-specific scoring: profiles ------------------------------------------
+ * A PROFILE is n positions (1 <= n <= SW_PROFILE_MAX_LENGTH) over an alphabet of K <= 32 byte symbols, and a
+ * table of entries in [-127, 127]: scores[i*K + c] is what symbol c of the sequence scores at position i.  The
+ * alphabet is a matrix object's: `other`, SW_MATRIX_FOLD_CASE and the same 256-byte byte-to-code map.  A PSSM,
+ * a family profile, a query with masked or up-weighted positions, a DNA query with degenerate positions are
+ * such tables: the score of a cell depends on the query POSITION, not on a query residue.  A profile is
+ * immutable and may be used from any thread at once.
+ *
+ * SEMANTICS.  The recurrence, the three modes (SW_MODE_*), the gap model, the end-cell rule, the walk and the
+ * tie rules of sw_score_matrix_batch_mode / sw_align_matrix_batch_mode hold word for word with s(seq1[i], seq2[j])
+ * replaced by P[i][code(seq[j])].  The profile is seq1, index i: an I consumes a profile position, beg1 and end1
+ * are profile positions, and in SW_MODE_SEMIGLOBAL the profile is the query that is covered end to end.  The
+ * sequence is seq2.  The profile is never laid on the streaming side (it has no bytes to stream).
+ *
+ * sw_profile_create: from a table of n*k entries, row-major by position.  NULL on error (sw_last_error): n < 1 or
+ *   above SW_PROFILE_MAX_LENGTH (named), k outside 1..32, a duplicate symbol, a bad `other` or flags, an entry -128.
+ * sw_profile_from_matrix: row i is the matrix row of query byte i, P[i][c] = T[code(q_i)][c], so that the profile
+ *   calls give what the matrix calls give for that query as seq1.  A query byte outside the matrix alphabet is an
+ *   error that names the position.
+ * sw_profile_parse / sw_profile_open: a text format of this library's own (it is not any other tool's PSSM
+ *   format): a line whose first token begins with '#' is a comment; the first other line is the header, K symbols
+ *   of one byte each ('*' becomes `other`); every further line is one position: a one-byte label (the position's
+ *   consensus residue: not read when scoring, and not '#') and K integers.  Any run of blanks separates tokens;
+ *   CRLF and a missing final newline are accepted.  NULL with a message for a row that has not K entries, a label
+ *   or symbol wider than a byte, a duplicate symbol, more than 32 symbols, an entry outside +-127, a token that
+ *   is not an integer, no header, no rows, or more than SW_PROFILE_MAX_LENGTH rows.
+ * sw_profile_length / sw_profile_size / sw_profile_symbols: n; K; the K bytes (returns K).
+ * sw_profile_score: *out = P[pos][code(byte)]; -1 for a position outside [0, n) or a byte without a code.
+ * sw_score_profile_batch: scores_out[k] = the score of the profile against seqs[k] in `mode`; one launch; 0 or -1.
+ *   An empty sequence is answered on the host: 0 in SW_MODE_LOCAL, else the profile as one gap run,
+ *   -(gap_init + (n - 1) * min(gap_ext, gap_init)).  Refused before anything is launched: an unknown mode, a
+ *   sequence with min(n, len) * max(0, largest entry) >= 2^28, in the two other modes a sequence over the SCORE
+ *   RANGE bound of sw_score_matrix_batch_mode with the profile as seq1, and a byte outside the alphabet (-1;
+ *   sw_last_error names "sequence k", the position and the byte).
+ *   The kernels are one more instantiation of the matrix kernels (sw_matrix.hip PROFILE): score-only at 1, 2, 4
+ *   and 8 columns a lane, chosen by the matrix kernels' cost estimate (option "W" forces one); every wave keeps
+ *   the rows of its strip's columns in an LDS slab of its own (9216 * W bytes a workgroup), copied before each
+ *   strip from a device image of the profile, (n + 1) * 36 bytes uploaded on every call.  Option "blocks" is
+ *   honoured.  sw_last_stats: mode 13, W, variant = the alignment mode, as mode 6.
+ * sw_align_profile_batch: an alignment per sequence, by the traced instantiation (W = 8) and the matrix path's
+ *   walk; out, cigar, cigar_cap, cigar_used and option "trace_mb" as sw_align_matrix_batch_mode, with n the
+ *   profile's length.  A sequence whose trace does not fit trace_mb alone is refused: there is no long path
+ *   with a profile.  sw_last_stats: mode 14, otherwise as mode 7.
+ * sw_align_profile_cpu: the same arguments and, bit for bit, the same alignments from the host aligner of
+ *   sw_align_matrix_cpu / sw_align_matrix_cpu_mode (n * len bytes a sequence, at most 2^32 cells).
+ * sw_db_search_profile / sw_db_align_profile: as sw_db_search_matrix_mode / sw_db_align_matrix_mode with the
+ *   profile in the query's place: nothing of it enters the arena.  The records are checked against the
+ *   profile's alphabet once per (database, profile).
+ * Not built: a band, the cooperative and the long paths with a profile; many profiles in one call;
+ * position-specific gap penalties; building a profile from an alignment. */
+typedef struct sw_profile sw_profile;
+#define SW_PROFILE_MAX_LENGTH (1 << 22)
+sw_profile* sw_profile_create(const unsigned char* symbols, int k, const signed char* scores /* n*k */, int n,
+                              int other, int flags);
+sw_profile* sw_profile_from_matrix(const sw_matrix*, const unsigned char* query, int qlen);
+sw_profile* sw_profile_parse(const char* text, long long nbytes);
+sw_profile* sw_profile_open(const char* path);
+int  sw_profile_length(const sw_profile*);
+int  sw_profile_size(const sw_profile*);
+int  sw_profile_symbols(const sw_profile*, unsigned char* out /* k bytes */);
+int  sw_profile_score(const sw_profile*, int pos, unsigned char byte, int* out);
+void sw_profile_free(sw_profile*);
+int  sw_score_profile_batch(const sw_profile*, const unsigned char* const* seqs, const int* lens, int nseq,
+                            int gap_init, int gap_ext, int mode, int* scores_out);
+int  sw_align_profile_batch(const sw_profile*, const unsigned char* const* seqs, const int* lens, int nseq,
+                            int gap_init, int gap_ext, int mode, sw_alignment* out,
+                            unsigned* cigar, long long cigar_cap, long long* cigar_used);
+int  sw_align_profile_cpu(const sw_profile*, const unsigned char* const* seqs, const int* lens, int nseq,
+                          int gap_init, int gap_ext, int mode, sw_alignment* out,
+                          unsigned* cigar, long long cigar_cap, long long* cigar_used);
+int  sw_db_search_profile(sw_db*, const sw_profile*, int gap_init, int gap_ext, int mode, int* scores_out);
+int  sw_db_align_profile(sw_db*, const sw_profile*, const int* record_idx, int nidx, int gap_init, int gap_ext,
+                         int mode, sw_alignment* out, unsigned* cigar, long long cigar_cap, long long* cigar_used);
+
 /* Tuning knobs (process-wide).  Keys:
  *   "W"        columns per lane: 0 = auto, 1, 2, 4, 8
  *   "C"        rows per strip hand-off chunk: 0 = auto, 16, 32, 64
@@ -639,7 +713,8 @@ int  sw_db_align_matrix_long_coop_mode(sw_db*, const sw_matrix*, const unsigned 
  *              sw_*_matrix entry points, which honour "blocks" and "W" only; and mode 7 = the
  *              traced launches of sw_align_matrix_batch / sw_db_align_matrix: "blocks", "trace_mb";
  *              and mode 8 = their _long counterparts, which honour the same two; and modes 9 and 10 =
- *              the band launches, score-only and traced: sw_*_band, as modes 6 and 7)
+ *              the band launches, score-only and traced: sw_*_band, as modes 6 and 7; and modes 13 and 14 =
+ *              the profile launches, score-only and traced: sw_*_profile_*, as modes 6 and 7)
  *   "trace_mb" MiB of trace memory one traced launch may hold, 1..3072 (default 1024)
  *   "duo16"    1 = (default) packed duos take max3 through v_pk_maximum3_f16 when every
  *              value stays below 0x7C00 (MATCH*(min(n,m)+1) <= 31743), 0 = u16 max only

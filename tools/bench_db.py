@@ -17,9 +17,14 @@ by mutated copies of the query, so that the top hits have real alignments (with 
 --mode global|semiglobal (with --matrix): the same search, alignments and timings in that alignment mode
 (Database.search(mode=...)); the lines then carry "align_mode".
 
+--profile (with --matrix): a further line: the search with Profile.from_matrix(matrix, query) (sw_db_search_profile, the
+PROFILE instantiations of sw_matrix.hip) against the matrix search of the same query, alternated three times, --steps
+searches each after one warm-up: both times, their ratio, W and the resident waves per CU of each, and whether the scores
+are equal (they must be).
+
     python tools/bench_db.py [--records R] [--qlen Q] [--lo L] [--hi H] [--steps K] [--alphabet dna|protein]
                              [--opt k=v ...] [--matrix random|FILE --gaps G_INIT,G_EXT] [--alignments K] [--plant P]
-                             [--mode local|global|semiglobal]
+                             [--mode local|global|semiglobal] [--profile]
 """
 import argparse
 import json
@@ -50,7 +55,11 @@ def main():
     ap.add_argument("--plant", type=int, default=0, help="records replaced by mutated copies of the query")
     ap.add_argument("--mode", default="local", choices=("local", "global", "semiglobal"),
                     help="alignment mode of a --matrix search")
+    ap.add_argument("--profile", action="store_true",
+                    help="also search with Profile.from_matrix(matrix, query), alternated with the matrix search (--matrix)")
     a = ap.parse_args()
+    if a.profile and a.matrix is None:
+        ap.error("--profile needs --matrix")
     if a.mode != "local" and a.matrix is None:
         ap.error("--mode needs --matrix")
     if (a.matrix is None) != (a.gaps is None):
@@ -111,6 +120,36 @@ def main():
                       "unit": "GCUPS", "ms_per_search": round(dt * 1e3, 3), "records": a.records,
                       "residues": int(lens.sum()), "qlen": a.qlen, "len_range": [a.lo, a.hi],
                       "max_score": int(sc.max())}))
+    if a.profile:
+        pf = sw.Profile.from_matrix(mx, q)
+        t_mx, t_pf, k_mx, k_pf, st_mx, st_pf, equal = [], [], [], [], None, None, True
+        for _ in range(3):
+            for which in ("matrix", "profile"):
+                run = (lambda: db.search(q, **kw)) if which == "matrix" else (lambda: db.search_profile(pf, gi, ge, mode=a.mode))
+                got = run()   # warm
+                equal = equal and got.tolist() == sc.tolist()
+                kms = []
+                t0 = time.perf_counter()
+                for _ in range(a.steps):
+                    run()
+                    kms.append(sw.last_stats()["kernel_ms"])
+                dt = (time.perf_counter() - t0) / a.steps
+                (t_mx if which == "matrix" else t_pf).append(round(dt * 1e3, 3))
+                (k_mx if which == "matrix" else k_pf).append(round(float(np.median(kms)), 3))
+                if which == "matrix":
+                    st_mx = sw.last_stats()
+                else:
+                    st_pf = sw.last_stats()
+        print(json.dumps({**extra, "metric": "db profile search against matrix search (host API, alternated)", "alphabet": a.alphabet,
+                          "records": a.records, "qlen": a.qlen, "len_range": [a.lo, a.hi], "steps": a.steps,
+                          "matrix_ms_per_search": t_mx, "profile_ms_per_search": t_pf,
+                          "matrix_kernel_ms": k_mx, "profile_kernel_ms": k_pf,
+                          "ratio_profile_over_matrix": round(float(np.median(t_pf)) / float(np.median(t_mx)), 3),
+                          "kernel_ratio_profile_over_matrix": round(float(np.median(k_pf)) / float(np.median(k_mx)), 3),
+                          "matrix_launch": {"mode": st_mx["mode"], "W": st_mx["W"], "waves_per_cu": st_mx["waves_per_cu"], "blocks": st_mx["blocks"]},
+                          "profile_launch": {"mode": st_pf["mode"], "W": st_pf["W"], "waves_per_cu": st_pf["waves_per_cu"], "blocks": st_pf["blocks"]},
+                          "profile_GCUPS": round(cells / (float(np.median(t_pf)) / 1e3) / 1e9, 2), "scores_equal": equal}))
+        pf.close()
     if a.alignments:
         K = a.alignments
         top = db.top(q, k=K, **kw, alignments=True)   # warm: the trace buffers are allocated here
