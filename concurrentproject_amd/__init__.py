@@ -27,6 +27,8 @@ __all__ = [
     "SW_MATRIX_FOLD_CASE", "Alignment", "align_matrix", "align_matrix_batch", "last_align_ms",
     "align_matrix_long", "align_long_plan", "last_align_long_ms", "coop_plan", "align_long_coop_plan",
     "Profile", "score_profile", "score_profile_batch", "align_profile", "align_profile_batch",
+    "STANDARD_CODE", "FRAMES", "translate", "translated_range", "TranslatedAlignment", "score_matrix_translated",
+    "score_matrix_translated_batch", "align_matrix_translated", "align_matrix_translated_batch",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -319,6 +321,28 @@ def lib() -> ctypes.CDLL:
         L.sw_db_align_profile.argtypes = [vp, vp, ctypes.POINTER(i), i, i, i, i, ctypes.POINTER(_Alignment),
                                           ctypes.POINTER(ctypes.c_uint), ll, ctypes.POINTER(ll)]
         L.sw_db_align_profile.restype = i
+    if hasattr(L, "sw_translate"):   # translated search (include/algoGPU.h sw_*_translated*)
+        ip = ctypes.POINTER(i)
+        L.sw_standard_code.argtypes = [u8p]
+        L.sw_standard_code.restype = None
+        L.sw_translate.argtypes = [u8p, i, i, u8p, u8p, i]
+        L.sw_translate.restype = i
+        L.sw_translated_range.argtypes = [i, i, i, i, ip, ip]
+        L.sw_translated_range.restype = i
+        L.sw_translated_tables.argtypes = [vp, u8p, u8p, u8p]
+        L.sw_translated_tables.restype = i
+        L.sw_score_matrix_translated_batch.argtypes = [vp, ctypes.POINTER(u8p), ip, ctypes.POINTER(u8p), ip, i, i, i, i, u8p, ip]
+        L.sw_score_matrix_translated_batch.restype = i
+        for name in ("sw_align_matrix_translated_batch", "sw_align_matrix_translated_cpu"):
+            f = getattr(L, name)
+            f.argtypes = [vp, ctypes.POINTER(u8p), ip, ctypes.POINTER(u8p), ip, ip, i, i, i, i, u8p,
+                          ctypes.POINTER(_Alignment), ctypes.POINTER(ctypes.c_uint), ll, ctypes.POINTER(ll)]
+            f.restype = i
+        L.sw_db_search_matrix_translated.argtypes = [vp, vp, u8p, i, i, i, i, u8p, ip]
+        L.sw_db_search_matrix_translated.restype = i
+        L.sw_db_align_matrix_translated.argtypes = [vp, vp, u8p, i, ip, ip, i, i, i, i, u8p, ctypes.POINTER(_Alignment),
+                                                    ctypes.POINTER(ctypes.c_uint), ll, ctypes.POINTER(ll)]
+        L.sw_db_align_matrix_translated.restype = i
     _lib = L
     return L
 
@@ -1047,6 +1071,132 @@ def align_profile_batch(profile: Profile, seqs: Iterable, gap_init: int, gap_ext
 def align_profile(profile: Profile, seq, gap_init: int, gap_ext: int, cpu: bool = False, mode: str = "local") -> Alignment:
     """One sequence (see :func:`align_profile_batch`)."""
     return align_profile_batch(profile, [seq], gap_init, gap_ext, cpu=cpu, mode=mode)[0]
+
+
+# ---- translated search: protein queries against DNA in six reading frames (include/algoGPU.h sw_*_translated*) ----
+
+FRAMES = (1, 2, 3, -1, -2, -3)
+STANDARD_CODE = b"FFLLSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG"
+
+
+def _code(code):
+    """``code`` as the library takes it: None (the standard code), or 64 bytes in NCBI's TCAG order."""
+    if code is None:
+        return None, None
+    c = _u8(code)
+    if len(c) != 64:
+        raise ValueError("a genetic code is 64 bytes, one amino acid a codon in TCAG order (got %d)" % len(c))
+    return c, _ptr(c)
+
+
+def _frame(frame) -> int:
+    if isinstance(frame, bool) or not isinstance(frame, (int, np.integer)) or int(frame) not in FRAMES:
+        raise ValueError("frame %r is not one of +1, +2, +3, -1, -2, -3" % (frame,))
+    return int(frame)
+
+
+def translate(dna, frame: int, code=None) -> bytes:
+    """Reading frame ``frame`` (+1, +2, +3, -1, -2, -3) of ``dna`` as protein under ``code`` (64 bytes in TCAG order;
+    None: the standard code), by the rules the translated kernels follow (sw_translate): T/U, C, A, G in either
+    case, any codon with another byte is ``X`` (degenerate codons are not resolved), stops are ``*``.  A minus frame
+    reads the reverse complement; translating a DNA *query* into its six frames and searching a protein database
+    with each is the other direction (blastx)."""
+    d = _u8(dna)
+    keep, cp = _code(code)
+    out = np.zeros(len(d) // 3 + 1, dtype=np.uint8)
+    m = _check(lib().sw_translate(_ptr(d), len(d), _frame(frame), cp, _ptr(out), len(out)))
+    return out[:m].tobytes()
+
+
+def translated_range(length: int, frame: int, beg2: int, end2: int) -> tuple:
+    """The half-open DNA range, forward strand, that residues [beg2, end2) of ``frame`` of a DNA of ``length`` bases
+    cover (sw_translated_range)."""
+    b, e = ctypes.c_int(), ctypes.c_int()
+    _check(lib().sw_translated_range(int(length), _frame(frame), int(beg2), int(end2), ctypes.byref(b), ctypes.byref(e)))
+    return b.value, e.value
+
+
+@dataclass(frozen=True)
+class TranslatedAlignment(Alignment):
+    """An :class:`Alignment` of a protein (seq1) with one reading frame of a DNA (seq2): ``beg2`` / ``end2`` are
+    residues of ``frame``, and [``dna_beg``, ``dna_end``) is the range of bases they cover on the forward strand.
+    ``columns(query, translate(dna, frame))`` gives the aligned rows."""
+    frame: int = 1
+    dna_beg: int = 0
+    dna_end: int = 0
+
+
+def score_matrix_translated_batch(pairs: Iterable[Sequence], matrix: Matrix, gap_init: int, gap_ext: int, mode: str = "local",
+                                  code=None) -> np.ndarray:
+    """int32 scores, shape (npairs, 6): the protein of every (protein, dna) pair against the six reading frames of
+    its DNA, frames +1, +2, +3, -1, -2, -3 in this order, in one launch (sw_score_matrix_translated_batch).  The
+    kernel translates as it fetches; entry [k, f] equals ``score_matrix(protein, translate(dna, FRAMES[f], code),
+    ...)``.  The matrix must score every byte the code can emit, ``*`` and ``X`` among them.  No ``band=``,
+    ``coop=``, long path or profile against a translated frame."""
+    am = _mode(mode)
+    keep, cp = _code(code)
+    arrs = [(_u8(a), _u8(b)) for a, b in pairs]
+    n = len(arrs)
+    out = np.zeros((n, 6), dtype=np.int32)
+    if n == 0:
+        return out
+    u8p = ctypes.POINTER(ctypes.c_ubyte)
+    A = (u8p * n)(*[_ptr(x) for x, _ in arrs])
+    B = (u8p * n)(*[_ptr(y) for _, y in arrs])
+    AL = (ctypes.c_int * n)(*[len(x) for x, _ in arrs])
+    BL = (ctypes.c_int * n)(*[len(y) for _, y in arrs])
+    _check(lib().sw_score_matrix_translated_batch(matrix._handle(), A, AL, B, BL, n, int(gap_init), int(gap_ext), am, cp,
+                                                  out.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+    return out
+
+
+def score_matrix_translated(protein, dna, matrix: Matrix, gap_init: int, gap_ext: int, mode: str = "local",
+                            code=None) -> np.ndarray:
+    """One pair (see :func:`score_matrix_translated_batch`): the six scores."""
+    return score_matrix_translated_batch([(protein, dna)], matrix, gap_init, gap_ext, mode=mode, code=code)[0]
+
+
+def _translated(als, frames, dlens) -> list:
+    """TranslatedAlignment of every Alignment with its frame and the DNA range of [beg2, end2)."""
+    res = []
+    for x, f, L in zip(als, frames, dlens):
+        b, e = translated_range(L, f, x.beg2, x.end2)
+        res.append(TranslatedAlignment(x.score, x.beg1, x.end1, x.beg2, x.end2, x.ops, f, b, e))
+    return res
+
+
+def align_matrix_translated_batch(pairs: Iterable[Sequence], frames, matrix: Matrix, gap_init: int, gap_ext: int,
+                                  cpu: bool = False, mode: str = "local", code=None) -> list:
+    """A :class:`TranslatedAlignment` per (protein, dna) pair in the frame ``frames[k]`` names, on the GPU
+    (sw_align_matrix_translated_batch: the traced translated kernel and the matrix path's walk) or, with
+    ``cpu=True``, from the host (sw_align_matrix_translated_cpu: translate, then the host aligner), which gives the
+    same result bit for bit.  A pair whose trace does not fit option ``trace_mb`` is refused: there is no long
+    path, band or cooperative path against a translated frame."""
+    am = _mode(mode)
+    keep, cp = _code(code)
+    arrs = [(_u8(a), _u8(b)) for a, b in pairs]
+    fr = [_frame(f) for f in frames]
+    n = len(arrs)
+    if len(fr) != n:
+        raise ValueError("%d frames for %d pairs" % (len(fr), n))
+    if n == 0:
+        return []
+    u8p = ctypes.POINTER(ctypes.c_ubyte)
+    A = (u8p * n)(*[_ptr(x) for x, _ in arrs])
+    B = (u8p * n)(*[_ptr(y) for _, y in arrs])
+    AL = (ctypes.c_int * n)(*[len(x) for x, _ in arrs])
+    BL = (ctypes.c_int * n)(*[len(y) for _, y in arrs])
+    FR = (ctypes.c_int * n)(*fr)
+    f = lib().sw_align_matrix_translated_cpu if cpu else lib().sw_align_matrix_translated_batch
+    als = _align_call(lambda out, cig, cap, used: f(matrix._handle(), A, AL, B, BL, FR, n, int(gap_init), int(gap_ext), am, cp,
+                                                    out, cig, cap, used), n, 16 * n)
+    return _translated(als, fr, [len(y) for _, y in arrs])
+
+
+def align_matrix_translated(protein, dna, frame: int, matrix: Matrix, gap_init: int, gap_ext: int, cpu: bool = False,
+                            mode: str = "local", code=None) -> TranslatedAlignment:
+    """One pair (see :func:`align_matrix_translated_batch`)."""
+    return align_matrix_translated_batch([(protein, dna)], [frame], matrix, gap_init, gap_ext, cpu=cpu, mode=mode, code=code)[0]
 
 
 def last_align_ms() -> tuple:

@@ -22,7 +22,14 @@ them on many waves (Database.align(long=True, coop=True)); the lines are the sam
 --mode global|semiglobal (with --matrix; default local): the query and the record end to end, or
 the whole query inside the record with the record's flanks free.  Scores may be negative, an
 alignment may begin or end with a gap, and the queries are searched one after another
-(Database.search(mode=...)).  Not with --long."""
+(Database.search(mode=...)).  Not with --long.
+
+--translate (with --matrix and --gaps): the database is DNA and the queries are proteins; every query is scored
+against the six reading frames (+1, +2, +3, -1, -2, -3) of every record, translated under the standard genetic
+code by the kernel (Database.search_translated), one query after another.  A hit is a (record, frame): its line is
+``query_index  query_header  rank  score  db_index  db_header  frame``, and with --alignments it gains
+``q_beg  q_end  dna_beg  dna_end  cigar``, the DNA range on the forward strand.  Ties rank by record, then by frame
+in the order above.  Not with --long or --coop (no long path against a translated frame)."""
 import argparse
 import sys
 import time
@@ -31,6 +38,26 @@ import numpy as np
 
 from . import Matrix, Params, set_params
 from .db import Database
+
+
+def translated(a, db, qs, matrix, gaps, lens) -> int:
+    """--translate: every query through Database.top_translated, one after another."""
+    t0 = time.perf_counter()
+    out = sys.stdout
+    for q in range(len(qs)):
+        qh, query = qs.record(q)
+        hits = db.top_translated(query, a.top, matrix, gaps[0], gaps[1], alignments=a.alignments, mode=a.mode)
+        for r, h in enumerate(hits):
+            line = "%d\t%s\t%d\t%d\t%d\t%s\t%+d" % (q, qh, r + 1, h[0], h[1], h[3], h[2])
+            if a.alignments:
+                x = h[4]
+                line += "\t%d\t%d\t%d\t%d\t%s" % (x.beg1, x.end1, x.dna_beg, x.dna_end, x.cigar or "*")
+            out.write(line + "\n")
+    dt = time.perf_counter() - t0
+    cells = int(qs.lengths().sum()) * int(sum(2 * ((L - o) // 3 if L >= o + 3 else 0) for L in lens for o in range(3)))
+    print("%d queries x %d records x 6 frames: %.3e cells in %.3f s = %.2f GCUPS"
+          % (len(qs), len(db), cells, dt, cells / max(dt, 1e-12) / 1e9), file=sys.stderr)
+    return 0
 
 
 def main(argv=None) -> int:
@@ -49,7 +76,13 @@ def main(argv=None) -> int:
     ap.add_argument("--mode", choices=("local", "global", "semiglobal"), default="local",
                     help="alignment mode of a --matrix search: global = query and record end to end, semiglobal = the "
                          "whole query inside the record")
+    ap.add_argument("--translate", action="store_true",
+                    help="the database is DNA: protein queries against its six reading frames (needs --matrix and --gaps)")
     a = ap.parse_args(argv)
+    if a.translate and (a.matrix is None or a.gaps is None):
+        ap.error("--translate requires --matrix and --gaps")
+    if a.translate and (a.long or a.coop):
+        ap.error("--translate is not with --long or --coop: there is no long path against a translated frame")
     if a.long and not a.alignments:
         ap.error("--long goes with --alignments")
     if a.coop and not a.long:
@@ -72,6 +105,8 @@ def main(argv=None) -> int:
         set_params(prm)
     with Database.open(a.db) as db, Database.open(a.query) as qs:
         lens = db.lengths()
+        if a.translate:
+            return translated(a, db, qs, matrix, gaps, lens)
         t0 = time.perf_counter()
         if a.mode != "local":   # one query after another: search_db is local only
             scores = np.zeros((len(qs), len(db)), dtype=np.int32)

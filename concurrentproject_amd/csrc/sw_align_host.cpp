@@ -179,6 +179,63 @@ int profile_align_check(const char* fn, const sw_profile* pf, const unsigned cha
     return profile_check(fn, pf, seqs, lens, nseq, gap_init, gap_ext, mode);
 }
 
+// ---- translated search: the checks of the sw_*_matrix_translated_* entry points (sw_matrix_host.h) ----
+
+bool translated_range_ok(const char* fn, const sw_matrix* mx, int alen, int dlen, int gap_init, int gap_ext, int amode,
+                         const char* what, int idx) {
+    const int m = frame_residues(dlen, 0);   // frame +1 is the longest, and both bounds grow with m
+    char w[96];
+    std::snprintf(w, sizeof w, "%s: %s", fn, what);
+    if (amode != SW_MODE_LOCAL && !mode_range_ok(alen, m, gap_init, gap_ext, w, idx)) return false;
+    return alen == 0 || m == 0 || align_range_ok(mx, alen, m, w, idx);
+}
+
+int translated_check(const char* fn, const sw_matrix* mx, const unsigned char* const* a, const int* alen,
+                     const unsigned char* const* dna, const int* dlen, const int* frames, int npairs, int gap_init,
+                     int gap_ext, int mode, const unsigned char* code64, Translated* xl) {
+    char m[240];
+    if (!mx || npairs < 0 || (npairs > 0 && (!a || !alen || !dna || !dlen))) {
+        std::snprintf(m, sizeof m, "%s: invalid arguments (a null pointer)", fn);
+        report_error(m);
+        return -1;
+    }
+    if (!mode_ok(fn, mode)) return -1;
+    if (gap_init < 0 || gap_ext < 0 || gap_init > (1 << 20) || gap_ext > (1 << 20)) {
+        std::snprintf(m, sizeof m, "%s: unsupported gap penalties (%d, %d): need 0 <= G_INIT, G_EXT <= 2^20", fn, gap_init,
+                      gap_ext);
+        report_error(m);
+        return -1;
+    }
+    if (translated_tables(fn, mx, code64, xl)) return -1;
+    for (int k = 0; k < npairs; ++k) {
+        if (frames && frame_index(frames[k]) < 0) {
+            std::snprintf(m, sizeof m, "%s: pair %d: frame %d is not one of +1, +2, +3, -1, -2, -3", fn, k, frames[k]);
+            report_error(m);
+            return -1;
+        }
+        if (alen[k] < 0 || dlen[k] < 0 || alen[k] > ALIGN_MAX_SEQ || dlen[k] > ALIGN_MAX_SEQ) {
+            std::snprintf(m, sizeof m, "%s: pair %d: a length of %d residues / %d bases is outside [0, 2^27 - 1]", fn, k, alen[k],
+                          dlen[k]);
+            report_error(m);
+            return -1;
+        }
+        if ((alen[k] > 0 && !a[k]) || (dlen[k] > 0 && !dna[k])) {
+            std::snprintf(m, sizeof m, "%s: pair %d: a null sequence pointer", fn, k);
+            report_error(m);
+            return -1;
+        }
+        if (!translated_range_ok(fn, mx, alen[k], dlen[k], gap_init, gap_ext, mode, "pair", k)) return -1;
+        const long long bad = matrix_first_bad(mx, a[k], alen[k]);
+        if (bad >= 0) {
+            std::snprintf(m, sizeof m, "%s: pair %d: seq1 position %lld: byte 0x%02x is outside the matrix alphabet", fn, k, bad,
+                          a[k][bad]);
+            report_error(m);
+            return -1;
+        }
+    }
+    return 0;
+}
+
 // ---- long pairs: the plan of a checkpointed traceback (sw_matrix_host.h) ----
 
 long long align_strip_steps(long long m) { return (m + ALIGN_STRIP - 1 + 63) / 64 * 64; }
@@ -779,6 +836,33 @@ int sw_align_profile_cpu(const sw_profile* pf, const unsigned char* const* seqs,
         }
     }
     return sink.finish(cigar, cigar_cap, cigar_used);
+}
+
+int sw_align_matrix_translated_cpu(const sw_matrix* mx, const unsigned char* const* a, const int* alen,
+                                   const unsigned char* const* dna, const int* dlen, const int* frames, int npairs,
+                                   int gap_init, int gap_ext, int mode, const unsigned char* code64, sw_alignment* out,
+                                   unsigned* cigar, long long cigar_cap, long long* cigar_used) {
+    const char* fn = "sw_align_matrix_translated_cpu";
+    if (cigar_cap < 0 || !cigar_used || (cigar_cap > 0 && !cigar) || (npairs > 0 && (!out || !frames))) {
+        report_error("sw_align_matrix_translated_cpu: invalid arguments (a null pointer)");
+        return -1;
+    }
+    Translated xl;
+    if (translated_check(fn, mx, a, alen, dna, dlen, frames, npairs, gap_init, gap_ext, mode, code64, &xl)) return -1;
+    // sw_translate, then the aligner of the matrix path over the frames' residues
+    std::vector<std::vector<unsigned char>> prot((size_t)npairs);
+    std::vector<const unsigned char*> bp((size_t)npairs);
+    std::vector<int> bl((size_t)npairs);
+    for (int k = 0; k < npairs; ++k) {
+        std::vector<unsigned char>& p = prot[(size_t)k];
+        p.resize((size_t)dlen[k] / 3 + 1);
+        const int m = sw_translate(dna[k], dlen[k], frames[k], code64, p.data(), (int)p.size());
+        if (m < 0) return -1;
+        bp[(size_t)k] = p.data();
+        bl[(size_t)k] = m;
+    }
+    return sw_align_matrix_cpu_mode(mx, a, alen, bp.data(), bl.data(), npairs, gap_init, gap_ext, mode, out, cigar, cigar_cap,
+                                    cigar_used);
 }
 
 int sw_band_plan(int n, int m, int band, sw_band_plan_t* out) {

@@ -357,12 +357,121 @@ int align_profile(sw_db* db, const sw_profile* pf, const int* record_idx, int ni
                                 amode);
 }
 
+// ---- translated searches (include/algoGPU.h sw_db_*_matrix_translated): the records are DNA, the query a protein ----
+
+// the query against the matrix alphabet and, for every record it will meet, the range refusals; the records are
+// not checked (any byte is a DNA byte) and matrix_ok is not touched
+int check_translated(const char* fn, const sw_db* db, const sw_matrix* mx, const unsigned char* query, int qlen, const int* record_idx,
+                     int nidx, int gap_init, int gap_ext, int amode) {
+    const long long bad = matrix_first_bad(mx, query, qlen);
+    if (bad >= 0) {
+        char m[200];
+        std::snprintf(m, sizeof m, "%s: query position %lld: byte 0x%02x is outside the matrix alphabet", fn, bad, query[bad]);
+        report_error(m);
+        return -1;
+    }
+    const int n = record_idx ? nidx : (int)db->len.size();
+    for (int k = 0; k < n; ++k) {
+        const int r = record_idx ? record_idx[k] : k;
+        if (db->len[(size_t)r] > (1 << 27) - 1 || qlen > (1 << 27) - 1) {
+            char m[200];
+            std::snprintf(m, sizeof m, "%s: record %d: a length of %d residues / %d bases is outside [0, 2^27 - 1]", fn, r, qlen,
+                          db->len[(size_t)r]);
+            report_error(m);
+            return -1;
+        }
+        if (!translated_range_ok(fn, mx, qlen, db->len[(size_t)r], gap_init, gap_ext, amode, "record", r)) return -1;
+    }
+    return 0;
+}
+
+int search_translated(sw_db* db, const sw_matrix* mx, const Translated& xl, const unsigned char* query, int qlen, int gap_init,
+                      int gap_ext, int amode, int* scores_out) {
+    const char* fn = "sw_db_search_matrix_translated";
+    const int nrec = (int)db->len.size();
+    if (nrec == 0) return 0;
+    if (check_translated(fn, db, mx, query, qlen, nullptr, 0, gap_init, gap_ext, amode)) return -1;
+    sw_db::Dev* v = nullptr;
+    if (device_arena(db, qlen, &v)) return -1;
+    const int64_t qoff = (int64_t)db->res.size();
+    if (qlen > 0) DBCHK(hipMemcpy(v->arena + qoff, query, (size_t)qlen, hipMemcpyHostToDevice));
+    std::vector<int64_t> a_off((size_t)nrec, qoff), d_off((size_t)nrec);
+    std::vector<int> alen((size_t)nrec, qlen);
+    for (int r = 0; r < nrec; ++r) d_off[(size_t)r] = db->off[(size_t)r];
+    return translated_score_device(mx, xl, v->arena, a_off.data(), alen.data(), d_off.data(), db->len.data(), nrec, gap_init,
+                                   gap_ext, amode, scores_out);
+}
+
+int align_translated(sw_db* db, const sw_matrix* mx, const Translated& xl, const unsigned char* query, int qlen,
+                     const int* record_idx, const int* frames, int nidx, int gap_init, int gap_ext, int amode, AlignSink& sink) {
+    const char* fn = "sw_db_align_matrix_translated";
+    const int nrec = (int)db->len.size();
+    char m[200];
+    std::vector<int> fidx((size_t)nidx);
+    for (int k = 0; k < nidx; ++k) {
+        if (record_idx[k] < 0 || record_idx[k] >= nrec) {
+            std::snprintf(m, sizeof m, "%s: record index %d (entry %d) is outside [0, %d)", fn, record_idx[k], k, nrec);
+            report_error(m);
+            return -1;
+        }
+        if ((fidx[(size_t)k] = frame_index(frames[k])) < 0) {
+            std::snprintf(m, sizeof m, "%s: entry %d: frame %d is not one of +1, +2, +3, -1, -2, -3", fn, k, frames[k]);
+            report_error(m);
+            return -1;
+        }
+    }
+    if (nidx == 0) return 0;
+    if (check_translated(fn, db, mx, query, qlen, record_idx, nidx, gap_init, gap_ext, amode)) return -1;
+    sw_db::Dev* v = nullptr;
+    if (device_arena(db, qlen, &v)) return -1;
+    const int64_t qoff = (int64_t)db->res.size();
+    if (qlen > 0) DBCHK(hipMemcpy(v->arena + qoff, query, (size_t)qlen, hipMemcpyHostToDevice));
+    std::vector<int64_t> a_off((size_t)nidx, qoff), d_off((size_t)nidx);
+    std::vector<int> alen((size_t)nidx, qlen), dlen((size_t)nidx);
+    for (int k = 0; k < nidx; ++k) {
+        d_off[(size_t)k] = db->off[(size_t)record_idx[k]];
+        dlen[(size_t)k] = db->len[(size_t)record_idx[k]];
+    }
+    return translated_align_device(mx, xl, v->arena, a_off.data(), alen.data(), d_off.data(), dlen.data(), fidx.data(), record_idx,
+                                   nidx, gap_init, gap_ext, "sw_db_align_matrix_translated: record", sink, amode);
+}
+
 }  // namespace
 }  // namespace swmi
 
 using namespace swmi;
 
 extern "C" {
+
+int sw_db_search_matrix_translated(sw_db* db, const sw_matrix* mx, const unsigned char* query, int qlen, int gap_init,
+                                   int gap_ext, int mode, const unsigned char* code64, int* scores_out) {
+    const char* fn = "sw_db_search_matrix_translated";
+    if (!db || !mx || qlen < 0 || (qlen > 0 && !query) || (!db->len.empty() && !scores_out)) {
+        report_error("sw_db_search_matrix_translated: invalid arguments (a null pointer or a negative length)");
+        return -1;
+    }
+    Translated xl;
+    if (!mode_ok(fn, mode) || translated_tables(fn, mx, code64, &xl)) return -1;
+    std::lock_guard<std::mutex> g(db->mu);
+    return search_translated(db, mx, xl, query, qlen, gap_init, gap_ext, mode, scores_out);
+}
+
+int sw_db_align_matrix_translated(sw_db* db, const sw_matrix* mx, const unsigned char* query, int qlen, const int* record_idx,
+                                  const int* frames, int nidx, int gap_init, int gap_ext, int mode, const unsigned char* code64,
+                                  sw_alignment* out, unsigned* cigar, long long cigar_cap, long long* cigar_used) {
+    const char* fn = "sw_db_align_matrix_translated";
+    if (!db || !mx || qlen < 0 || (qlen > 0 && !query) || nidx < 0 || cigar_cap < 0 || !cigar_used || (cigar_cap > 0 && !cigar) ||
+        (nidx > 0 && (!record_idx || !frames || !out))) {
+        report_error("sw_db_align_matrix_translated: invalid arguments (a null pointer or a negative length)");
+        return -1;
+    }
+    Translated xl;
+    if (!mode_ok(fn, mode) || translated_tables(fn, mx, code64, &xl)) return -1;
+    std::lock_guard<std::mutex> g(db->mu);
+    AlignSink sink{out, {}};
+    if (align_translated(db, mx, xl, query, qlen, record_idx, frames, nidx, gap_init, gap_ext, mode, sink)) return -1;
+    return sink.finish(cigar, cigar_cap, cigar_used);
+}
 
 int sw_db_search_profile(sw_db* db, const sw_profile* pf, int gap_init, int gap_ext, int mode, int* scores_out) {
     if (!db || !pf || (!db->len.empty() && !scores_out)) {

@@ -67,6 +67,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <map>
@@ -91,6 +92,8 @@ constexpr int MODE_MATRIX_BAND = 9;                  // the band launches, score
 constexpr int MODE_MATRIX_BAND_TRACE = 10;           // and traced (sw_align_matrix_batch_band)
 constexpr int MODE_MATRIX_PROFILE = 13;              // the profile launches, score-only (sw_score_profile_batch)
 constexpr int MODE_MATRIX_PROFILE_TRACE = 14;        // and traced (sw_align_profile_batch)
+constexpr int MODE_MATRIX_XLATE = 15;                // the translated launches, score-only (sw_score_matrix_translated_batch)
+constexpr int MODE_MATRIX_XLATE_TRACE = 16;          // and traced (sw_align_matrix_translated_batch)
 constexpr int TRACE_W = 8;                           // the traced variant's columns per lane: a step is a dword a lane
 static_assert(SW_PROFILE_STRIDE == MAT_STRIDE && SW_PROFILE_SENT == MAT_SENT, "the profile image is rows of the table");
 
@@ -149,6 +152,9 @@ struct MatArgs {
     unsigned char* trace;
     TraceRes* res;            // nscores entries
     // profile launches only (PROFILE below): the device image, pd.n + 1 rows of MAT_STRIDE bytes
+    // translated launches (XLATE below) instead: the two tables of the translation in a small device buffer, the
+    // base-class map, 256 bytes, then the matrix code of every codon's amino acid, 68 bytes, entry 64 that of 'X'
+    // (sw_translated_tables).  MatArgs does not grow for them: no existing kernel sees another argument layout.
     const unsigned char* prof;
 };
 static_assert(sizeof(MatArgs) <= 4096, "kernel arguments");
@@ -414,6 +420,31 @@ __device__ __forceinline__ unsigned mat_fetch_raw(const __amdgpu_buffer_rsrc_t r
     const int row = k0 + lane;
     return __builtin_amdgcn_raw_buffer_load_b8(row_rsrc, row < m ? (unsigned)row : OOR, 0, 0);
 }
+// XLATE: translated search (include/algoGPU.h sw_*_matrix_translated*), a sixth compile-time
+// parameter of the pair loop and the kernel, not of the step: the rows are the residues of one reading frame of a
+// DNA, and only where a chunk's row code comes from changes.  The item's rows are the 3 * m bases the frame covers
+// (row_rsrc holds exactly those, so the resource drops any stray read), pd.swap_or_band says the frame is a minus
+// frame, and seq1 is always across the lanes (table 0).  A lane loads the three bytes of its row's codon, one
+// chunk ahead as the byte of a plain row is: row r of a plus frame at 3r, 3r + 1, 3r + 2; of a minus frame at
+// 3(m - 1 - r) + 2, + 1, + 0, to be complemented.  The three travel as one dword.
+__device__ __forceinline__ unsigned xl_fetch_raw(const __amdgpu_buffer_rsrc_t row_rsrc, int k0, int lane, int m, int minus) {
+    const int row = k0 + lane;
+    const bool live = row < m;
+    const unsigned o0 = minus ? 3u * (unsigned)(m - 1 - row) + 2u : 3u * (unsigned)row;
+    const unsigned o1 = minus ? o0 - 1u : o0 + 1u, o2 = minus ? o0 - 2u : o0 + 2u;
+    const unsigned b0 = __builtin_amdgcn_raw_buffer_load_b8(row_rsrc, live ? o0 : OOR, 0, 0);
+    const unsigned b1 = __builtin_amdgcn_raw_buffer_load_b8(row_rsrc, live ? o1 : OOR, 0, 0);
+    const unsigned b2 = __builtin_amdgcn_raw_buffer_load_b8(row_rsrc, live ? o2 : OOR, 0, 0);
+    return (b0 & 0xFFu) | (b1 & 0xFFu) << 8 | (b2 & 0xFFu) << 16;
+}
+// the row code of a fetched codon: the bytes' classes through the base map in LDS (a minus frame complements a
+// class, x ^ 2; an ambiguous byte stays above 3 either way), then the composed codon table at 16a + 4b + c, or
+// its entry 64 when a base is ambiguous
+__device__ __forceinline__ int xl_row_code(unsigned raw, int minus, const unsigned char* s_base, const unsigned char* s_codon) {
+    const int cx = minus ? 2 : 0;
+    const int c0 = (int)s_base[raw & 0xFFu] ^ cx, c1 = (int)s_base[(raw >> 8) & 0xFFu] ^ cx, c2 = (int)s_base[(raw >> 16) & 0xFFu] ^ cx;
+    return (int)s_codon[(c0 | c1 | c2) > 3 ? 64 : 16 * c0 + 4 * c1 + c2];
+}
 __device__ __forceinline__ u32x2 mat_fetch_edge(const __amdgpu_buffer_rsrc_t scr_rsrc, int k0, int lane, int m) {
     const int row = k0 + lane;
     return __builtin_amdgcn_raw_buffer_load_b64(scr_rsrc, row < m ? (unsigned)row * 8u : OOR, 0, AUX_SC1);
@@ -462,10 +493,14 @@ __device__ __forceinline__ int band_nch(int i0, int SW, int m, int dlo, int dhi)
 // chunk k0 >= k0'; which rows a strip skips changes nothing in that.
 // PROFILE: the columns are the positions of a profile; s_tab is the wave's slab (MStrip above), filled again
 // before every strip.
-template <int W, int MODE, int AM = AM_LOCAL, bool BAND = false, bool PROFILE = false>
+// XLATE: the rows are the residues of a reading frame (xl_fetch_raw above); minus: the frame is a minus frame;
+// s_base and s_codon: the two tables of the translation in LDS.
+template <int W, int MODE, int AM = AM_LOCAL, bool BAND = false, bool PROFILE = false, bool XLATE = false>
 __device__ void matrix_pair(const MatArgs& a, const MatPair& pd, const WalkPair& wp, const int lane, uint2* scr,
                             const signed char* s_tab, const unsigned char* s_code, unsigned char* ckpt = nullptr,
-                            unsigned ckpt_stride = 0, const BandPair bp = BandPair{0, 0}) {
+                            unsigned ckpt_stride = 0, const BandPair bp = BandPair{0, 0}, const int minus = 0,
+                            const unsigned char* s_base = nullptr, const unsigned char* s_codon = nullptr) {
+    static_assert(!XLATE || (!BAND && !PROFILE && MODE != M_LOCATE), "a translated frame has no band, profile or long path");
     constexpr bool TRACE = MODE != M_SCORE;   // the end cell is kept
     constexpr int SW = 64 * W, C = MAT_C;
     const int m = pd.m;
@@ -473,7 +508,7 @@ __device__ void matrix_pair(const MatArgs& a, const MatPair& pd, const WalkPair&
     const bool l63 = lane == 63;
     const int strips = (pd.n + SW - 1) / SW;
     const __amdgpu_buffer_rsrc_t row_rsrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(a.seq + pd.row_off), 0, m, RSRC_FLAGS);
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(a.seq + pd.row_off), 0, XLATE ? 3 * m : m, RSRC_FLAGS);
     // a single strip never touches the scratch: a resource of no bytes drops every access
     const __amdgpu_buffer_rsrc_t scr_rsrc =
         __builtin_amdgcn_make_buffer_rsrc(scr, 0, MODE != M_LOCATE && strips > 1 ? (int)((unsigned)m * 8u) : 0, RSRC_FLAGS);
@@ -555,17 +590,18 @@ __device__ void matrix_pair(const MatArgs& a, const MatPair& pd, const WalkPair&
             out_rsrc = __builtin_amdgcn_make_buffer_rsrc(ckpt + (uint64_t)(has_out ? strip : 0) * ckpt_stride, 0,
                                                          has_out ? (int)((unsigned)m * 8u) : 0, RSRC_FLAGS);
         }
-        unsigned raw_nxt = mat_fetch_raw(row_rsrc, 0, lane, m);
+        unsigned raw_nxt = XLATE ? xl_fetch_raw(row_rsrc, 0, lane, m, minus) : mat_fetch_raw(row_rsrc, 0, lane, m);
         u32x2 g_nxt = has_in ? mat_fetch_edge(in_rsrc, 0, lane, m) : u32x2{0u, 0u};
         for (int c = 0; c < nchunks; ++c) {
             const int k0 = c * C;
             const unsigned raw = raw_nxt;
             const u32x2 g = g_nxt;
             // the next chunk's rows in flight while this chunk computes
-            raw_nxt = mat_fetch_raw(row_rsrc, k0 + C, lane, m);
+            raw_nxt = XLATE ? xl_fetch_raw(row_rsrc, k0 + C, lane, m, minus) : mat_fetch_raw(row_rsrc, k0 + C, lane, m);
             if (has_in) g_nxt = mat_fetch_edge(in_rsrc, k0 + C, lane, m);
             const bool live = k0 + lane < m;
-            S.IOR = live ? (int)s_code[raw & 0xFFu] : a.k;
+            if constexpr (XLATE) S.IOR = live ? xl_row_code(raw, minus, s_base, s_codon) : a.k;
+            else S.IOR = live ? (int)s_code[raw & 0xFFu] : a.k;
             if constexpr (AM == AM_LOCAL) {
                 S.IOH = has_in && live ? (int)g.x : -go;
                 S.IOE = has_in && live ? (int)g.y : -ge;
@@ -670,6 +706,27 @@ __device__ __forceinline__ MatLds profile_stage(const MatArgs& a) {
     return MatLds{reinterpret_cast<const signed char*>(s_slabw + wave * (W * 64 * MAT_STRIDE / 4)),
                   reinterpret_cast<const unsigned char*>(s_codew)};
 }
+// XLATE: the map, the table of seq1 across the lanes (a frame is never swapped onto them) and the two tables of
+// the translation, 256 + 68 bytes more
+struct XlLds {
+    MatLds m;
+    const unsigned char* base;
+    const unsigned char* codon;
+};
+__device__ __forceinline__ XlLds xlate_stage(const MatArgs& a) {
+    __shared__ unsigned s_tabw[MAT_TAB_BYTES / 4];
+    __shared__ unsigned s_codew[64];
+    __shared__ unsigned s_basew[64];
+    __shared__ unsigned s_codonw[17];
+    for (int i = threadIdx.x; i < MAT_TAB_BYTES / 4; i += 256) s_tabw[i] = a.tab[i];
+    if (threadIdx.x < 64) s_codew[threadIdx.x] = a.code[threadIdx.x];
+    const unsigned* xl = reinterpret_cast<const unsigned*>(a.prof);   // 64 + 17 dwords (fill_args)
+    if (threadIdx.x >= 64 && threadIdx.x < 128) s_basew[threadIdx.x - 64] = xl[threadIdx.x - 64];
+    if (threadIdx.x >= 128 && threadIdx.x < 128 + 17) s_codonw[threadIdx.x - 128] = xl[threadIdx.x - 64];
+    __syncthreads();
+    return XlLds{MatLds{reinterpret_cast<const signed char*>(s_tabw), reinterpret_cast<const unsigned char*>(s_codew)},
+                 reinterpret_cast<const unsigned char*>(s_basew), reinterpret_cast<const unsigned char*>(s_codonw)};
+}
 // the wave's next item; false: none is left
 __device__ __forceinline__ bool matrix_claim(const MatArgs& a, const int lane, unsigned& item) {
     item = 0;
@@ -699,10 +756,15 @@ __device__ __forceinline__ void matrix_claimed_pair(const MatArgs& a, const unsi
 
 // BAND: the pair's diagonal range beside it; seq1 is across the lanes (table 0) in local mode too.
 // PROFILE: seq1 is the profile of the launch (MatArgs::prof), pd.n its length for every item.
-template <int W, bool TRACE = false, int AM = AM_LOCAL, bool BAND = false, bool PROFILE = false>
+// XLATE: seq2 is a reading frame of a DNA, translated by the fetch; the item's swap_or_band is 1 for a minus frame.
+template <int W, bool TRACE = false, int AM = AM_LOCAL, bool BAND = false, bool PROFILE = false, bool XLATE = false>
 __global__ void __launch_bounds__(256) sw_matrix_kernel(MatArgs a) {
     MatLds s;
-    if constexpr (PROFILE) s = profile_stage<W>(a);
+    XlLds x{};
+    if constexpr (XLATE) {
+        x = xlate_stage(a);
+        s = x.m;
+    } else if constexpr (PROFILE) s = profile_stage<W>(a);
     else s = matrix_stage(a);
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
@@ -717,7 +779,13 @@ __global__ void __launch_bounds__(256) sw_matrix_kernel(MatArgs a) {
             bp = band_of(pd.n, pd.m, pd.swap_or_band);
             pd.swap_or_band = 0;
         }
-        matrix_pair<W, TRACE ? M_TRACE : M_SCORE, AM, BAND, PROFILE>(a, pd, wp, lane, scr, s.tab, s.code, nullptr, 0, bp);
+        int minus = 0;
+        if constexpr (XLATE) {
+            minus = pd.swap_or_band;
+            pd.swap_or_band = 0;
+        }
+        matrix_pair<W, TRACE ? M_TRACE : M_SCORE, AM, BAND, PROFILE, XLATE>(a, pd, wp, lane, scr, s.tab, s.code, nullptr, 0, bp,
+                                                                            minus, x.base, x.codon);
     }
 }
 
@@ -1399,6 +1467,15 @@ void name_profile_kernels(FillKernel (&row)[5]) {   // as name_fill_kernels; a w
 }
 
 template <int AM>
+void name_xlate_kernels(FillKernel (&row)[5]) {   // as name_fill_kernels: the translated kernels
+    row[0].fn = (const void*)sw_matrix_kernel<1, false, AM, false, false, true>;
+    row[1].fn = (const void*)sw_matrix_kernel<2, false, AM, false, false, true>;
+    row[2].fn = (const void*)sw_matrix_kernel<4, false, AM, false, false, true>;
+    row[3].fn = (const void*)sw_matrix_kernel<8, false, AM, false, false, true>;
+    row[WI_TRACED].fn = (const void*)sw_matrix_kernel<TRACE_W, true, AM, false, false, true>;
+}
+
+template <int AM>
 void name_coop_kernels(FillKernel (&row)[4]) {   // the cooperative score kernels at W_OF
     row[0].fn = (const void*)sw_matrix_coop_kernel<1, AM>;
     row[1].fn = (const void*)sw_matrix_coop_kernel<2, AM>;
@@ -1420,7 +1497,7 @@ enum {
     B_LONG, B_CKPT, B_ITEMS, B_STATE,                    // long pairs: locate items, checkpoints, strip items, walk states
     B_CPAIRS, B_CITEMS, B_EDGE, B_PROGRESS,              // cooperative score: pairs, items, edge columns, progress words
     B_ENDS, B_WINDOWS,                                   // long pairs on many waves: end-cell records, a round's windows
-    B_PROFILE,                                           // profile launches: the profile's device image
+    B_PROFILE,                                           // profile launches: the profile's device image; translated: the tables
     B_COUNT
 };
 struct MatCtx {
@@ -1434,6 +1511,7 @@ struct MatCtx {
     FillKernel coop[3][4];      // [SW_MODE_*][index into W_OF]
     FillKernel locate_coop[3];  // [SW_MODE_*]
     FillKernel pfill[3][5];     // [SW_MODE_*][index into W_OF, or WI_TRACED]: the profile kernels
+    FillKernel xfill[3][5];     // [SW_MODE_*][index into W_OF, or WI_TRACED]: the translated kernels
     MatCtx() {
         name_profile_kernels<AM_LOCAL>(pfill[AM_LOCAL]);
         name_profile_kernels<AM_GLOBAL>(pfill[AM_GLOBAL]);
@@ -1450,6 +1528,9 @@ struct MatCtx {
         name_fill_kernels<AM_LOCAL, true>(fill[1][AM_LOCAL]);
         name_fill_kernels<AM_GLOBAL, true>(fill[1][AM_GLOBAL]);
         name_fill_kernels<AM_SEMI, true>(fill[1][AM_SEMI]);
+        name_xlate_kernels<AM_LOCAL>(xfill[AM_LOCAL]);
+        name_xlate_kernels<AM_GLOBAL>(xfill[AM_GLOBAL]);
+        name_xlate_kernels<AM_SEMI>(xfill[AM_SEMI]);
     }
 };
 thread_local float t_fill_ms = 0.f, t_walk_ms = 0.f;   // sw_last_align_ms
@@ -1522,6 +1603,7 @@ bool gaps_ok(int gap_init, int gap_ext) {
 struct DevSeq {
     int64_t a_off, b_off;
     int alen, blen, idx;
+    int minus = 0;   // translated launches: b is the 3 * blen bases of a reading frame, and this a minus frame
 };
 
 // the byte-to-code map and both orientations of the table, as the kernel stages them in LDS
@@ -1603,7 +1685,8 @@ int fill_blocks(MatCtx* c, FillKernel& k, size_t items, long long scratch_rows, 
 // passes scratch_rows = 0; its kernels never touch the scratch pointer, whatever it holds.
 // pf: a profile launch: mx is its alphabet, and its image goes up into a buffer of its own.
 int fill_args(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, const std::vector<MatPair>& pairs, int nscores,
-              int gap_init, int gap_ext, long long scratch_rows, long long blocks, MatArgs& a, const sw_profile* pf = nullptr) {
+              int gap_init, int gap_ext, long long scratch_rows, long long blocks, MatArgs& a, const sw_profile* pf = nullptr,
+              const Translated* xl = nullptr) {
     if (ensure(c, B_PAIRS, pairs.size() * sizeof(MatPair)) || ensure(c, B_CTRL, sizeof(Ctrl)) ||
         ensure(c, B_SCRATCH, (size_t)scratch_rows * 8 * 4 * (size_t)blocks))
         return -1;
@@ -1624,6 +1707,12 @@ int fill_args(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, cons
         MCHK(hipMemcpyAsync(c->buf[B_PROFILE], pf->image.data(), pf->image.size(), hipMemcpyHostToDevice, c->stream));
         a.prof = (const unsigned char*)c->buf[B_PROFILE];
     }
+    if (xl) {   // base and codon lie back to back in Translated: one copy of 324 bytes
+        static_assert(offsetof(Translated, codon) == offsetof(Translated, base) + 256, "the tables are one block");
+        if (ensure(c, B_PROFILE, 256 + 68)) return -1;
+        MCHK(hipMemcpyAsync(c->buf[B_PROFILE], xl->base, 256 + 68, hipMemcpyHostToDevice, c->stream));
+        a.prof = (const unsigned char*)c->buf[B_PROFILE];
+    }
     return 0;
 }
 // the scratch column of a launch: the rows of its widest pair of more than one strip, in whole chunks
@@ -1640,12 +1729,13 @@ long long scratch_rows_of(const std::vector<MatPair>& pairs, int SW) {
 // pf: the profile launches: seq1 of every pair is the profile (alen = pf->n, a_off not read), always across the
 // lanes, and mx its alphabet.
 int launch(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, std::vector<DevSeq>& act, int gap_init,
-           int gap_ext, int* d_scores, int nscores, bool a_on_lanes, int amode, int band = -1, const sw_profile* pf = nullptr) {
+           int gap_ext, int* d_scores, int nscores, bool a_on_lanes, int amode, int band = -1, const sw_profile* pf = nullptr,
+           const Translated* xl = nullptr) {
     const auto t0 = std::chrono::steady_clock::now();
     const bool banded = band >= 0;
-    if (amode != AM_LOCAL || banded || pf) a_on_lanes = true;
+    if (amode != AM_LOCAL || banded || pf || xl) a_on_lanes = true;
     sw_stats st{};
-    st.mode = pf ? MODE_MATRIX_PROFILE : banded ? MODE_MATRIX_BAND : MODE_MATRIX;
+    st.mode = xl ? MODE_MATRIX_XLATE : pf ? MODE_MATRIX_PROFILE : banded ? MODE_MATRIX_BAND : MODE_MATRIX;
     st.variant = amode;   // free on score-only matrix launches: the alignment mode (SW_MODE_*)
     st.C = MAT_C;
     st.items = nscores;
@@ -1687,6 +1777,7 @@ int launch(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, std::ve
         const DevSeq& p = act[k];
         const bool swap = !a_on_lanes && pair_cost(p.blen, p.alen, W) < pair_cost(p.alen, p.blen, W);
         const MatPair& d = pairs[k] = make_pair(p, p.idx, swap, band);
+        if (xl) pairs[k].swap_or_band = p.minus;
         if (banded) {
             int dlo, dhi;
             band_range(d.n, d.m, band, &dlo, &dhi);
@@ -1695,12 +1786,12 @@ int launch(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, std::ve
             cells += (long long)d.n * d.m;
         }
     }
-    FillKernel& kern = pf ? c->pfill[amode][wi] : c->fill[banded][amode][wi];
+    FillKernel& kern = xl ? c->xfill[amode][wi] : pf ? c->pfill[amode][wi] : c->fill[banded][amode][wi];
     const long long scratch_rows = scratch_rows_of(pairs, 64 * W);
     long long blocks = 0;
     MatArgs a{};
     if (fill_blocks(c, kern, pairs.size(), scratch_rows, &blocks) ||
-        fill_args(c, mx, d_arena, pairs, nscores, gap_init, gap_ext, scratch_rows, blocks, a, pf))
+        fill_args(c, mx, d_arena, pairs, nscores, gap_init, gap_ext, scratch_rows, blocks, a, pf, xl))
         return -1;
     a.scores = d_scores;
 
@@ -1995,9 +2086,10 @@ struct TracedOut {
     int blocks = 0;
 };
 int launch_traced(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, const std::vector<DevSeq>& act,
-                  int gap_init, int gap_ext, TracedOut& o, int amode, int band = -1, const sw_profile* pf = nullptr) {
+                  int gap_init, int gap_ext, TracedOut& o, int amode, int band = -1, const sw_profile* pf = nullptr,
+                  const Translated* xl = nullptr) {
     const bool banded = band >= 0;
-    FillKernel& kern = pf ? c->pfill[amode][WI_TRACED] : c->fill[banded][amode][WI_TRACED];
+    FillKernel& kern = xl ? c->xfill[amode][WI_TRACED] : pf ? c->pfill[amode][WI_TRACED] : c->fill[banded][amode][WI_TRACED];
     const size_t np = act.size();
     const std::vector<int> order = longest_first(act);
     std::vector<MatPair> pairs(np);
@@ -2012,6 +2104,7 @@ int launch_traced(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, 
     for (size_t s = 0; s < np; ++s) {
         WalkPair& w = walk[s];
         pairs[s] = make_pair(act[(size_t)order[s]], order[s], false, band, &w);
+        if (xl) pairs[s].swap_or_band = act[(size_t)order[s]].minus;
         w.trace_off = (uint64_t)trace_total;
         w.ops_off = o.ops_off[(size_t)order[s]];
         trace_total += (long long)w.trace_bytes;
@@ -2020,7 +2113,7 @@ int launch_traced(MatCtx* c, const sw_matrix* mx, const unsigned char* d_arena, 
     long long blocks = 0;
     MatArgs a{};
     if (fill_blocks(c, kern, np, scratch_rows, &blocks) ||
-        fill_args(c, mx, d_arena, pairs, (int)np, gap_init, gap_ext, scratch_rows, blocks, a, pf) ||
+        fill_args(c, mx, d_arena, pairs, (int)np, gap_init, gap_ext, scratch_rows, blocks, a, pf, xl) ||
         ensure(c, B_WALK, np * sizeof(WalkPair)) || ensure(c, B_TRACE, (size_t)trace_total) ||
         ensure(c, B_RES, np * sizeof(TraceRes)) || ensure(c, B_OPS, (size_t)ops_total))
         return -1;
@@ -2434,7 +2527,8 @@ int matrix_align_long_device(const sw_matrix* mx, const unsigned char* d_arena, 
 
 int matrix_align_device(const sw_matrix* mx, const unsigned char* d_arena, const int64_t* a_off, const int* alen,
                         const int64_t* b_off, const int* blen, const int* name_idx, int npairs, int gap_init,
-                        int gap_ext, const char* what, AlignSink& sink, int amode, int band, const sw_profile* pf) {
+                        int gap_ext, const char* what, AlignSink& sink, int amode, int band, const sw_profile* pf,
+                        const Translated* xl) {
     const auto t0 = std::chrono::steady_clock::now();
     if (!gaps_ok(gap_init, gap_ext)) return -1;
     const long long budget = sw_get_option("trace_mb") << 20;
@@ -2459,7 +2553,12 @@ int matrix_align_device(const sw_matrix* mx, const unsigned char* d_arena, const
         const long long need = pair_trace(alen[k], blen[k]);
         if (need > budget) {
             char m[400];
-            if (pf)
+            if (xl)
+                std::snprintf(m, sizeof m,
+                              "%s %d: a %d x %d alignment needs %lld bytes of trace memory, more than option trace_mb = %lld "
+                              "MiB, and there is no long path against a translated frame",
+                              what, name_idx ? name_idx[k] : k, alen[k], blen[k], need, budget >> 20);
+            else if (pf)
                 std::snprintf(m, sizeof m,
                               "%s %d: a %d x %d alignment needs %lld bytes of trace memory, more than option trace_mb = %lld "
                               "MiB, and there is no long path with a profile",
@@ -2489,7 +2588,7 @@ int matrix_align_device(const sw_matrix* mx, const unsigned char* d_arena, const
     t_fill_ms = t_walk_ms = t_locate_ms = 0.f;
     t_rounds = 0;
     sw_stats st{};
-    st.mode = pf ? MODE_MATRIX_PROFILE_TRACE : banded ? MODE_MATRIX_BAND_TRACE : MODE_MATRIX_TRACE;
+    st.mode = xl ? MODE_MATRIX_XLATE_TRACE : pf ? MODE_MATRIX_PROFILE_TRACE : banded ? MODE_MATRIX_BAND_TRACE : MODE_MATRIX_TRACE;
     st.W = TRACE_W;
     st.C = MAT_C;
     st.items = npairs;
@@ -2505,14 +2604,15 @@ int matrix_align_device(const sw_matrix* mx, const unsigned char* d_arena, const
             const long long need = pair_trace(alen[hi], blen[hi]);
             if (!act.empty() && sum + need > budget) break;
             sum += need;
-            act.push_back(DevSeq{a_off[hi], b_off[hi], alen[hi], blen[hi], hi});
+            act.push_back(DevSeq{a_off[hi], b_off[hi], alen[hi], blen[hi], hi, xl && xl->minus ? xl->minus[hi] : 0});
             st.cells += pair_cells(alen[hi], blen[hi]);
         }
         if (!act.empty()) {
-            if (launch_traced(c, mx, d_arena, act, gap_init, gap_ext, o, amode, band, pf)) return -1;
+            if (launch_traced(c, mx, d_arena, act, gap_init, gap_ext, o, amode, band, pf, xl)) return -1;
             st.variant += 1;
             st.blocks = o.blocks;
-            st.waves_per_cu = 4 * (pf ? c->pfill[amode][WI_TRACED] : c->fill[banded][amode][WI_TRACED]).wgs;
+            st.waves_per_cu =
+                4 * (xl ? c->xfill[amode][WI_TRACED] : pf ? c->pfill[amode][WI_TRACED] : c->fill[banded][amode][WI_TRACED]).wgs;
             st.boundary_bytes = std::max(st.boundary_bytes, o.trace_total);
         }
         size_t s = 0;
@@ -2573,6 +2673,55 @@ int profile_align_device(const sw_profile* pf, const unsigned char* d_arena, con
     const std::vector<int> alen((size_t)nseq, pf->n);
     return matrix_align_device(&pf->alpha, d_arena, a_off.data(), alen.data(), b_off, blen, name_idx, nseq, gap_init, gap_ext,
                                what, sink, amode, -1, pf);
+}
+
+// ---- translated search, host side (XLATE above) ----
+
+// Six items a pair, one a non-empty frame, out_idx = 6 * pair + frame index; launch orders them longest first by
+// n * m and sizes the scratch, W and the cells from residues.  The empty frames and queries are answered here.
+int translated_score_device(const sw_matrix* mx, const Translated& xl, const unsigned char* d_arena, const int64_t* a_off,
+                            const int* alen, const int64_t* d_off, const int* dlen, int npairs, int gap_init, int gap_ext,
+                            int amode, int* scores_out) {
+    if (!gaps_ok(gap_init, gap_ext)) return -1;
+    if (npairs > (1 << 30) / 6) {
+        report_error("translated scoring: more than 2^30 / 6 pairs or records in one call");
+        return -1;
+    }
+    MatCtx* c = get_mctx();
+    if (!c) return -1;
+    const int nscores = 6 * npairs;
+    std::vector<DevSeq> act;
+    for (int k = 0; k < npairs; ++k)
+        for (int f = 0; f < 6 && alen[k] > 0; ++f) {
+            const int m = frame_residues(dlen[k], f);
+            if (m > 0) act.push_back(DevSeq{a_off[k], d_off[k] + frame_region(dlen[k], f), alen[k], m, 6 * k + f, f >= 3 ? 1 : 0});
+        }
+    if (ensure(c, B_SCORES, (size_t)std::max(nscores, 1) * sizeof(int))) return -1;
+    if (launch(c, mx, d_arena, act, gap_init, gap_ext, (int*)c->buf[B_SCORES], nscores, true, amode, -1, nullptr, &xl)) return -1;
+    if (nscores) MCHK(hipMemcpy(scores_out, c->buf[B_SCORES], (size_t)nscores * sizeof(int), hipMemcpyDeviceToHost));
+    if (amode != AM_LOCAL)
+        for (int k = 0; k < npairs; ++k)
+            for (int f = 0; f < 6; ++f) {
+                const int m = frame_residues(dlen[k], f);
+                if (alen[k] == 0 || m == 0) scores_out[6 * k + f] = mode_empty_score(alen[k], m, gap_init, gap_ext, amode);
+            }
+    return 0;
+}
+
+int translated_align_device(const sw_matrix* mx, const Translated& xl, const unsigned char* d_arena, const int64_t* a_off,
+                            const int* alen, const int64_t* d_off, const int* dlen, const int* fidx, const int* name_idx,
+                            int npairs, int gap_init, int gap_ext, const char* what, AlignSink& sink, int amode) {
+    std::vector<int64_t> b_off((size_t)npairs);
+    std::vector<int> blen((size_t)npairs), minus((size_t)npairs);
+    for (int k = 0; k < npairs; ++k) {
+        b_off[(size_t)k] = d_off[k] + frame_region(dlen[k], fidx[k]);
+        blen[(size_t)k] = frame_residues(dlen[k], fidx[k]);
+        minus[(size_t)k] = fidx[k] >= 3 ? 1 : 0;
+    }
+    Translated x = xl;
+    x.minus = minus.data();
+    return matrix_align_device(mx, d_arena, a_off, alen, b_off.data(), blen.data(), name_idx, npairs, gap_init, gap_ext, what,
+                               sink, amode, -1, nullptr, &x);
 }
 
 }  // namespace swmi
@@ -2834,6 +2983,72 @@ int sw_align_profile_batch(const sw_profile* pf, const unsigned char* const* seq
     if (profile_upload(c, seqs, lens, nseq, b_off)) return -1;
     if (profile_align_device(pf, (const unsigned char*)c->buf[B_ARENA], b_off.data(), lens, nullptr, nseq, gap_init, gap_ext,
                              "sequence", sink, mode))
+        return -1;
+    return sink.finish(cigar, cigar_cap, cigar_used);
+}
+
+// The sequences of a translated call in one arena: the query then the DNA of every pair, as score_host lays pairs out.
+static int translated_upload(MatCtx* c, const unsigned char* const* a, const int* alen, const unsigned char* const* dna,
+                             const int* dlen, int npairs, std::vector<int64_t>& a_off, std::vector<int64_t>& d_off) {
+    a_off.assign((size_t)npairs, 0);
+    d_off.assign((size_t)npairs, 0);
+    size_t total = 0;
+    for (int k = 0; k < npairs; ++k) {
+        a_off[(size_t)k] = (int64_t)total;
+        total += ((size_t)alen[k] + 15) / 16 * 16;
+        d_off[(size_t)k] = (int64_t)total;
+        total += ((size_t)dlen[k] + 15) / 16 * 16;
+    }
+    std::vector<unsigned char> arena(total);
+    for (int k = 0; k < npairs; ++k) {
+        if (alen[k] > 0) std::memcpy(arena.data() + a_off[(size_t)k], a[k], (size_t)alen[k]);
+        if (dlen[k] > 0) std::memcpy(arena.data() + d_off[(size_t)k], dna[k], (size_t)dlen[k]);
+    }
+    if (ensure(c, B_ARENA, total)) return -1;
+    if (total) MCHK(hipMemcpy(c->buf[B_ARENA], arena.data(), total, hipMemcpyHostToDevice));
+    return 0;
+}
+
+int sw_score_matrix_translated_batch(const sw_matrix* mx, const unsigned char* const* a, const int* alen,
+                                     const unsigned char* const* dna, const int* dlen, int npairs, int gap_init,
+                                     int gap_ext, int mode, const unsigned char* code64, int* scores_out) {
+    const char* fn = "sw_score_matrix_translated_batch";
+    if (npairs > 0 && !scores_out) {
+        report_error("sw_score_matrix_translated_batch: invalid arguments (a null pointer)");
+        return -1;
+    }
+    Translated xl;
+    if (translated_check(fn, mx, a, alen, dna, dlen, nullptr, npairs, gap_init, gap_ext, mode, code64, &xl)) return -1;
+    if (npairs == 0) return 0;
+    MatCtx* c = get_mctx();
+    if (!c) return -1;
+    std::vector<int64_t> a_off, d_off;
+    if (translated_upload(c, a, alen, dna, dlen, npairs, a_off, d_off)) return -1;
+    return translated_score_device(mx, xl, (const unsigned char*)c->buf[B_ARENA], a_off.data(), alen, d_off.data(), dlen, npairs,
+                                   gap_init, gap_ext, mode, scores_out);
+}
+
+int sw_align_matrix_translated_batch(const sw_matrix* mx, const unsigned char* const* a, const int* alen,
+                                     const unsigned char* const* dna, const int* dlen, const int* frames, int npairs,
+                                     int gap_init, int gap_ext, int mode, const unsigned char* code64, sw_alignment* out,
+                                     unsigned* cigar, long long cigar_cap, long long* cigar_used) {
+    const char* fn = "sw_align_matrix_translated_batch";
+    if (cigar_cap < 0 || !cigar_used || (cigar_cap > 0 && !cigar) || (npairs > 0 && (!out || !frames))) {
+        report_error("sw_align_matrix_translated_batch: invalid arguments (a null pointer)");
+        return -1;
+    }
+    Translated xl;
+    if (translated_check(fn, mx, a, alen, dna, dlen, frames, npairs, gap_init, gap_ext, mode, code64, &xl)) return -1;
+    AlignSink sink{out, {}};
+    if (npairs == 0) return sink.finish(cigar, cigar_cap, cigar_used);
+    MatCtx* c = get_mctx();
+    if (!c) return -1;
+    std::vector<int64_t> a_off, d_off;
+    if (translated_upload(c, a, alen, dna, dlen, npairs, a_off, d_off)) return -1;
+    std::vector<int> fidx((size_t)npairs);
+    for (int k = 0; k < npairs; ++k) fidx[(size_t)k] = frame_index(frames[k]);
+    if (translated_align_device(mx, xl, (const unsigned char*)c->buf[B_ARENA], a_off.data(), alen, d_off.data(), dlen, fidx.data(),
+                                nullptr, npairs, gap_init, gap_ext, "sw_align_matrix_translated_batch: pair", sink, mode))
         return -1;
     return sink.finish(cigar, cigar_cap, cigar_used);
 }

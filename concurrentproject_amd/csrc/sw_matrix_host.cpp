@@ -5,6 +5,7 @@
 #include "sw_matrix_host.h"
 #include "../../include/algoGPU.h"
 
+#include <algorithm>
 #include <atomic>
 #include <cstdio>
 #include <cstring>
@@ -217,6 +218,56 @@ long long matrix_first_bad(const sw_matrix* m, const unsigned char* p, long long
     return -1;
 }
 
+// ---- translated search: bases, frames and the composed tables (include/algoGPU.h; sw_matrix_host.h) ----
+
+namespace {
+const char STANDARD_CODE[65] = "FFLLSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG";
+
+int base_class(unsigned char b) {
+    switch (b) {
+    case 'T': case 't': case 'U': case 'u': return 0;
+    case 'C': case 'c': return 1;
+    case 'A': case 'a': return 2;
+    case 'G': case 'g': return 3;
+    default: return XL_AMBIGUOUS;
+    }
+}
+}  // namespace
+
+int frame_index(int frame) { return frame >= 1 && frame <= 3 ? frame - 1 : frame <= -1 && frame >= -3 ? 2 - frame : -1; }
+
+int frame_residues(int len, int fi) {
+    const int o = fi % 3;
+    return len >= o + 3 ? (len - o) / 3 : 0;
+}
+
+int frame_region(int len, int fi) {
+    const int o = fi % 3;
+    return fi < 3 ? o : len - o - 3 * frame_residues(len, fi);
+}
+
+int translated_tables(const char* fn, const sw_matrix* mx, const unsigned char* code64, Translated* out) {
+    const unsigned char* code = code64 ? code64 : reinterpret_cast<const unsigned char*>(STANDARD_CODE);
+    for (int b = 0; b < 256; ++b) out->base[b] = (unsigned char)base_class((unsigned char)b);
+    std::memset(out->codon, 0, sizeof out->codon);
+    for (int c = 0; c <= 64; ++c) {
+        const unsigned char aa = c < 64 ? code[c] : (unsigned char)'X';
+        if (mx->code[aa] == SW_MATRIX_NOCODE) {
+            char m[200];
+            if (c < 64)
+                std::snprintf(m, sizeof m, "%s: the genetic code emits byte 0x%02x ('%c', codon %d), which the matrix does not score",
+                              fn, aa, aa >= 32 && aa < 127 ? aa : '?', c);
+            else
+                std::snprintf(m, sizeof m, "%s: a codon with an ambiguous base translates to byte 0x58 ('X'), which the matrix "
+                              "does not score", fn);
+            report_error(m);
+            return -1;
+        }
+        out->codon[c] = mx->code[aa];
+    }
+    return 0;
+}
+
 }  // namespace swmi
 
 using namespace swmi;
@@ -359,5 +410,76 @@ int sw_profile_score(const sw_profile* p, int pos, unsigned char byte, int* out)
 }
 
 void sw_profile_free(sw_profile* p) { delete p; }
+
+void sw_standard_code(unsigned char out[64]) {
+    if (out) std::memcpy(out, STANDARD_CODE, 64);
+}
+
+int sw_translate(const unsigned char* dna, int len, int frame, const unsigned char* code64, unsigned char* out, int cap) {
+    const int fi = frame_index(frame);
+    char msg[160];
+    if (fi < 0) {
+        std::snprintf(msg, sizeof msg, "sw_translate: frame %d is not one of +1, +2, +3, -1, -2, -3", frame);
+        report_error(msg);
+        return -1;
+    }
+    if (len < 0 || cap < 0 || (len > 0 && !dna)) {
+        report_error("sw_translate: invalid arguments");
+        return -1;
+    }
+    const int m = frame_residues(len, fi), o = fi % 3;
+    if (m > cap || (m > 0 && !out)) {
+        std::snprintf(msg, sizeof msg, "sw_translate: %d residues do not fit the output buffer of %d", m, cap);
+        report_error(msg);
+        return -1;
+    }
+    const unsigned char* code = code64 ? code64 : reinterpret_cast<const unsigned char*>(STANDARD_CODE);
+    for (int r = 0; r < m; ++r) {
+        int c[3];
+        for (int t = 0; t < 3; ++t)
+            c[t] = fi < 3 ? base_class(dna[3 * r + o + t]) : base_class(dna[len - 1 - 3 * r - o - t]) ^ 2;
+        out[r] = ((c[0] | c[1] | c[2]) & XL_AMBIGUOUS) ? (unsigned char)'X' : code[16 * c[0] + 4 * c[1] + c[2]];
+    }
+    return m;
+}
+
+int sw_translated_range(int len, int frame, int beg2, int end2, int* dna_beg, int* dna_end) {
+    const int fi = frame_index(frame);
+    char msg[200];
+    if (fi < 0) {
+        std::snprintf(msg, sizeof msg, "sw_translated_range: frame %d is not one of +1, +2, +3, -1, -2, -3", frame);
+        report_error(msg);
+        return -1;
+    }
+    if (len < 0 || !dna_beg || !dna_end) {
+        report_error("sw_translated_range: invalid arguments");
+        return -1;
+    }
+    const int m = frame_residues(len, fi), o = fi % 3;
+    if (beg2 < 0 || beg2 > end2 || end2 > m) {
+        std::snprintf(msg, sizeof msg, "sw_translated_range: residues [%d, %d) are outside frame %d of %d bases (%d residues)",
+                      beg2, end2, frame, len, m);
+        report_error(msg);
+        return -1;
+    }
+    // (a DNA shorter than the offset has an empty frame, whose empty range is kept inside [0, len])
+    const int lo = fi < 3 ? 3 * beg2 + o : len - o - 3 * end2, hi = fi < 3 ? 3 * end2 + o : len - o - 3 * beg2;
+    *dna_beg = std::min(std::max(lo, 0), len);
+    *dna_end = std::min(std::max(hi, 0), len);
+    return 0;
+}
+
+int sw_translated_tables(const sw_matrix* mx, const unsigned char* code64, unsigned char base_out[256],
+                         unsigned char codon_out[65]) {
+    if (!mx || !base_out || !codon_out) {
+        report_error("sw_translated_tables: invalid arguments");
+        return -1;
+    }
+    Translated t;
+    if (translated_tables("sw_translated_tables", mx, code64, &t)) return -1;
+    std::memcpy(base_out, t.base, 256);
+    std::memcpy(codon_out, t.codon, 65);
+    return 0;
+}
 
 }  // extern "C"

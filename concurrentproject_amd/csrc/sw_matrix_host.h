@@ -106,10 +106,12 @@ void align_mode_empty(AlignSink& sink, int k, int alen, int blen, int gap_init, 
 // `what` k when name_idx is null).
 // amode: SW_MODE_*; global and semi-global pairs are checked with mode_range_ok here.
 // band >= 0: the band launches (below), whose trace is the band's; -1: the whole matrix.
+// xl: the translated launches (further below): seq2 of pair k is the 3 * blen[k] bases at b_off[k], blen[k] residues.
+struct Translated;
 int matrix_align_device(const sw_matrix* m, const unsigned char* d_arena, const int64_t* a_off, const int* alen,
                         const int64_t* b_off, const int* blen, const int* name_idx, int npairs, int gap_init,
                         int gap_ext, const char* what, AlignSink& sink, int amode, int band = -1,
-                        const sw_profile* pf = nullptr);
+                        const sw_profile* pf = nullptr, const Translated* xl = nullptr);
 
 // ---- position-specific scoring: the profile launches (sw_matrix.hip PROFILE) ----
 // As matrix_score_device / matrix_align_device with the profile as seq1 (across the lanes, never swapped, no
@@ -130,6 +132,42 @@ int profile_align_check(const char* fn, const sw_profile* pf, const unsigned cha
 // the refusals of one sequence of length len against pf, before any device work: mode_range_ok in a mode, and
 // the int32 score range (min(n, len) * largest entry < 2^28); the message names `what idx`
 bool profile_range_ok(const sw_profile* pf, int len, int gap_init, int gap_ext, int amode, const char* what, int idx);
+
+// ---- translated search (include/algoGPU.h sw_*_translated*) ----
+// The rules are host only (sw_matrix_host.cpp: frames, sw_translate, the composed tables; sw_align_host.cpp: the
+// checks and the CPU aligner); sw_matrix.hip's XLATE kernels fetch codons by the same rules.
+constexpr int XL_AMBIGUOUS = 4;   // base[] of a byte that is none of T, C, A, G (either case) or U
+// What the XLATE kernels stage beside the matrix: sw_translated_tables' two tables.  minus: the align launches,
+// one frame a pair: 1 where pair k's frame is a minus frame (null: the caller sets DevSeq::minus itself).
+struct Translated {
+    unsigned char base[256];
+    unsigned char codon[68];   // 65 used
+    const int* minus = nullptr;
+};
+// frame +1, +2, +3, -1, -2, -3 -> index 0..5; anything else -1
+int frame_index(int frame);
+// residues of frame index fi of a DNA of len bases, and where the 3 * m bases the frame covers begin
+int frame_residues(int len, int fi);
+int frame_region(int len, int fi);
+// the tables of (mx, code64 or null: the standard code); a byte the matrix does not score: -1, the message names fn
+int translated_tables(const char* fn, const sw_matrix* mx, const unsigned char* code64, Translated* out);
+// The argument, mode, gap, length, frame, range and alphabet checks of the sw_*_matrix_translated_* entry points
+// over host pairs (fn names the entry point in every message); frames null: the score call, all six.  Fills *xl.
+int translated_check(const char* fn, const sw_matrix* mx, const unsigned char* const* a, const int* alen,
+                     const unsigned char* const* dna, const int* dlen, const int* frames, int npairs, int gap_init,
+                     int gap_ext, int mode, const unsigned char* code64, Translated* xl);
+// the range refusals of one query of length alen against a DNA of dlen bases (its longest frame), `what idx`
+bool translated_range_ok(const char* fn, const sw_matrix* mx, int alen, int dlen, int gap_init, int gap_ext, int amode,
+                         const char* what, int idx);
+// The XLATE launches of sw_matrix.hip over pairs resident in device memory: seq1 = d_arena[a_off[k], +alen[k]),
+// the DNA d_arena[d_off[k], +dlen[k]); checked by the caller.  Score: all six frames, scores_out (host) holds
+// 6 * npairs entries, the empty frames answered here.  Align: frame index fidx[k] of pair k, sink.out[k] in order.
+int translated_score_device(const sw_matrix* mx, const Translated& xl, const unsigned char* d_arena, const int64_t* a_off,
+                            const int* alen, const int64_t* d_off, const int* dlen, int npairs, int gap_init, int gap_ext,
+                            int amode, int* scores_out);
+int translated_align_device(const sw_matrix* mx, const Translated& xl, const unsigned char* d_arena, const int64_t* a_off,
+                            const int* alen, const int64_t* d_off, const int* dlen, const int* fidx, const int* name_idx,
+                            int npairs, int gap_init, int gap_ext, const char* what, AlignSink& sink, int amode);
 
 // ---- banded alignment (include/algoGPU.h sw_*_band) ----
 // The arithmetic is host only (sw_align_host.cpp); sw_matrix.hip's kernels compute the same per strip.

@@ -21,7 +21,7 @@ import os
 
 import numpy as np
 
-from . import _LONG_CIGAR_CAP, SwError, _align_call, _check, _mode, _ptr, _u8, lib
+from . import FRAMES, _LONG_CIGAR_CAP, SwError, _align_call, _check, _code, _frame, _mode, _ptr, _translated, _u8, lib
 
 
 class Database:
@@ -240,6 +240,54 @@ class Database:
         if not alignments:
             return hits
         al = self.align_profile(profile, [h[1] for h in hits], gap_init, gap_ext, mode=mode)
+        return [h + (x,) for h, x in zip(hits, al)]
+
+    # ---- translated search: a protein query against DNA records in six reading frames ---------------
+    def search_translated(self, query, matrix, gap_init: int, gap_ext: int, mode: str = "local", code=None) -> np.ndarray:
+        """int32 scores, shape (len(self), 6): the protein ``query`` against the six reading frames (+1, +2, +3, -1,
+        -2, -3) of every DNA record, translated by the kernel as it reads the arena (sw_db_search_matrix_translated);
+        ``code``: a genetic code of 64 bytes (None: the standard one).  The records are not checked against the
+        matrix: any byte is a DNA byte, and a codon with a byte other than T/U, C, A, G is ``X``."""
+        q = _u8(query)
+        keep, cp = _code(code)
+        out = np.zeros((len(self), 6), dtype=np.int32)
+        _check(lib().sw_db_search_matrix_translated(self._h, matrix._handle(), _ptr(q), len(q), int(gap_init), int(gap_ext),
+                                                    _mode(mode), cp, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+        return out
+
+    def align_translated(self, query, indices, frames, matrix, gap_init: int, gap_ext: int, mode: str = "local",
+                         code=None) -> list:
+        """A :class:`TranslatedAlignment` of ``query`` (seq1) with frame ``frames[k]`` of record ``indices[k]``, out of
+        the database's device arena (sw_db_align_matrix_translated)."""
+        am = _mode(mode)
+        q = _u8(query)
+        keep, cp = _code(code)
+        idx = [int(i) for i in indices]
+        fr = [_frame(f) for f in frames]
+        n = len(idx)
+        if len(fr) != n:
+            raise ValueError("%d frames for %d records" % (len(fr), n))
+        if n == 0:
+            return []
+        IDX = (ctypes.c_int * n)(*idx)
+        FR = (ctypes.c_int * n)(*fr)
+        als = _align_call(lambda out, cig, cap, used: lib().sw_db_align_matrix_translated(
+            self._h, matrix._handle(), _ptr(q), len(q), IDX, FR, n, int(gap_init), int(gap_ext), am, cp, out, cig, cap, used),
+            n, 16 * n)
+        return _translated(als, fr, [self.length(i) for i in idx])
+
+    def top_translated(self, query, k: int = 10, matrix=None, gap_init: int = 0, gap_ext: int = 0, alignments: bool = False,
+                       mode: str = "local", code=None) -> list:
+        """The k best (record, frame) hits of :meth:`search_translated`: [(score, index, frame, header)], score
+        descending, then index ascending, then frame order +1, +2, +3, -1, -2, -3; with ``alignments=True`` each
+        tuple ends with the hit's :class:`TranslatedAlignment`."""
+        sc = self.search_translated(query, matrix, gap_init, gap_ext, mode=mode, code=code).reshape(-1)
+        flat = np.lexsort((np.arange(len(sc)), -sc.astype(np.int64)))[:k]   # flat = 6 * index + frame index
+        hits = [(int(sc[i]), int(i) // 6, FRAMES[int(i) % 6], self.header(int(i) // 6)) for i in flat]
+        if not alignments:
+            return hits
+        al = self.align_translated(query, [h[1] for h in hits], [h[2] for h in hits], matrix, gap_init, gap_ext, mode=mode,
+                                   code=code)
         return [h + (x,) for h, x in zip(hits, al)]
 
     def top(self, query, k: int = 10, matrix=None, gap_init=None, gap_ext=None, alignments: bool = False,

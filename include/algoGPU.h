@@ -694,6 +694,81 @@ int  sw_db_search_profile(sw_db*, const sw_profile*, int gap_init, int gap_ext, 
 int  sw_db_align_profile(sw_db*, const sw_profile*, const int* record_idx, int nidx, int gap_init, int gap_ext,
                          int mode, sw_alignment* out, unsigned* cigar, long long cigar_cap, long long* cigar_used);
 
+/* ---- translated search: a protein query against DNA in six reading frames ----------
+ * The tblastn / tfasty question: where does this protein occur in these DNA records?  seq1 is the protein
+ * (the query), seq2 a reading frame of the DNA, translated by the kernel as it fetches: nothing is translated
+ * ahead of time and the DNA stays in the arena as it is.
+ *
+ * BASES.  A byte's class: T, t, U, u = 0; C, c = 1; A, a = 2; G, g = 3; every other byte is ambiguous.  The
+ *   complement of class x is x ^ 2.  Any byte is a legal DNA byte: the DNA is not checked against the matrix
+ *   alphabet (and a database's record of checked matrices is not touched).
+ * GENETIC CODE.  64 bytes, one amino-acid byte a codon, at index 16*b1 + 4*b2 + b3 over the classes above
+ *   (NCBI's TCAG order).  A codon with an ambiguous base translates to 'X'; degenerate codons are NOT resolved
+ *   (CTN is 'X', not 'L').  code64 = NULL is the standard code (sw_standard_code):
+ *   FFLLSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG.
+ * FRAMES.  +1, +2, +3, -1, -2, -3 (BLAST's numbering); arrays of six hold them in this order.  Frame +-k has
+ *   offset o = k - 1 and m = (L - o) / 3 residues if L >= o + 3, else 0.  Residue r of a plus frame is the codon
+ *   dna[3r+o .. 3r+o+2]; of a minus frame the codon comp(dna[L-1-3r-o]), comp(dna[L-2-3r-o]), comp(dna[L-3-3r-o])
+ *   (the reverse complement read forward).
+ * ALPHABET.  The matrix must score every byte the code can emit: the distinct bytes of the 64 and 'X', each a
+ *   symbol of the matrix or covered by `other`.  A missing byte is refused before any launch and named.  The
+ *   query is checked against the matrix as in every matrix call.
+ * SCORING.  Everything else is the matrix path's: the recurrence, the gap model, the three modes (SW_MODE_*),
+ *   the end-cell rule, the walk, the tie rules, and the range refusals with m the frame's residue count.  The
+ *   query lies across the lanes, the frame streams: never swapped.  An empty frame or an empty query is
+ *   answered on the host as an empty sequence is (local: 0 and an empty alignment).
+ * COORDINATES.  beg2 / end2 of an alignment are residues of the frame.  [beg2, end2) covers the bases
+ *   [3*beg2 + o, 3*end2 + o) in a plus frame, [L - o - 3*end2, L - o - 3*beg2) on the forward strand in a minus
+ *   frame (sw_translated_range).
+ *
+ * sw_standard_code: the 64 bytes above.
+ * sw_translate: out[0, m) = the residues of `frame` of dna[0, len) under code64 (NULL: standard); returns m, or
+ *   -1 for a frame outside +-1..+-3, a null pointer, len < 0, or cap < m.  The single host statement of the
+ *   rules above; with a minus frame it also gives the other direction (blastx): translate the DNA query into
+ *   six protein queries and call the existing matrix search with each.
+ * sw_translated_range: the DNA range of residues [beg2, end2) of `frame` of a DNA of `len` bases; -1 for a bad
+ *   frame or a range outside the frame.
+ * sw_translated_tables: what the kernel stages, composed from (matrix, code): base[256] the class of every byte
+ *   (0..3, 4 = ambiguous) and codon[65] the matrix code of each codon's amino acid, entry 64 that of 'X'.  -1
+ *   with the missing byte named when the matrix does not score a byte the code can emit.
+ * sw_score_matrix_translated_batch: scores_out[6*k + f] = the score of a[k] against frame index f of dna[k] in
+ *   `mode`; one launch of up to 6 * npairs items, longest first.  sw_last_stats: mode 15, variant the alignment
+ *   mode, cells the sum of n * m over the frames; options "W" and "blocks" as mode 6.
+ * sw_align_matrix_translated_batch: one alignment a pair, in the frame frames[k] names (+-1..+-3), by the traced
+ *   instantiation (W = 8) and the matrix path's walk; sw_alignment as it is, in residues of the frame.  A pair
+ *   whose trace does not fit trace_mb alone is refused: there is no long path here.  sw_last_stats: mode 16.
+ * sw_align_matrix_translated_cpu: the same arguments and, bit for bit, the same alignments: sw_translate, then
+ *   the host aligner of sw_align_matrix_cpu_mode.
+ * sw_db_search_matrix_translated: scores_out[6*r + f] for every record r of a DNA database, out of the arena.
+ * sw_db_align_matrix_translated: the query aligned with frame frames[k] of record record_idx[k].
+ * Every refusal names the call: a frame outside +-1..+-3, a null pointer, a DNA longer than 2^27 - 1 bases, a
+ *   byte of the code the matrix does not score, a pair whose trace does not fit.
+ * Not built: band=, coop=, the long path and profiles against translated frames; many queries in one call;
+ *   degenerate-codon resolution; frameshift-aware alignment; start-codon tables; a both-strand
+ *   nucleotide-against-nucleotide search; 16-bit packing. */
+void sw_standard_code(unsigned char out[64]);
+int  sw_translate(const unsigned char* dna, int len, int frame, const unsigned char* code64, unsigned char* out, int cap);
+int  sw_translated_range(int len, int frame, int beg2, int end2, int* dna_beg, int* dna_end);
+int  sw_translated_tables(const sw_matrix*, const unsigned char* code64, unsigned char base_out[256],
+                          unsigned char codon_out[65]);
+int  sw_score_matrix_translated_batch(const sw_matrix*, const unsigned char* const* a, const int* alen,
+                                      const unsigned char* const* dna, const int* dlen, int npairs, int gap_init,
+                                      int gap_ext, int mode, const unsigned char* code64, int* scores_out /* 6*npairs */);
+int  sw_align_matrix_translated_batch(const sw_matrix*, const unsigned char* const* a, const int* alen,
+                                      const unsigned char* const* dna, const int* dlen, const int* frames, int npairs,
+                                      int gap_init, int gap_ext, int mode, const unsigned char* code64, sw_alignment* out,
+                                      unsigned* cigar, long long cigar_cap, long long* cigar_used);
+int  sw_align_matrix_translated_cpu(const sw_matrix*, const unsigned char* const* a, const int* alen,
+                                    const unsigned char* const* dna, const int* dlen, const int* frames, int npairs,
+                                    int gap_init, int gap_ext, int mode, const unsigned char* code64, sw_alignment* out,
+                                    unsigned* cigar, long long cigar_cap, long long* cigar_used);
+int  sw_db_search_matrix_translated(sw_db*, const sw_matrix*, const unsigned char* query, int qlen, int gap_init,
+                                    int gap_ext, int mode, const unsigned char* code64, int* scores_out /* 6*records */);
+int  sw_db_align_matrix_translated(sw_db*, const sw_matrix*, const unsigned char* query, int qlen, const int* record_idx,
+                                   const int* frames, int nidx, int gap_init, int gap_ext, int mode,
+                                   const unsigned char* code64, sw_alignment* out, unsigned* cigar, long long cigar_cap,
+                                   long long* cigar_used);
+
 /* Tuning knobs (process-wide).  Keys:
  *   "W"        columns per lane: 0 = auto, 1, 2, 4, 8
  *   "C"        rows per strip hand-off chunk: 0 = auto, 16, 32, 64
@@ -714,7 +789,8 @@ int  sw_db_align_profile(sw_db*, const sw_profile*, const int* record_idx, int n
  *              traced launches of sw_align_matrix_batch / sw_db_align_matrix: "blocks", "trace_mb";
  *              and mode 8 = their _long counterparts, which honour the same two; and modes 9 and 10 =
  *              the band launches, score-only and traced: sw_*_band, as modes 6 and 7; and modes 13 and 14 =
- *              the profile launches, score-only and traced: sw_*_profile_*, as modes 6 and 7)
+ *              the profile launches, score-only and traced: sw_*_profile_*, as modes 6 and 7; and modes 15 and
+ *              16 = the translated launches, score-only and traced: sw_*_matrix_translated*, as modes 6 and 7)
  *   "trace_mb" MiB of trace memory one traced launch may hold, 1..3072 (default 1024)
  *   "duo16"    1 = (default) packed duos take max3 through v_pk_maximum3_f16 when every
  *              value stays below 0x7C00 (MATCH*(min(n,m)+1) <= 31743), 0 = u16 max only

@@ -22,9 +22,15 @@ PROFILE instantiations of sw_matrix.hip) against the matrix search of the same q
 searches each after one warm-up: both times, their ratio, W and the resident waves per CU of each, and whether the scores
 are equal (they must be).
 
+--translated (with --matrix): instead of all the above, the translated search (Database.search_translated, the XLATE
+instantiations of sw_matrix.hip) of a random protein query against R DNA records of 3 * lo to 3 * hi bases, and its
+yardstick: the existing matrix search of the same query over a protein database that holds the six host-translated
+frames of the same records -- the same items, cells and W.  Alternated three times, --steps searches each after one
+warm-up; one line with both times, the kernel times, the ratios and whether the scores are equal (they must be).
+
     python tools/bench_db.py [--records R] [--qlen Q] [--lo L] [--hi H] [--steps K] [--alphabet dna|protein]
                              [--opt k=v ...] [--matrix random|FILE --gaps G_INIT,G_EXT] [--alignments K] [--plant P]
-                             [--mode local|global|semiglobal] [--profile]
+                             [--mode local|global|semiglobal] [--profile] [--translated]
 """
 import argparse
 import json
@@ -36,6 +42,65 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from concurrentproject_amd.db import Database  # noqa: E402
+
+
+def translated(a):
+    import concurrentproject_amd as sw
+    for kv in a.opt:
+        k, v = kv.split("=")
+        sw.set_option(k, int(v))
+    rng = np.random.default_rng(4)
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+    aa = np.frombuffer(b"ACDEFGHIKLMNPQRSTVWY", dtype=np.uint8)
+    lens = rng.integers(3 * a.lo, 3 * a.hi + 1, size=a.records)
+    recs = [acgt[rng.integers(0, 4, size=n)] for n in lens]
+    q = aa[rng.integers(0, 20, size=a.qlen)]
+    if a.matrix == "random":   # over the amino acids and what else the code emits: 'X' and '*'
+        trng = np.random.default_rng(62)
+        sym = aa.tobytes() + b"X*"
+        tab = trng.integers(-4, 4, (22, 22))
+        tab[np.arange(22), np.arange(22)] = trng.integers(4, 12, 22)
+        mx = sw.Matrix(sym, tab)
+    else:
+        mx = sw.Matrix.open(a.matrix)
+    gi, ge = (int(x) for x in a.gaps.split(","))
+    dna = Database.from_fasta(b"".join(b">r%d\n" % i + r.tobytes() + b"\n" for i, r in enumerate(recs)))
+    frames = Database.from_fasta(b"".join(b">r%d%+d\n" % (i, f) + sw.translate(r, f) + b"\n"
+                                          for i, r in enumerate(recs) for f in sw.FRAMES))
+    runs = {"translated": lambda: dna.search_translated(q, mx, gi, ge, mode=a.mode).reshape(-1),
+            "frames": lambda: frames.search(q, matrix=mx, gap_init=gi, gap_ext=ge, mode=a.mode)}
+    ms = {k: [] for k in runs}
+    kms = {k: [] for k in runs}
+    stats, equal, ref = {}, True, None
+    for _ in range(3):
+        for which in ("frames", "translated"):
+            got = runs[which]()   # warm
+            ref = got if ref is None else ref
+            equal = equal and got.tolist() == ref.tolist()
+            k = []
+            t0 = time.perf_counter()
+            for _ in range(a.steps):
+                runs[which]()
+                k.append(sw.last_stats()["kernel_ms"])
+            ms[which].append(round((time.perf_counter() - t0) / a.steps * 1e3, 3))
+            kms[which].append(round(float(np.median(k)), 3))
+            stats[which] = sw.last_stats()
+    cells = stats["translated"]["cells"]
+    launch = lambda st: {"mode": st["mode"], "W": st["W"], "waves_per_cu": st["waves_per_cu"], "blocks": st["blocks"],
+                         "cells": st["cells"]}
+    print(json.dumps({"metric": "db translated search against the matrix search of the six translated frames (host API, alternated)",
+                      "matrix": a.matrix, "gaps": [gi, ge], "align_mode": a.mode, "records": a.records, "qlen": a.qlen,
+                      "dna_len_range": [3 * a.lo, 3 * a.hi], "bases": int(lens.sum()), "steps": a.steps,
+                      "frames_ms_per_search": ms["frames"], "translated_ms_per_search": ms["translated"],
+                      "frames_kernel_ms": kms["frames"], "translated_kernel_ms": kms["translated"],
+                      "ratio_translated_over_frames": round(float(np.median(ms["translated"])) / float(np.median(ms["frames"])), 3),
+                      "kernel_ratio_translated_over_frames": round(float(np.median(kms["translated"])) / float(np.median(kms["frames"])), 3),
+                      "frames_launch": launch(stats["frames"]), "translated_launch": launch(stats["translated"]),
+                      "translated_GCUPS": round(cells / (float(np.median(ms["translated"])) / 1e3) / 1e9, 2),
+                      "scores_equal": equal, "max_score": int(ref.max())}))
+    dna.close()
+    frames.close()
+    mx.close()
 
 
 def main():
@@ -57,7 +122,14 @@ def main():
                     help="alignment mode of a --matrix search")
     ap.add_argument("--profile", action="store_true",
                     help="also search with Profile.from_matrix(matrix, query), alternated with the matrix search (--matrix)")
+    ap.add_argument("--translated", action="store_true",
+                    help="the translated search of a protein query against DNA records, and the matrix search over their "
+                         "six host-translated frames (--matrix)")
     a = ap.parse_args()
+    if a.translated and a.matrix is None:
+        ap.error("--translated needs --matrix")
+    if a.translated:
+        return translated(a)
     if a.profile and a.matrix is None:
         ap.error("--profile needs --matrix")
     if a.mode != "local" and a.matrix is None:
