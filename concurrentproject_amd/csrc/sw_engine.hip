@@ -182,6 +182,12 @@ struct Opts {
     // chains in a combine kernel of its own; anything else or unset = the staged kernel does all of it
     // (sw_internal.h KParams::wedge_join)
     int f3join = 1;
+    // environment SWMI_F3WEDGE_TRACE, read with the snapshot (tools/trace_wedge.py; not an option): 1 = a traced
+    // launch (option trace) may still be planned as two wedges, and then the trace buffer holds 2 S rows of 16
+    // words, chain * S + strip (S: the strips a chain of sw_internal.h steep_bounds / wedge_bounds, never more
+    // than sw_last_stats' items * 2); anything else or unset = a traced launch stays one chain of 16-word rows
+    // per strip
+    int f3wtrace = 0;
     long long operator[](Opt o) const { return v[o]; }
 };
 Opts snapshot_opts() {
@@ -191,6 +197,8 @@ Opts snapshot_opts() {
     o.f3wedge = w && w[0] == '0' && !w[1] ? 0 : w && w[0] == '1' && !w[1] ? 1 : -1;
     const char* j = std::getenv("SWMI_F3JOIN");
     o.f3join = j && j[0] == '0' && !j[1] ? 0 : 1;
+    const char* t = std::getenv("SWMI_F3WEDGE_TRACE");
+    o.f3wtrace = t && t[0] == '1' && !t[1] ? 1 : 0;
     if (const char* d = std::getenv("SWMI_F3WEDGE_DROPS")) {
         char tail = 0;
         const int got = std::sscanf(d, "%d,%d,%d,%d%c", &o.f3drops[0], &o.f3drops[1], &o.f3drops[2], &o.f3drops[3], &tail);
@@ -873,7 +881,8 @@ constexpr int F3_STEEP_AUTO_N = 4096;
 constexpr int F3_STEEP_AUTO_DROPS[4] = {64, 128, 64, 128};
 constexpr int F3_STEEP_QUEUED_DROPS[4] = {128, 64, 128, 128};
 bool plan_wedge(Job& job, const Params& prm, const Opts& opt, int cus) {
-    if (opt[O_f3split] != -1 || opt.f3wedge == 0 || job.pairs.size() != 1 || opt[O_trace] != 0) return false;
+    if (opt[O_f3split] != -1 || opt.f3wedge == 0 || job.pairs.size() != 1 || (opt[O_trace] != 0 && !opt.f3wtrace))
+        return false;
     const Variant v = select_variant(job, prm, opt, cus);
     if (v.err || !v.cfg.f3 || v.ring || v.cfg.f2_stream || v.cfg.f3p || job.slab) return false;
     const PairDesc whole = job.pairs[0];

@@ -99,7 +99,8 @@ struct KParams {
     const unsigned char* hrows;   // ring mode (sw_flow3r3h / ra3h_kernel): the pair's rows as perm selectors
     const DuoDesc* duos;          // duo mode: nduos descriptors (npairs counts duos)
     long long timeout_ticks;      // s_memrealtime ticks (100 MHz) before a spin gives up
-    unsigned long long* trace;    // optional (tools/trace_flow.py): per-strip timestamps, else null
+    unsigned long long* trace;    // optional (tools/trace_flow.py): per-strip timestamps, else null; a wedge launch
+                                  // (tools/trace_wedge.py): 16 words at row chain * S + strip, sw_flow3.hip
     // Column slab of a pair split across GPUs (grouped modes, one pair per launch):
     // the first group's inflow comes from slab_in (the previous slab's last
     // column, written by the previous GPU over xGMI), the last group's outflow

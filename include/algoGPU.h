@@ -836,7 +836,9 @@ int  sw_db_align_matrix_translated(sw_db*, const sw_matrix*, const unsigned char
  *              A two-wedge launch is one kernel: the staged kernel joins the chains itself, carries the two
  *              descriptors in its arguments and neither copies nor clears anything first.  The environment
  *              variable SWMI_F3JOIN = 0 (A/B runs and tests) keeps the earlier launch instead: descriptor
- *              copies, memsets of the claim counter and the score, and a combine kernel behind the staged one
+ *              copies, memsets of the claim counter and the score, and a combine kernel behind the staged one.
+ *              SWMI_F3WEDGE_TRACE = 1 lets a traced launch (option trace) keep its two wedges: the trace buffer
+ *              then holds 16 words at row chain * S + strip, S the strips a chain (tools/trace_wedge.py)
  *   "f3pwg"    1 = (default) DNA batches on a pair-per-workgroup plan (scores that need int32, or 1-2
  *              pairs per CU) run flow3's three-column ring step (sw_flow3r3p / ra3p_kernel), 0 = flow2's
  *   "f3slab"   1 = (default) column slabs run flow3's ring kernel with slab roles
