@@ -19,7 +19,8 @@ Register use inside the block is fixed (declared as clobbers):
   v64/v65 IO / L0 (they swap roles every step), v66 H_A, v67 max(H_A - G, 0),
   v68 H_B, v69 max(H_B - G, 0), v70/v71 tA/tB, v72/v73 score bytes of 4 rows,
   v74 running max, v[76:83] / v[84:91] row codes of the even / odd chunk,
-  v92 inflow rows, v93 producer word, v94 code address, v95 inflow address,
+  v92 inflow rows (half-chunk links: the odd chunk's I/O register, v64 the even chunk's, each taking
+  the other's next inflow read), v93 producer word, v94 code address, v95 inflow address,
   v96 outflow address, v97 producer word value, v98 consumer word value,
   v99 back-pressure read, v[100:101] granule, v105 granule offset (row * 8),
   v106 masked offset; s40 k0 (the chunk's first lane-0 row), s41 ring offset,
@@ -31,7 +32,11 @@ Hazards handled here (gfx950): a VALU write of a VGPR is >= 2 instructions befor
 a DPP read of it (the step order guarantees 4-10); no sub-dword (SDWA dst_sel)
 writes; every LDS/SMEM result is waited for with an explicit lgkmcnt before use,
 and the block drains lgkmcnt/vmcnt before it returns (the compiler does not see
-the counters inside).
+the counters inside).  A v_cmp that writes vcc needs no s_nop before s_cbranch_vccnz:
+the ISA's table of software wait states asks for them only where a VALU reads
+VCCZ / EXECZ as data, before v_readlane / v_div_fmas and before DPP, not before a
+branch on vccz, which waits for the VALU itself (LLVM's hazard recognizer inserts
+none there either).
 """
 import os
 import sys
@@ -48,6 +53,21 @@ RING_ALIGN = int(os.environ.get("F3_RING_ALIGN", "0"))   # A/B: align the ring l
 STAGED_PROMOTE = int(os.environ.get("F3_PROMOTE", "1"))   # A/B: staged alignment by VOP3 re-encoding (1) or s_nop only (0)
 RING_NOPS = int(os.environ.get("F3_RING_NOPS", "0"))   # A/B: alignment nops in the ring loops (0: re-encodings only)
 ROLES_OUT = ("none", "lds", "gran")
+# The half-chunk links (C = 32, hl) with fewer instructions a chunk ("leaner links";
+# profiles/f3links_decomp.md).  Each is an A/B switch; the committed .inc has the defaults.
+LINK_ADV = int(os.environ.get("F3_LINK_ADV", "1"))         # ring offset and inflow address advance once a loop iteration
+LINK_NOCOPY = int(os.environ.get("F3_LINK_NOCOPY", "1"))   # the inflow read lands in the next chunk's I/O register
+LINK_VCHK = int(os.environ.get("F3_LINK_VCHK", "1"))       # producer-word checks by v_cmp + s_cbranch_vccnz
+LINK_CONS2 = int(os.environ.get("F3_LINK_CONS2", "1"))     # the consumer word every second chunk
+# Timing probes only (wrong scores, never committed): F3_LINK_DROP = a comma list of
+#   mirror  one-dword row writes (no mirror copy)
+#   words   no producer- or consumer-word write in the loop (both words F3_BIG from the start)
+#   cons    no consumer-word write in the loop (F3_BIG from the start)
+#   mid     no mid-chunk publish and take
+#   book    no per-chunk advance of the ring offset, the addresses and the word values
+#   checks  no producer-word check at the chunk top and at mid-chunk
+LINK_DROP = frozenset(x for x in os.environ.get("F3_LINK_DROP", "").split(",") if x)
+assert LINK_DROP <= {"mirror", "words", "cons", "mid", "book", "checks"}, LINK_DROP
 
 
 # step registers of the staged (C2) loops: H_A, max(H_A - G, 0), H_B, max(H_B - G, 0), tA, tB,
@@ -92,7 +112,7 @@ OPERAND_CLASS = {
 }
 _SIZE_CACHE = {}
 _PROMOTABLE = ("v_mov_b32", "v_add_u32", "v_sub_u32", "v_subrev_u32", "v_xor_b32", "v_max_i32", "v_max_u32",
-               "v_min_i32", "v_lshrrev_b32", "v_lshlrev_b32", "v_and_b32", "v_or_b32", "v_cndmask_b32")
+               "v_min_i32", "v_lshrrev_b32", "v_lshlrev_b32", "v_and_b32", "v_or_b32", "v_cndmask_b32", "v_cmp_gt_i32")
 
 
 def _norm(line):
@@ -153,13 +173,13 @@ def align8(lines, nops=True, promote=True):
     return lines[:i0 + 1] + out + lines[i1:]
 
 
-def granule(a, rows):
-    """Publish the `rows` newest outflow rows (lanes 64-rows..63 of the IO register v64,
+def granule(a, rows, io="v64"):
+    """Publish the `rows` newest outflow rows (lanes 64-rows..63 of the IO register `io`,
     mask %[m48]) as 8-B granules {H-G, (H-G) ^ epoch ^ 0x5BD1E995} at row * 8 of the group
     edge, write-through (sw_flow3.hip header).  v105 = this lane's row * 8 (rows < 0 wrap
     to huge offsets: dropped by the buffer range check, as are rows past 2m)."""
-    a("v_mov_b32 v100, v64")
-    a("v_xor_b32 v101, %[ek], v64")
+    a(f"v_mov_b32 v100, {io}")
+    a(f"v_xor_b32 v101, %[ek], {io}")
     a("v_cndmask_b32_e64 v106, -16, v105, %[m48]")
     a(f"v_add_u32 v105, {rows * 8:#x}, v105")    # (an independent VALU between the data writes and the store)
     a("buffer_store_dwordx2 v[100:101], v106, %[rsrc], 0 offen sc1")
@@ -184,6 +204,37 @@ def gen_role(IN, OUT_, spec=0, halfpub=True, C=32, hl=False):
     nw = 2 if lds_out else 0            # LDS writes of a chunk's publish (ring + mirror in one, the word)
     grows = C // 2 if halfpub else C    # rows per granule publish
     assert not hl or (C == 32 and spec == 4)
+    # ---- the leaner half-chunk links (the switches at the top of this file; hl roles only)
+    adv = hl and bool(LINK_ADV) and (lds_in or lds_out)   # (a role without a link keeps its code)
+    nocopy = hl and lds_in and bool(LINK_NOCOPY)
+    vchk = hl and bool(LINK_VCHK)
+    cons2 = hl and bool(LINK_CONS2)
+    drop = LINK_DROP if hl else frozenset()
+    mid = hl and "mid" not in drop
+    wr_prod = lds_out and "words" not in drop                      # the producer word, every publish
+    wr_cons = lds_in and not drop & {"words", "cons"}              # the consumer word
+    checks = "checks" not in drop
+    # k0 + H for the back-pressure check at the loop's top comes from the end of the last loop body (two
+    # scalar instructions in front of the 8-B publish instead of three and an s_nop)
+    s52_early = hl and lds_out and bool(LINK_ADV)
+    slot0 = hl_slot0() if hl and (lds_in or lds_out) else 128                              # slot of row 0 (sw_flow3.hip f3_slot0)
+    s41_0 = (slot0 - 64 - C) * 4                                   # ring offset of the chunk at k0 = 0, in bytes
+
+    def io_of(p):
+        """The I/O register's name in chunk p of the loop body: with nocopy the odd chunk steps from
+        v92, where the read issued in the even chunk landed, and the even chunk from v64."""
+        return "v92" if nocopy and p == 1 else "v64"
+
+    def row_write(addr, io):
+        """The 64 lanes' rows into the ring and its mirror copy (timing probe: the ring only)."""
+        if "mirror" in drop:
+            a(f"ds_write_b32 {addr}, {io}")
+        else:
+            a(f"ds_write2st64_b32 {addr}, {io}, {io} offset1:{R * 4 // 256}")
+
+    def off(n):
+        return f" offset:{n}" if n else ""
+
     # ---- entry (s_nop 4: the "s" operands may be fresh from v_readfirstlane, and buffer
     # instructions read them as descriptors: 5 wait states)
     a("s_nop 4")
@@ -192,9 +243,11 @@ def gen_role(IN, OUT_, spec=0, halfpub=True, C=32, hl=False):
         a(f"v_mov_b32 {r}, 0")
     a("v_mov_b32 v64, %[ng]")
     a("v_mov_b32 v65, %[ng]")
+    if nocopy:
+        a("v_mov_b32 v92, %[ng]")        # (the first chunk top publishes it: rows < 0, never read)
     a("v_mov_b32 v94, %[code]")
     a("s_mov_b32 s40, 0")
-    a(f"s_movk_i32 s41, {(64 - C) * 4:#x}")       # ((k0 + 64 - C) mod R) * 4 at k0 = 0
+    a(f"s_movk_i32 s41, {s41_0:#x}")     # ((k0 + slot0 - 96) mod R) * 4 at k0 = 0
     a("s_mov_b32 s45, 0")
     a("s_mov_b32 s46, 0")
     a(f"s_movk_i32 s44, {R}")            # consumer word seen: 0 rows consumed (+ R)
@@ -207,13 +260,23 @@ def gen_role(IN, OUT_, spec=0, halfpub=True, C=32, hl=False):
         if hl:
             a("s_mov_b32 s50, 0xffff")   # lanes 0..15: the mid-chunk inflow rows
             a("s_mov_b32 s51, 0")
+    if drop & {"words", "cons", "book"}:   # timing probes: the words this loop no longer moves say "all done"
+        a(f"v_mov_b32 v99, {BIG:#x}")
+        if lds_out and drop & {"words", "book"}:
+            a("ds_write_b32 %[pout], v99")
+            a("v_mov_b32 v97, v99")
+        if lds_in:
+            a("ds_write_b32 %[qme], v99")
+            a("v_mov_b32 v98, v99")
     if gran:
         a("v_mov_b32 v105, %[lrow]")
     for q in range(ncr):
         a(f"ds_read_b128 v[{76 + 4 * q}:{79 + 4 * q}], v94 offset:{16 * q}")
     if lds_in and spec:
         a("ds_read_b32 v93, %[pin]")
-        a("ds_read_b32 v92, v95")
+        a(f"ds_read_b32 {io_of(0) if nocopy else 'v92'}, v95")
+    if s52_early:
+        a(f"s_movk_i32 s52, {H}")
     a(".p2align 6")                # the chunk loop on a 64-B boundary (a lone wave's issue rate depends on it)
     for _ in range(LOOP_PAD):
         a("s_nop 0")
@@ -222,90 +285,120 @@ def gen_role(IN, OUT_, spec=0, halfpub=True, C=32, hl=False):
         cur = 76 if p == 0 else 84
         nxt = 84 if p == 0 else 76
         obase = C if p == 0 else 2 * C
+        X, Y = io_of(p), io_of(1 - p)    # this chunk's I/O register; the last chunk's (its outflow), which takes
+        #                                  the next chunk's inflow once the top has published it
+        ioff = 4 * C * p if adv else 0   # adv: the inflow address moves once a loop body, the odd chunk reads 32 rows on
         # ---- chunk top: publish the last chunk's outflow, take this chunk's inflow
         if lds_in and not spec:
             a("ds_read_b32 v93, %[pin]")
             a("ds_read_b32 v92, v95")
+        ntw = 0                          # LDS writes of this chunk top's publish
         if lds_out:
             if p == 0:   # back-pressure for this chunk's and the next chunk's publish
                 if hl:   # (whose mid-chunk write-ahead lanes reach 16 rows further)
-                    a(f"s_add_u32 s52, s40, {H}")
+                    if not s52_early:
+                        a(f"s_add_u32 s52, s40, {H}")
                     a("s_cmp_lt_i32 s44, s52")
                 else:
                     a("s_cmp_lt_i32 s44, s40")
                 a(f"s_cbranch_scc1 L_bp{p}_%=")
                 a(f"L_bpr{p}_%=:")
-            a(f"ds_write2st64_b32 v96, v64, v64 offset1:{R * 4 // 256}")   # the row and its mirror copy
-            a("ds_write_b32 %[pout], v97")
+            row_write("v96", Y)          # the row and its mirror copy
+            ntw = 1
+            if wr_prod:
+                a("ds_write_b32 %[pout], v97")
+                ntw = 2
         if gran:
-            granule(a, grows)
+            granule(a, grows, Y)
         for q in range(ncr):
             a(f"ds_read_b128 v[{nxt + 4 * q}:{nxt + 4 * q + 3}], v94 offset:{obase + 16 * q}")
         if lds_in:
-            after = 1 + nw + ncr         # LDS ops issued after the producer-word read
-            a(f"s_waitcnt lgkmcnt({after})")
-            a("v_readfirstlane_b32 s43, v93")
-            a("s_cmp_lt_i32 s43, s40")
-            a(f"s_cbranch_scc1 L_in{p}_%=")
-            a(f"L_inr{p}_%=:")
+            after = 1 + ntw + ncr        # LDS ops issued after the producer-word read
+            if checks:
+                a(f"s_waitcnt lgkmcnt({after})")
+                if vchk:                 # (the word is read at a uniform address: every lane compares the same)
+                    a("v_cmp_gt_i32 vcc, s40, v93")
+                    a(f"s_cbranch_vccnz L_in{p}_%=")
+                else:
+                    a("v_readfirstlane_b32 s43, v93")
+                    a("s_cmp_lt_i32 s43, s40")
+                    a(f"s_cbranch_scc1 L_in{p}_%=")
+                a(f"L_inr{p}_%=:")
             a(f"s_waitcnt lgkmcnt({after - 1})")
-            a("v_mov_b32 v64, v92")
-            a("ds_write_b32 %[qme], v98")
+            if not nocopy:
+                a("v_mov_b32 v64, v92")
+            if wr_cons and not (cons2 and p == 1):
+                a("ds_write_b32 %[qme], v98")
         else:
-            a(f"s_waitcnt lgkmcnt({nw + ncr})")
+            a(f"s_waitcnt lgkmcnt({ntw + ncr})")
             a("v_mov_b32 v64, %[ng]")
         # ---- C steps, C/4 groups of 4 rows (one v_perm_b32 per column per group)
         ng = C // 4
         spec_at = ng - spec // 4 if spec else None
         for u in range(ng):
             if spec and u == spec_at:
-                book(a, p, lds_in, lds_out, C, H)
+                if "book" in drop:
+                    book(a, p, False, False, C, H, ring=False)
+                else:
+                    book(a, p, lds_in, lds_out, C, H, adv, cons2, mid)
                 a("ds_read_b32 v93, %[pin]")
-                a("ds_read_b32 v92, v95")
-            if hl and lds_in and u == ng // 2 - MID_AHEAD:
+                a(f"ds_read_b32 {Y if nocopy else 'v92'}, v95{off(4 * C * (1 - p) if adv and lds_in else 0)}")
+            if mid and lds_in and u == ng // 2 - MID_AHEAD:
                 # the second half's rows, read 4 steps ahead behind the producer's word
                 a("ds_read_b32 v93, %[pin]")
-                a(f"ds_read_b32 v102, v95 offset:{4 * H}")
-            if hl and u == ng // 2:
+                a(f"ds_read_b32 v102, v95 offset:{4 * H + ioff}")
+            if mid and u == ng // 2:
                 # ---- mid-chunk: the newest 16 outflow rows out, the chunk's other 16 rows in
+                nmw = 0                  # LDS writes of the mid-chunk publish
                 if lds_out:
                     a("v_add_u32 v103, %[lmid], v96")   # lanes 32..47 (the chunk top's inflow) 32 rows on
                     a(f"v_add_u32 v97, {H}, v97")
-                    a(f"ds_write2st64_b32 v103, v64, v64 offset1:{R * 4 // 256}")
-                    a("ds_write_b32 %[pout], v97")
+                    row_write("v103", X)
+                    nmw = 1
+                    if wr_prod:
+                        a("ds_write_b32 %[pout], v97")
+                        nmw = 2
                 if lds_in:
-                    a(f"s_waitcnt lgkmcnt({1 + (2 if lds_out else 0)})")
-                    a("v_readfirstlane_b32 s43, v93")
-                    if not (lds_out and p == 0):   # (the chunk top's back-pressure check set s52 = k0 + H)
-                        a(f"s_add_u32 s52, s40, {H}")
-                    a("s_cmp_lt_i32 s43, s52")
-                    a(f"s_cbranch_scc1 L_mid{p}_%=")
-                    a(f"L_midr{p}_%=:")
-                    a(f"s_waitcnt lgkmcnt({2 if lds_out else 0})")
-                    a("v_cndmask_b32_e64 v64, v64, v102, s[50:51]")
+                    if checks:
+                        a(f"s_waitcnt lgkmcnt({1 + nmw})")
+                        if not vchk:
+                            a("v_readfirstlane_b32 s43, v93")
+                        if not (lds_out and p == 0):   # (the chunk top's back-pressure check set s52 = k0 + H)
+                            a(f"s_add_u32 s52, s40, {H}")
+                        if vchk:
+                            a("v_cmp_gt_i32 vcc, s52, v93")
+                            a(f"s_cbranch_vccnz L_mid{p}_%=")
+                        else:
+                            a("s_cmp_lt_i32 s43, s52")
+                            a(f"s_cbranch_scc1 L_mid{p}_%=")
+                        a(f"L_midr{p}_%=:")
+                    a(f"s_waitcnt lgkmcnt({nmw})")
+                    a(f"v_cndmask_b32_e64 {X}, {X}, v102, s[50:51]")
             # score bytes of 4 rows: selectors 4..7 pick pA (row symbols 0..3), 0..3 pick qA (0: no row,
             # 0x80; 1..3: row symbols 4..6 of a seven-letter alphabet, sw_flow3.hip HEP; DNA: 0x80808080)
             a(f"v_perm_b32 v72, %[pA], %[qA], v{cur + u}")
             a(f"v_perm_b32 v73, %[pB], %[qB], v{cur + u}")
             for b in range(4):
-                io, l0 = ("v64", "v65") if b % 2 == 0 else ("v65", "v64")
+                io, l0 = (X, "v65") if b % 2 == 0 else ("v65", X)
                 step(a, io, l0, b)
             if gran and halfpub and u == ng // 2 - 1:
-                granule(a, grows)
+                granule(a, grows, X)
         if not spec:
             book(a, p, lds_in, lds_out, C, H)
+    if s52_early:
+        a(f"s_add_u32 s52, s40, {H}")
     a("s_cmp_lt_i32 s40, %[end]")
     a("s_cbranch_scc1 L_loop_%=")
-    # ---- exit: the last chunk's outflow, then every row is out
+    # ---- exit: the last chunk's outflow (the odd chunk's I/O register), then every row is out
     if lds_out:
         a("s_cmp_lt_i32 s44, s40")
         a("s_cbranch_scc1 L_bpx_%=")
         a("L_bpxr_%=:")
-        a(f"ds_write2st64_b32 v96, v64, v64 offset1:{R * 4 // 256}")
+        row_write("v96", io_of(1))
         a(f"v_mov_b32 v97, {BIG:#x}")
         a("ds_write_b32 %[pout], v97")
     if gran:
-        granule(a, grows)
+        granule(a, grows, io_of(1))
     a("s_waitcnt vmcnt(0) lgkmcnt(0)")
     # ---- the strip's lower boundary (a wedge chain's staircase, sw_flow3.hip PAIR_WEDGE): H of both
     # columns at the lane's last row, then one step more (row k0 - lane: the next chunk's first row
@@ -333,12 +426,14 @@ def gen_role(IN, OUT_, spec=0, halfpub=True, C=32, hl=False):
     a("s_mov_b32 %[slow], s46")
     a("s_branch L_done_%=")
     # ---- slow paths (a late producer word, or a full ring): bounded spins
-    if lds_in:
+    if lds_in and checks:
         for p in (0, 1):
-            slow_wait(a, f"L_in{p}_%=", f"L_inr{p}_%=", "v93", "%[pin]", "s43", reread="ds_read_b32 v92, v95")
-            if hl:
+            ioff = 4 * C * p if adv else 0
+            slow_wait(a, f"L_in{p}_%=", f"L_inr{p}_%=", "v93", "%[pin]", "s43",
+                      reread=f"ds_read_b32 {io_of(p) if nocopy else 'v92'}, v95{off(ioff)}")
+            if mid:
                 slow_wait(a, f"L_mid{p}_%=", f"L_midr{p}_%=", "v93", "%[pin]", "s43",
-                          reread=f"ds_read_b32 v102, v95 offset:{4 * H}", target="s52")
+                          reread=f"ds_read_b32 v102, v95 offset:{4 * H + ioff}", target="s52")
     if lds_out:
         slow_wait(a, "L_bp0_%=", "L_bpr0_%=", "v99", "%[qnx]", "s44", target="s52" if hl else "s40")
         slow_wait(a, "L_bpx_%=", "L_bpxr_%=", "v99", "%[qnx]", "s44")
@@ -346,21 +441,69 @@ def gen_role(IN, OUT_, spec=0, halfpub=True, C=32, hl=False):
     return L
 
 
-def book(a, p, lds_in, lds_out, C=32, H=None):
+def hl_slot0():
+    """Slot of row 0 in a half-chunk link's ring (sw_flow3.hip F3_HL_SLOT0, written into the .inc).
+    With the ring offset advanced once a loop body (LINK_ADV) the even chunk's offset is
+    (k0 + slot0 - 96) mod R and the odd chunk sits 32 rows behind it without a wrap of its own; at
+    slot0 = 96 the even offsets are the multiples of 64 below R, so both chunks' windows start where
+    a window starts at slot0 = 128 with an advance every chunk: the multiples of 32 below R."""
+    return 96 if LINK_ADV else 128
+
+
+def hl_base(k0):
+    """Ring offset, in rows, that the half-chunk-link loops (C = 32) address the chunk at k0 from: s41 / 4, and
+    with LINK_ADV the odd chunk's 32 rows more (its reads' immediate offset, its publishes' address register).
+    Lane addresses on top of it (sw_flow3.hip F3Loop lin, lout, lmid): inflow 96 + (lane & 31) and 16 more at
+    mid-chunk; outflow (lane + 32) & 63, at mid-chunk 16 more and lanes 32..47 another 32; every write also at
+    R slots on.  tests/test_f3links_cpu.py holds these windows against sw_flow3.hip F3_RS."""
+    C = 32
+    p = (k0 // C) & 1
+    if LINK_ADV:
+        return (k0 - C * p + hl_slot0() - 96) % R + C * p
+    return (k0 + hl_slot0() - 96) % R
+
+
+def book(a, p, lds_in, lds_out, C=32, H=None, adv=False, cons2=False, mid=True, ring=True):
     """Advance k0, the ring offset and the words to the next chunk (H: rows a half-chunk
-    publish already added to the producer word)."""
-    H = C if H is None else H
-    a(f"s_add_i32 s40, s40, {C}")
-    a(f"s_add_u32 s41, s41, {4 * C:#x}")
-    a(f"s_and_b32 s41, s41, {(R - 1) * 4:#x}")
+    publish already added to the producer word).  adv: the ring offset and the inflow address
+    advance by two chunks in the odd chunk only, the outflow address by 32 rows in the even
+    chunk (ds_write2st64_b32 has no byte offset); cons2: the consumer word moves with them."""
+    H = C if H is None or not mid else H
+    if not adv:
+        a(f"s_add_i32 s40, s40, {C}")
+        if ring:
+            a(f"s_add_u32 s41, s41, {4 * C:#x}")
+            a(f"s_and_b32 s41, s41, {(R - 1) * 4:#x}")
+        if lds_out:
+            a("v_add_u32 v96, s41, %[lout]")
+            a(f"v_add_u32 v97, {C if H == C else C - H}, v97")
+        if lds_in:
+            a("v_add_u32 v95, s41, %[lin]")
+            if not cons2:
+                a(f"v_add_u32 v98, {C}, v98")
+            elif p == 1:
+                a(f"v_add_u32 v98, {2 * C}, v98")
+        if p == 1:
+            a(f"v_add_u32 v94, {2 * C}, v94")
+        return
+    # (the 4-B VALU adds first: align8 re-encodes one of them where the 8-B instructions behind the
+    # scalar ones would otherwise need an s_nop)
     if lds_out:
-        a("v_add_u32 v96, s41, %[lout]")
         a(f"v_add_u32 v97, {C if H == C else C - H}, v97")
-    if lds_in:
-        a("v_add_u32 v95, s41, %[lin]")
-        a(f"v_add_u32 v98, {C}, v98")
+    if lds_in and (p == 0 or not cons2):   # (cons2: the word is written at the even chunk's top only)
+        a(f"v_add_u32 v98, {2 * C if cons2 else C}, v98")
     if p == 1:
         a(f"v_add_u32 v94, {2 * C}, v94")
+    a(f"s_add_i32 s40, s40, {C}")
+    if p == 1:
+        a(f"s_add_u32 s41, s41, {8 * C:#x}")
+        a(f"s_and_b32 s41, s41, {(R - 1) * 4:#x}")
+        if lds_out:
+            a("v_add_u32 v96, s41, %[lout]")
+        if lds_in:
+            a("v_add_u32 v95, s41, %[lin]")
+    elif lds_out:
+        a(f"v_add_u32 v96, {4 * C:#x}, v96")
 
 
 def slow_wait(a, label, resume, vreg, addr, sreg, reread=None, target="s40"):
@@ -394,7 +537,11 @@ def emit(spec=0, halfpub=True):
            "// one inline-asm block per (chunk rows C, half-chunk LDS links HL, strip role), R = %d ring rows, SPEC = %d, HALFPUB = %d."
            % (R, spec, halfpub),
            "// Operands: see F3Loop in sw_flow3.hip; fixed registers: tools/gen_flow3.py.",
-           "#pragma once", ""]
+           "#pragma once", "",
+           "// slot of row 0 in the rings of the half-chunk-link loops (tools/gen_flow3.py hl_slot0)",
+           "constexpr int F3_HL_SLOT0 = %d;" % hl_slot0(), ""]
+    if LINK_DROP:
+        out.insert(1, "// TIMING PROBE (F3_LINK_DROP=%s): WRONG SCORES, never commit." % ",".join(sorted(LINK_DROP)))
     for C, hl in ((32, 0), (16, 0), (32, 1)):
         for IN in ROLES_IN:
             for OUT_ in ROLES_OUT:
